@@ -9,6 +9,15 @@ per GPU; reads shard over ranks with the index replicated and no data-path colle
 (main.rs:152,162-173): torch.distributed (gloo) only carries the barriers,
 the max-over-ranks of the timed region and the per-rank parity verdicts.
 
+A plain run (`--gpus N --steps K --warmup W`) does what the headline needs and no more: it
+builds and uploads the C91 index, makes the rank's reads, runs W untimed and K timed encode
+steps and prints the line (metric, value, unit, ms_per_step, config; roofline, cpu_baseline
+and the parity verdicts null).  `--dump-outputs DIR` adds the last timed step's records and
+record offsets as .npy files (dump_outputs below); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.  Everything else listed here
+-- D91, C31, S91, the rooflines with their isolated launches, the CPU baselines and the
+parity checks against the oracle -- runs with `--full`, as do --configs / --mode.
+
 Workload:
   C91   per GPU 10M (N = 1) or 25M (N > 1: 8 x 25M = C91x8's 200M) synthetic 150 bp reads
         (uniform starts, 50 % reverse complemented, 1 % i.i.d. substitutions) against the
@@ -76,9 +85,17 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline C91 encode: D91, C31 and S91, the rooflines (isolated launches after "
+                         "the timed region), the CPU baselines and the parity checks against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed C91 encode steps, write what the last step returned (records and record "
+                         "offsets; a fixed seeded sample of reads plus whole-output totals) as DIR/<name>.npy")
     ap.add_argument("--configs", default=None,
-                    help="comma list of encode,decode,strains,c31 (default: all four at N=1, encode,decode at N>1)")
-    ap.add_argument("--mode", choices=["encode", "decode"], default=None, help="(legacy) = --configs <mode>")
+                    help="(--full) comma list of encode,decode,strains,c31 (default: all four at N=1, "
+                         "encode,decode at N>1)")
+    ap.add_argument("--mode", choices=["encode", "decode"], default=None,
+                    help="(--full, legacy) = --configs <mode>")
     ap.add_argument("--k", type=int, default=91)
     ap.add_argument("--reads-per-gpu", type=int, default=None, help="default 10M at N=1, 25M at N>1 (C91x8)")
     ap.add_argument("--batch-reads", type=int, default=0,
@@ -106,6 +123,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.mode and not args.configs:
         args.configs = args.mode
+    if not args.full and args.configs not in (None, "encode"):
+        ap.error("--configs/--mode other than encode need --full: a plain run times C91 encode alone")
+    if args.dump_outputs and args.configs and "encode" not in args.configs.split(","):
+        ap.error("--dump-outputs writes the C91 encode outputs: --configs must name encode")
     return args
 
 
@@ -348,6 +369,7 @@ class Pipe:
         ctx, o = self.ctxs[c], b["out"][c]
         if self.kind == "encode":
             ctx.encode_device(b["d_bases"], b["d_offs"], b["n"], sh.L, o["d_recs"], b["cap"], o["d_roffs"])
+            b["last_out"] = c  # the output buffers of the batch's latest encode (--dump-outputs)
         else:
             if not o.get("d_out"):
                 o["d_out"], o["d_ooffs"] = ctx.alloc(b["bases"] + 64), ctx.alloc((b["n"] + 1) * 8)
@@ -419,6 +441,58 @@ def records_of(ctx, b, a_read, b_read):
     lo, hi = int(ro[a_read]), int(ro[b_read])
     recs = ctx.d2h(np.zeros(hi - lo, dtype=np.uint64), o["d_recs"] + 8 * lo) if hi > lo else np.zeros(0, np.uint64)
     return recs, ro
+
+
+DUMP_SEED = 91
+DUMP_READS = 250_000  # sampled reads: 2 MB of read numbers + 4 MB of offsets
+DUMP_RECORDS = 3_000_000  # records of the sampled reads kept: 48 MB as (hi, lo) float64 pairs
+
+
+def dump_outputs(ctx, sh, out_dir, rank, world):
+    """--dump-outputs: what the last timed encode step returned to its caller -- every batch's
+    records and record offsets, from the output buffers its latest call wrote -- as float64
+    .npy files (a u64 record as its high and low 32-bit words, both exact in float64):
+      sample_reads            (m,)   read numbers (seeded by index, so sharding never changes them)
+      sample_record_offsets   (m, 2) [start, end) of each sampled read's records in the shard's output
+      sample_records          (r, 2) those records, hi and lo words
+      totals                  (4,)   reads, records, xor of every record's hi words, of its lo words
+    The sample is DUMP_READS reads drawn once with DUMP_SEED, cut where their records pass
+    DUMP_RECORDS: under 64 MB whatever the shard's size."""
+    import numpy as np
+    recs, roffs, base = [], [], 0
+    for b in sh.batches:
+        o = b["out"][b["last_out"]]
+        if b["n_recs"] > b["cap"]:
+            raise RuntimeError(f"{b['n_recs']} records in a buffer of {b['cap']}")
+        ro = ctx.d2h(np.empty(b["n"] + 1, dtype=np.uint64), o["d_roffs"])
+        if int(ro[-1]) != b["n_recs"]:
+            raise RuntimeError(f"record offsets end at {int(ro[-1])}, the call reported {b['n_recs']} records")
+        recs.append(ctx.d2h(np.empty(b["n_recs"], dtype=np.uint64), o["d_recs"]))
+        roffs.append(ro[:-1] + np.uint64(base))
+        base += b["n_recs"]
+    recs = recs[0] if len(recs) == 1 else np.concatenate(recs)
+    roffs = np.concatenate(roffs + [np.array([base], dtype=np.uint64)]).astype(np.int64)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(sh.n, size=min(DUMP_READS, sh.n), replace=False))
+    cnt = roffs[pick + 1] - roffs[pick]
+    pick = pick[:int(np.searchsorted(np.cumsum(cnt), DUMP_RECORDS, side="right"))]
+    start, end = roffs[pick], roffs[pick + 1]
+    cnt = end - start
+    where = np.repeat(start - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()))
+    lo32 = np.uint64(0xFFFFFFFF)
+
+    def words(r):
+        return np.stack([(r >> np.uint64(32)).astype(np.float64), (r & lo32).astype(np.float64)], axis=-1)
+
+    fold = np.bitwise_xor.reduce(recs) if len(recs) else np.uint64(0)
+    arrays = {"sample_reads": (sh.first + pick).astype(np.float64),
+              "sample_record_offsets": np.stack([start, end], axis=-1).astype(np.float64),
+              "sample_records": words(recs[where]),
+              "totals": np.concatenate([[float(sh.n), float(base)], words(fold)])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + (".npy" if world == 1 else f".rank{rank}.npy")), a)
+    log(f"[rank {rank}] --dump-outputs: {len(pick)} reads, {len(where)} records, "
+        f"{sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB in {out_dir}")
 
 
 def check_shard(ctx, orc, sh, seconds, full_decode, pin, dry):
@@ -511,7 +585,11 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    configs = (args.configs or ("encode,decode,strains,c31" if world == 1 else "encode,decode")).split(",")
+    if not args.full:  # a plain run: the headline alone (C91 encode timed; no oracle, no isolated launches)
+        configs = ["encode"]
+        args.no_cpu = True
+    else:
+        configs = (args.configs or ("encode,decode,strains,c31" if world == 1 else "encode,decode")).split(",")
     reads_per_gpu = args.reads_per_gpu or (10_000_000 if world == 1 else 25_000_000)
 
     import numpy as np
@@ -539,7 +617,8 @@ def main():
 
     import ntcomp_amd as nt
     from ntcomp_amd import shard as shard_mod
-    from oracle_lib import OracleIndex  # the checker / CPU baseline (test infrastructure)
+    if args.full:
+        from oracle_lib import OracleIndex  # the checker / CPU baseline (test infrastructure)
 
     def barrier():
         if dist is not None:
@@ -560,8 +639,8 @@ def main():
         return out
 
     nthreads = max(1, min(16, (os.cpu_count() or 8) // max(1, world)))
-    pmc, pmc_note = load_pmc(args.pmc_json, nt.device_source_hash())
-    alg = load_alg(ALG_JSON)
+    pmc, pmc_note = load_pmc(args.pmc_json, nt.device_source_hash()) if args.full else (None, "")
+    alg = load_alg(ALG_JSON) if args.full else {}
     # counters exist for the profiled workloads only (scripts/profile_bench.sh: the defaults)
     default_wl = (args.read_len, args.err_ppm, args.genome_bp, args.strains, args.strain_snp_ppm) == \
         (150, 10_000, 5_000_000, 10, 10_000)
@@ -621,17 +700,20 @@ def main():
         sh = Shard(nt, ctx, genome, first, n, L, args.err_ppm, args.batch_reads, nthreads, args.dry_run,
                    args.presort, n_out=len(ctxs))
         log(f"[rank {rank}] {label}{kk}: reads {first}..{first + n} in {len(sh.batches)} batch(es)")
-        orc = OracleIndex(index.n, kk, index.rows, index.C, index.lcs)
+        orc = OracleIndex(index.n, kk, index.rows, index.C, index.lcs) if args.full else None
         n_recs = None
         if not args.dry_run:
             encode_all_outputs(ctxs, sh)
             n_recs = sum(b["n_recs"] for b in sh.batches)
         enc = dec = None
         iso = {}  # isolated launches (one context, one call at a time): the roofline's denominator --
-        # with calls in flight, a launch shares the GPU with the other context's kernels
+        # with calls in flight, a launch shares the GPU with the other context's kernels (--full)
         n_iso = max(3, len(sh.batches))
         if want_enc and not args.dry_run:
             enc = timed(Pipe(ctxs, "encode"), sh, args.steps, args.warmup, barrier, sync, dist)
+            if args.dump_outputs and label == "C":
+                dump_outputs(ctx, sh, args.dump_outputs, rank, world)
+        if enc is not None and args.full:
             ip = Pipe(ctxs[:1], "encode")
             iso["encode"] = (timed(ip, sh, n_iso, 0, barrier, sync, dist)[1], list(ip.tms))
             encode_all_outputs(ctxs, sh)  # the timed calls alternate contexts: refresh every output
@@ -678,6 +760,8 @@ def main():
         out = {}
         if enc is not None:
             el, kms = enc
+            rl = None  # the roofline divides by isolated launches: --full
+        if enc is not None and args.full:
             b0 = sh.batches[0]
             units = [b["n"] for b in sh.batches]
             kavg, kmin = launch_ms(iso["encode"][0], units, b0["n"])
@@ -694,6 +778,7 @@ def main():
             rl["algorithmic"] = alg_encode(alg, f"C{kk}", b0["n"], kavg, rl.get("traffic"))
             if world > 1:
                 rl["aggregate"] = aggregate_roofline(gather({"traffic": rl.get("traffic"), "kernel_ms": kavg}), world)
+        if enc is not None:
             metric = METRIC if kk == 91 else METRIC.replace("k=91", f"k={kk}")
             out.update({"metric": metric, "value": round(units_all / el / 1e6, 2), "unit": "Mbases/s",
                         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -838,6 +923,7 @@ def main():
                          "decode": s.get("decode")})
 
     if rank == 0:
+        line["full"] = args.full
         line["wall_s"] = round(time.time() - t_start, 1)
         print(json.dumps(line), flush=True)
     for c in ctxs:

@@ -10,7 +10,7 @@ for i in $(seq 1 ${REPS:-2}); do
   for v in ${VARIANTS:-A cur}; do
     lib=ntcomp_amd/libntcomp_gpu_$v.so
     [ "$v" = cur ] && lib=ntcomp_amd/libntcomp_gpu.so
-    NTC_GPU_LIB=$lib timeout -k 10 300 python -u bench.py --configs $CONFIGS --no-cpu ${BENCH_ARGS:-} \
+    NTC_GPU_LIB=$lib timeout -k 10 300 python -u bench.py --full --configs $CONFIGS --no-cpu ${BENCH_ARGS:-} \
         > $OUT/${v}_$i.json 2> $OUT/${v}_$i.err
   done
 done

@@ -4,7 +4,7 @@ set -e
 mkdir -p gpurun_out/ab
 CFG=${1:-encode,strains}
 shift
-B="python -u bench.py --configs $CFG --no-cpu --steps 10 --warmup 3"
+B="python -u bench.py --full --configs $CFG --no-cpu --steps 10 --warmup 3"
 for i in 1 2; do
   for O in "$@"; do
     if [ "$O" = - ]; then A=""; n=default; else A="--opt $O"; n=$(echo "$O" | tr '=' '_'); fi

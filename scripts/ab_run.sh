@@ -4,7 +4,7 @@ set -e
 mkdir -p gpurun_out/ab
 CFG=${1:-encode,strains}
 shift
-B="python -u bench.py --configs $CFG --no-cpu --steps 10 --warmup 3 ${AB_ARGS:-}"
+B="python -u bench.py --full --configs $CFG --no-cpu --steps 10 --warmup 3 ${AB_ARGS:-}"
 for i in 1 2; do
   for L in "$@"; do
     n=$(basename $L .so)

@@ -8,7 +8,7 @@ shift
 for i in 1 2; do
   for spec in "$@"; do
     n="${spec%%|*}"; rest="${spec#*|}"; L="${rest%%|*}"; args="${rest#*|}"
-    B="python -u bench.py --configs $CFG --no-cpu --steps 10 --warmup 3 $args"
+    B="python -u bench.py --full --configs $CFG --no-cpu --steps 10 --warmup 3 $args"
     if [ "$L" = cur ]; then
       timeout -k 10 300 $B > gpurun_out/ab/$n.$i.json 2> gpurun_out/ab/$n.$i.err
     else

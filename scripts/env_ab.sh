@@ -9,6 +9,6 @@ shift
 for i in 1 2; do
   for spec in "$@"; do
     n="${spec%%|*}"; envs="${spec#*|}"
-    env $envs timeout -k 10 300 python -u bench.py --configs $CFG --no-cpu --steps 10 --warmup 3 > $O/$n.$i.json 2> $O/$n.$i.err
+    env $envs timeout -k 10 300 python -u bench.py --full --configs $CFG --no-cpu --steps 10 --warmup 3 > $O/$n.$i.json 2> $O/$n.$i.err
   done
 done

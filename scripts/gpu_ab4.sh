@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=${O:-gpurun_out/ab4}
 mkdir -p $O
 for s in 12 16 24 12 16 24; do
-  timeout -k 10 200 python -u bench.py --configs strains --no-cpu --opt ent_slots=$s > $O/s91_slots$s.json 2>> $O/s91.err || exit 1
+  timeout -k 10 200 python -u bench.py --full --configs strains --no-cpu --opt ent_slots=$s > $O/s91_slots$s.json 2>> $O/s91.err || exit 1
 done
 timeout -k 10 400 python3 -u scripts/host_ceiling.py --reads 10000000 --threads 16 --ctx 2 --reps 2 \
     --out /tmp/ntc_ceiling > $O/ceiling10M.jsonl 2> $O/ceiling10M.err || exit 1

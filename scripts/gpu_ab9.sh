@@ -8,6 +8,6 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_pack.py tests/test_gpu_pari
 for v in A cur C; do
   lib=ntcomp_amd/libntcomp_gpu_$v.so; [ $v = cur ] && lib=ntcomp_amd/libntcomp_gpu.so
   NTC_GPU_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$v -o kt --output-format csv -- \
-      python3 bench.py --configs encode,c31 --no-cpu --steps 10 --warmup 2 > $O/kt_$v.json 2> $O/kt_$v.err || exit 1
+      python3 bench.py --full --configs encode,c31 --no-cpu --steps 10 --warmup 2 > $O/kt_$v.json 2> $O/kt_$v.err || exit 1
 done
 OUT=$O/pack CONFIGS=encode,c31 VARIANTS="A cur C" REPS=3 timeout -k 10 600 bash scripts/ab_bench.sh > $O/pack.log 2>&1 || exit 1

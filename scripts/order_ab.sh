@@ -6,7 +6,7 @@ O=gpurun_out/order_ab
 mkdir -p $O
 for i in 1 2; do
   for v in 0 1; do
-    NTC_READ_ORDER=$v timeout -k 10 300 python -u bench.py --configs ${CFG:-encode,c31,strains} --steps 10 --warmup 3 --no-cpu \
+    NTC_READ_ORDER=$v timeout -k 10 300 python -u bench.py --full --configs ${CFG:-encode,c31,strains} --steps 10 --warmup 3 --no-cpu \
         > $O/ord$v.$i.json 2> $O/ord$v.$i.err
   done
 done

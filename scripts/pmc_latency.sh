@@ -11,7 +11,7 @@ B="--configs $CFG --no-cpu --steps 3 --warmup 0 ${OPTS:-}"
 run() {
   local name=$1; shift
   NTC_GPU_LIB=${LIB:-} timeout -s KILL 120 rocprofv3 --kernel-include-regex 'k_ms4|k_parse4' --pmc "$@" \
-      -d $OUT/${TAG}_$name -o $name --output-format csv -- python3 bench.py $B > $OUT/${TAG}_$name.out 2>&1 || exit 1
+      -d $OUT/${TAG}_$name -o $name --output-format csv -- python3 bench.py --full $B > $OUT/${TAG}_$name.out 2>&1 || exit 1
 }
 run ta TA_BUSY_avr TA_TA_BUSY_sum TD_TD_BUSY_sum GRBM_GUI_ACTIVE
 run tcp TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TOTAL_CACHE_ACCESSES_sum

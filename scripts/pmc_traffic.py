@@ -10,7 +10,7 @@ Per workload and kernel, the mean per launch of:
   dram_read_bytes = 32 * TCC_EA0_RDREQ_DRAM_32B
   fetch_size_bytes = the rocprofv3 FETCH_SIZE expression for gfx950 from the same counters
 Kernel durations come from the kernel-trace pass of the default bench command, split into
-its workloads by dispatch order (bench.py with --inflight I contexts):
+its workloads by dispatch order (bench.py --full with --inflight I contexts):
   C91 encode calls: I (every context's outputs) + W + K (timed, I in flight) + N isolated
       (one at a time, I > 1 only: the roofline's denominator) + I (outputs refreshed)
   D91 decode calls: W + K (timed) + N isolated (I > 1 only)
@@ -127,8 +127,8 @@ def main():
     out = {"device_source_hash": nt.device_source_hash(), "collected": time.strftime("%Y-%m-%d %H:%M"),
            "source": f"scripts/profile_bench.sh -> {os.path.relpath(a.prof_dir, REPO)}", "workloads": {}}
     md = ["# rocprofv3 summary (bench.py, one MI355X)", "",
-          f"device source hash `{out['device_source_hash']}`; kernel-trace pass = `bench.py --steps {a.steps} "
-          f"--warmup {a.warmup}` (all configs, --inflight {a.inflight}); counter passes = `bench.py --configs <w> --no-cpu --steps 3 "
+          f"device source hash `{out['device_source_hash']}`; kernel-trace pass = `bench.py --full --steps {a.steps} "
+          f"--warmup {a.warmup}` (all configs, --inflight {a.inflight}); counter passes = `bench.py --full --configs <w> --no-cpu --steps 3 "
           f"--warmup 0`, one pass per counter group.", "",
           "| workload | kernel | avg ms (trace) | read B/launch | write B/launch | B/unit | RDREQ/unit | 32/64/128 B req | "
           "DRAM rd B | L2 hit | GB/s | frac of 8 TB/s |", "|---|---|---|---|---|---|---|---|---|---|---|---|"]

@@ -19,7 +19,7 @@ run() {  # name, limit, bench args, rocprof args...
   local name=$1 secs=$2 bargs=$3; shift 3
   echo "=== $name ($(date +%T))" >&2
   timeout -k 10 "$secs" rocprofv3 "$@" -d "$OUT/$name" -o "$name" --output-format csv -- \
-      python3 bench.py $bargs > "$OUT/$name.stdout" 2> "$OUT/$name.stderr"
+      python3 bench.py --full $bargs > "$OUT/$name.stdout" 2> "$OUT/$name.stderr"
   local rc=$?
   echo "=== $name rc=$rc ($(date +%T))" >&2
   if [ $rc -ne 0 ]; then tail -20 "$OUT/$name.stderr" >&2; exit $rc; fi
