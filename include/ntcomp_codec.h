@@ -167,6 +167,27 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
                           uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
                           uint64_t *n_bases, int64_t *bad_read);
 
+/* ---- exception side file ("NTCX", version 1) ---------------------------------------------- */
+/* The exception runs of an encoded.dat written under policy keep (ntcomp_gpu.h, "non-ACGT
+ * symbols"), beside it and never inside it.  Everything little-endian:
+ *   header, 32 bytes: "NTCX", u32 version = 1, u8 sub (the substitute base), 23 zero bytes
+ *   sections until the end of the file: u64 n_runs, u64 0, then n_runs runs of 24 bytes
+ *     (ntc_nx_run: u64 read, u32 pos, u32 len, u32 sym, u32 0)
+ * `read` counts the reads of the blocks that were written: N - 1 of the ">seq.N" line decode
+ * prints (a block the pipeline drops takes its runs with it, and later reads move down).
+ * Across the whole file the runs increase strictly by (read, pos) and do not overlap.  A file
+ * without runs is the header alone.
+ * ntc_nx_write (host): the header when with_header, then one section of n_runs runs when
+ * n_runs > 0, to fd.  NTC_ERR_IO on a short write, NTC_ERR_INVALID_ARG for a sub other than
+ * A/C/G/T.
+ * ntc_nx_read (host): parses and validates the file at path; *runs (all sections, in file
+ * order; free with ntc_buffer_free; null when there are none), *n_runs, *sub.  NTC_ERR_IO if
+ * it cannot be read; NTC_ERR_FORMAT for a bad magic or version, a truncated header, section
+ * or run, a non-zero pad, len = 0, pos + len past 2^32, a sym that is not one of the twelve
+ * symbols, runs out of order or overlapping, a sub that is not A/C/G/T.                      */
+int ntc_nx_write(int fd, const ntc_nx_run *runs, uint64_t n_runs, uint32_t sub, int with_header);
+int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t *sub);
+
 #ifdef __cplusplus
 }
 #endif

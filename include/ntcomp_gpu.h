@@ -190,6 +190,50 @@ int ntc_decode_status(ntc_ctx *ctx, uint64_t *n_reads, uint64_t *n_bases);
 int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64_t n_reads, uint64_t n_bases,
                      uint64_t first_id, uint8_t *out, uint64_t out_capacity, uint64_t *out_len);
 
+/* ---- non-ACGT symbols (N and the IUPAC codes) ------------------------------------- */
+/* After normalize(true) a read holds A/C/G/T and twelve more symbols: N - B D H V R Y S W K
+ * M.  ntc_ctx_set_option(ctx, "non_acgt", policy) says what the host-buffer encode calls
+ * (ntc_encode_batch, ntc_encode_pack_batch, ntc_encode_pack_fastq) do with those twelve:
+ *   0  error (default): NTC_ERR_INVALID_BASE for the read, as ever.
+ *   1  mask (lossy): each is replaced by the substitute base before encoding.
+ *   2  keep (lossless): masked as under 1, and the replaced symbols are kept as exception
+ *      runs (ntc_encode_exceptions); a decode call given them (ntc_decode_set_exceptions)
+ *      puts them back.
+ * The substitute base is the lowest of A, C, G, T the index contains (read-only option
+ * "nx_sub": its ASCII code after an upload).  The records are exactly those of the masked
+ * reads, so any decoder without the runs returns the masked reads.  Under every policy an
+ * A/C/G/T the index does not contain is NTC_ERR_INVALID_BASE and an empty read
+ * NTC_ERR_EMPTY_READ.  Read-only options "nx_runs" / "nx_bases": the last encode call's run
+ * and masked-base counts (both policies 1 and 2).
+ *
+ * An exception run is a maximal stretch of one identical symbol inside one read: NNRRN is
+ * three runs, and a run never crosses a read boundary.  Runs are listed in increasing
+ * (read, pos) order; that form is canonical.
+ *
+ * ntc_encode_batch_device works on the caller's const buffer, which it cannot mask: with a
+ * policy other than 0 it returns NTC_ERR_UNSUPPORTED.  ntc_decode_batch_device ignores (and
+ * keeps) runs set with ntc_decode_set_exceptions.                                        */
+typedef struct ntc_nx_run {
+    uint64_t read;     /* read index, relative to the call's first read                      */
+    uint32_t pos, len; /* first position inside the read, symbols (> 0)                      */
+    uint32_t sym;      /* ASCII code, one of the twelve                                      */
+    uint32_t reserved; /* 0                                                                  */
+} ntc_nx_run;          /* 24 bytes */
+/* The runs of the last ntc_encode_batch, ntc_encode_pack_batch or ntc_encode_pack_fastq call
+ * on this context under policy 2 (no runs under 0 and 1); for ntc_encode_batch they cover
+ * all of its device passes.  *n_runs = their number; NTC_ERR_CAPACITY (nothing copied) when
+ * capacity is smaller.                                                                     */
+int ntc_encode_exceptions(ntc_ctx *ctx, ntc_nx_run *out, uint64_t capacity, uint64_t *n_runs);
+/* Runs for the next ntc_decode_batch, ntc_decode_fasta or ntc_decode_fasta_unpacked call on
+ * this context (copied; read relative to that call's first read), sub = the substitute base
+ * recorded at encode time.  That call checks every run -- read < its reads, len > 0, pos +
+ * len inside the read, sym one of the twelve, every byte under the run equal to sub (which
+ * catches runs that belong to another encoding) -- and writes sym over the run; a run that
+ * fails a check makes the call return NTC_ERR_FORMAT.  The runs are dropped once a call has
+ * used them, whatever it returned; a call that only reports sizes (NTC_ERR_CAPACITY) keeps
+ * them.  n_runs = 0 drops pending runs.                                                   */
+int ntc_decode_set_exceptions(ntc_ctx *ctx, const ntc_nx_run *runs, uint64_t n_runs, uint32_t sub);
+
 /* Timings of the last encode/decode call (synchronises). */
 int ntc_last_timing(ntc_ctx *ctx, ntc_timing *out);
 

@@ -68,6 +68,34 @@ int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
 int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_pipeline_opts *opts,
                     ntc_pipeline_stats *stats);
 
+/* ---- reads with N and IUPAC symbols ------------------------------------------------------- */
+/* ntc_encode_file under a non-ACGT policy (ntcomp_gpu.h): NTC_NX_ERROR = ntc_encode_file;
+ * NTC_NX_MASK replaces each such symbol by the substitute base (lossy); NTC_NX_KEEP also
+ * writes the replaced symbols as exception runs to nx_fd (not closed), in the "NTCX" format
+ * of ntcomp_codec.h -- always, so a file without such symbols gets the header alone.  nx_fd
+ * must be >= 0 under NTC_NX_KEEP and -1 otherwise (NTC_ERR_INVALID_ARG).  encoded.dat has
+ * the reference's layout under every policy; decoded without the side file it gives the
+ * masked reads.  The contexts' "non_acgt" option is set for the call and left at 0.
+ * A run's `read` counts the reads of the blocks written: a block the pipeline drops (no long
+ * or no short record, App. B.3) takes its runs with it and later reads move down, exactly
+ * as decode numbers its ">seq.N" lines.
+ * nx (may be NULL): runs = runs written to the side file (NTC_NX_MASK: runs found), bases =
+ * symbols replaced (dropped blocks included), reads = reads with a run in the side file
+ * (NTC_NX_MASK: 0), runs_in_dropped_blocks = runs not written because their block was
+ * dropped (NTC_NX_MASK: 0).
+ * ntc_decode_file_nx: ntc_decode_file, with the side file at nx_path (NULL: none) read once
+ * (ntc_nx_read) and each batch's runs put back before its text is formatted.  A side file
+ * that does not belong to this encoding -- a run past a read's end or over a base that is
+ * not the recorded substitute -- is NTC_ERR_FORMAT.                                        */
+enum { NTC_NX_ERROR = 0, NTC_NX_MASK = 1, NTC_NX_KEEP = 2 };
+typedef struct ntc_nx_stats {
+    uint64_t runs, bases, reads, runs_in_dropped_blocks;
+} ntc_nx_stats;
+int ntc_encode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx);
+int ntc_decode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,19 @@ EXPORTED = [
     "ntc_fastx_set_threads", "ntc_host_threads", "ntc_encode_file", "ntc_decode_fasta",
     "ntc_decode_file", "ntc_build_index_device", "ntc_build_index_device_ex", "ntc_index_set_prefix_precalc",
     "ntc_index_prefix_table", "ntc_index_share", "ntc_index_prepare", "ntc_index_upload_prepared", "ntc_index_prep_free",
+    "ntc_encode_exceptions", "ntc_decode_set_exceptions", "ntc_nx_write", "ntc_nx_read", "ntc_encode_file_nx",
+    "ntc_decode_file_nx",
 ]
+
+# non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
+NON_ACGT = {"error": 0, "mask": 1, "keep": 2}
+NX_SYMBOLS = b"N-BDHVRYSWKM"
+# ntc_nx_run: an exception run, 24 bytes
+NX_RUN = np.dtype([("read", "<u8"), ("pos", "<u4"), ("len", "<u4"), ("sym", "<u4"), ("reserved", "<u4")])
+
+
+def _policy_code(non_acgt):
+    return NON_ACGT[non_acgt] if isinstance(non_acgt, str) else int(non_acgt)
 
 
 class NtcError(RuntimeError):
@@ -87,6 +99,11 @@ class PipelineStats(ctypes.Structure):
                 ("wall_s", ctypes.c_double), ("alloc_s", ctypes.c_double), ("first_batch_s", ctypes.c_double),
                 ("reader_done_s", ctypes.c_double), ("gpu_done_s", ctypes.c_double), ("threads", ctypes.c_int32), ("gpu_parsed", ctypes.c_int32),
                 ("bad_read", ctypes.c_int64), ("error", ctypes.c_char * 256)]
+
+
+class NxStats(ctypes.Structure):
+    """ntc_nx_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("runs", "bases", "reads", "runs_in_dropped_blocks")]
 
 
 class BuildOpts(ctypes.Structure):
@@ -226,6 +243,14 @@ def lib():
         "ntc_unpack_streams": (I, [P, P, u64, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "ntc_unpacked_records": (I, [P, P, u64, ctypes.POINTER(u64)]),
         "ntc_decode_fasta_unpacked": (I, [P, u64, P, u64, ctypes.POINTER(u64)]),
+        "ntc_encode_exceptions": (I, [P, P, u64, ctypes.POINTER(u64)]),
+        "ntc_decode_set_exceptions": (I, [P, P, u64, u32]),
+        "ntc_nx_write": (I, [I, P, u64, u32, I]),
+        "ntc_nx_read": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
+        "ntc_encode_file_nx": (I, [P, I, ctypes.c_char_p, I, I, I, ctypes.POINTER(PipelineOpts),
+                                   ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats)]),
+        "ntc_decode_file_nx": (I, [P, I, ctypes.c_char_p, ctypes.c_char_p, I, ctypes.POINTER(PipelineOpts),
+                                   ctypes.POINTER(PipelineStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -423,10 +448,58 @@ class GpuContext:
         self._check(self.L.ntc_index_info(self.h, ctypes.byref(n), ctypes.byref(k), ctypes.byref(b)), "info")
         return int(n.value), int(k.value), int(b.value)
 
+    # ---- non-ACGT symbols ----------------------------------------------------------
+    class _Policy:
+        """`with ctx._policy(p)`: the context's "non_acgt" option is p inside (None: left alone)."""
+
+        def __init__(self, ctx, non_acgt):
+            self.ctx, self.new = ctx, None if non_acgt is None else _policy_code(non_acgt)
+
+        def __enter__(self):
+            if self.new is not None:
+                self.old = self.ctx.get_option("non_acgt")
+                self.ctx.set_option("non_acgt", self.new)
+
+        def __exit__(self, *exc):
+            if self.new is not None:
+                self.ctx.set_option("non_acgt", self.old)
+
+    def _policy(self, non_acgt):
+        return GpuContext._Policy(self, non_acgt)
+
+    def exceptions(self):
+        """The exception runs of the last encode / encode_pack / encode_pack_fastq call under
+        policy keep (ntc_encode_exceptions), as a structured array of dtype NX_RUN in (read,
+        pos) order."""
+        n = ctypes.c_uint64()
+        rc = self.L.ntc_encode_exceptions(self.h, None, 0, ctypes.byref(n))
+        if rc not in (0, 5):
+            self._check(rc, "ntc_encode_exceptions")
+        runs = np.zeros(n.value, dtype=NX_RUN)
+        if n.value:
+            self._check(self.L.ntc_encode_exceptions(self.h, _p(runs), len(runs), ctypes.byref(n)),
+                        "ntc_encode_exceptions")
+        return runs
+
+    def set_exceptions(self, runs, sub):
+        """Exception runs (dtype NX_RUN, read relative to the next call's first read) and the
+        substitute base for the next decode / decode_fasta call (ntc_decode_set_exceptions)."""
+        runs = np.ascontiguousarray(runs, dtype=NX_RUN)
+        sub = sub if isinstance(sub, int) else ord(sub)
+        self._check(self.L.ntc_decode_set_exceptions(self.h, _p(runs) if len(runs) else None, len(runs), sub),
+                    "ntc_decode_set_exceptions")
+
+    @property
+    def substitute(self):
+        """The substitute base of the uploaded index (option "nx_sub"), as an int."""
+        return self.get_option("nx_sub")
+
     # ---- encode ------------------------------------------------------------------
-    def encode(self, bases, offsets):
+    def encode(self, bases, offsets, non_acgt=None):
         """-> (uint64 records, uint64 rec_offsets[n_reads+1]); raises NtcError(code) with
-        .bad_read on a failing read."""
+        .bad_read on a failing read.  non_acgt ("error", "mask" or "keep"; None leaves the
+        context's option alone): the call runs under that policy and returns (records,
+        rec_offsets, exception runs)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nreads = len(offsets) - 1
@@ -434,12 +507,15 @@ class GpuContext:
         recs = np.zeros(total + 1, dtype=np.uint64)
         roff = np.zeros(nreads + 1, dtype=np.uint64)
         bad = ctypes.c_int64(-1)
-        rc = self.L.ntc_encode_batch(self.h, _p(bases), _p(offsets), nreads, _p(recs), len(recs), _p(roff),
-                                     ctypes.byref(bad))
+        with self._policy(non_acgt):
+            rc = self.L.ntc_encode_batch(self.h, _p(bases), _p(offsets), nreads, _p(recs), len(recs), _p(roff),
+                                         ctypes.byref(bad))
         if rc:
             e = NtcError(rc, self.L.ntc_last_error(self.h).decode(errors="replace"))
             e.bad_read = bad.value
             raise e
+        if non_acgt is not None:
+            return recs[: int(roff[-1])], roff, self.exceptions()
         return recs[: int(roff[-1])], roff
 
     def decode(self, recs):
@@ -497,10 +573,11 @@ class GpuContext:
                                                   ctypes.byref(used)), "ntc_pack_blocks_device")
         return list(metas)[:nb], int(used.value)
 
-    def encode_pack(self, bases, offsets, block_reads=65536):
+    def encode_pack(self, bases, offsets, block_reads=65536, non_acgt=None):
         """Reads -> packed blocks (ntc_encode_pack_batch): the records stay in HBM and the
         GPU packer writes each block's four streams; returns (list of BlockMeta, payload
-        bytes) ready for deflate_block."""
+        bytes) ready for deflate_block.  With non_acgt (as for encode) the exception runs
+        come third."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nreads = len(offsets) - 1
@@ -508,8 +585,9 @@ class GpuContext:
         metas = (BlockMeta * max(nb, 1))()
         out, used, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_int64(-1)
         b = bases if len(bases) else np.zeros(1, dtype=np.uint8)
-        rc = self.L.ntc_encode_pack_batch(self.h, _p(b), _p(offsets), nreads, block_reads, metas, ctypes.byref(out),
-                                          ctypes.byref(used), ctypes.byref(bad))
+        with self._policy(non_acgt):
+            rc = self.L.ntc_encode_pack_batch(self.h, _p(b), _p(offsets), nreads, block_reads, metas,
+                                              ctypes.byref(out), ctypes.byref(used), ctypes.byref(bad))
         if rc:
             e = NtcError(rc, self.L.ntc_last_error(self.h).decode(errors="replace"))
             e.bad_read = bad.value
@@ -518,6 +596,8 @@ class GpuContext:
             payload = ctypes.string_at(out.value, used.value) if used.value else b""
         finally:
             self.L.ntc_buffer_free(out)
+        if non_acgt is not None:
+            return list(metas)[:nb], payload, self.exceptions()
         return list(metas)[:nb], payload
 
     def parse_fastq(self, text, n_reads):
@@ -535,15 +615,18 @@ class GpuContext:
             raise e
         return bases[:nb.value].copy(), offs
 
-    def encode_pack_fastq(self, text, n_reads, block_reads=65536):
+    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None):
         """encode_pack on FASTQ text parsed on the GPU (ntc_encode_pack_fastq) -> (list of
-        BlockMeta, payload bytes, bases encoded)."""
+        BlockMeta, payload bytes, bases encoded).  With non_acgt (as for encode) the exception
+        runs come fourth."""
         t = np.frombuffer(bytes(text), dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
         nb = (n_reads + block_reads - 1) // block_reads
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
-        rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas, ctypes.byref(out),
-                                          ctypes.byref(used), ctypes.byref(nbases), ctypes.byref(bad))
+        with self._policy(non_acgt):
+            rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas,
+                                              ctypes.byref(out), ctypes.byref(used), ctypes.byref(nbases),
+                                              ctypes.byref(bad))
         if rc:
             self.L.ntc_buffer_free(out)
             e = NtcError(rc, self.L.ntc_last_error(self.h).decode(errors="replace"))
@@ -553,6 +636,8 @@ class GpuContext:
             payload = ctypes.string_at(out.value, used.value) if used.value else b""
         finally:
             self.L.ntc_buffer_free(out)
+        if non_acgt is not None:
+            return list(metas)[:nb], payload, int(nbases.value), self.exceptions()
         return list(metas)[:nb], payload, int(nbases.value)
 
     def encode_status(self):
@@ -814,29 +899,69 @@ def concat_streams(blocks):
 
 # ---- FASTX ingest ---------------------------------------------------------------------
 def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_bases=0, deflate="zlib",
-                host_parse=False):
+                host_parse=False, non_acgt=None, nx_fd=-1):
     """`ntcomp encode` file to file (ntc_encode_file, include/ntcomp_pipeline.h): FASTX ->
     GPU encode + block packer on every context -> deflate pool -> encoded.dat on out_fd.
     A plain FASTQ is parsed on the GPU unless host_parse.  Returns the per-stage stats as
-    a dict (gpu_parsed = batches parsed on the GPU); raises NtcError (with .bad_read)."""
-    return _run_pipeline("ntc_encode_file", ctxs, in_path, out_fd,
-                         PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate],
-                                      1 if host_parse else 0))
+    a dict (gpu_parsed = batches parsed on the GPU); raises NtcError (with .bad_read).
+    non_acgt ("error", "mask", "keep"; ntc_encode_file_nx): what becomes of N and IUPAC
+    symbols; "keep" writes their exception runs to nx_fd, and the stats gain an "nx" dict
+    (ntc_nx_stats)."""
+    o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
+    if non_acgt is None:
+        return _run_pipeline("ntc_encode_file", ctxs, in_path, out_fd, o)
+    nx = NxStats()
+    d = _run_pipeline("ntc_encode_file_nx", ctxs, in_path, out_fd, o, mid=(_policy_code(non_acgt), nx_fd),
+                      tail=(ctypes.byref(nx),))
+    d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
+    return d
 
 
-def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2):
+def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
     blocks before it without an error, like decode_block's Err ends the reference's loop
-    (src/main.rs:202): stats["dropped_blocks"] > 0 and stats["error"] say so."""
-    return _run_pipeline("ntc_decode_file", ctxs, in_path, out_fd, PipelineOpts(threads, blocks_per_batch, 0, 0, 0))
+    (src/main.rs:202): stats["dropped_blocks"] > 0 and stats["error"] say so.  nx_path: the
+    exception side file written by encode_file(non_acgt="keep"), whose symbols are put back
+    (ntc_decode_file_nx)."""
+    o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
+    if nx_path is None:
+        return _run_pipeline("ntc_decode_file", ctxs, in_path, out_fd, o)
+    return _run_pipeline("ntc_decode_file_nx", ctxs, in_path, out_fd, o, pre_fd=(os.fsencode(nx_path),))
 
 
-def _run_pipeline(fn, ctxs, in_path, out_fd, o):
+def read_exceptions(path):
+    """An exception side file ("NTCX", include/ntcomp_codec.h) parsed and validated by
+    ntc_nx_read -> (runs of dtype NX_RUN, substitute base as an int); NtcError(NTC_ERR_FORMAT)
+    if it is malformed."""
+    p, n, sub = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint32()
+    rc = lib().ntc_nx_read(os.fsencode(path), ctypes.byref(p), ctypes.byref(n), ctypes.byref(sub))
+    if rc:
+        raise NtcError(rc, f"ntc_nx_read({path})")
+    try:
+        runs = (np.frombuffer(ctypes.string_at(p.value, n.value * NX_RUN.itemsize), dtype=NX_RUN).copy()
+                if n.value else np.zeros(0, dtype=NX_RUN))
+    finally:
+        lib().ntc_buffer_free(p)
+    return runs, int(sub.value)
+
+
+def write_exceptions(fd, runs, sub, header=True):
+    """The side file's header (if header) and one section holding runs (if any) to fd
+    (ntc_nx_write); sections may follow one another, in (read, pos) order over the file."""
+    runs = np.ascontiguousarray(runs, dtype=NX_RUN)
+    sub = sub if isinstance(sub, int) else ord(sub)
+    rc = lib().ntc_nx_write(fd, _p(runs) if len(runs) else None, len(runs), sub, 1 if header else 0)
+    if rc:
+        raise NtcError(rc, "ntc_nx_write")
+
+
+def _run_pipeline(fn, ctxs, in_path, out_fd, o, pre_fd=(), mid=(), tail=()):
     arr = (ctypes.c_void_p * len(ctxs))(*[c.h.value for c in ctxs])
     st = PipelineStats()
-    rc = getattr(lib(), fn)(arr, len(ctxs), os.fsencode(in_path), out_fd, ctypes.byref(o), ctypes.byref(st))
+    rc = getattr(lib(), fn)(arr, len(ctxs), os.fsencode(in_path), *pre_fd, out_fd, *mid, ctypes.byref(o),
+                            ctypes.byref(st), *tail)
     d = {k: (getattr(st, k).decode(errors="replace") if k == "error" else getattr(st, k))
          for k, _ in PipelineStats._fields_}
     if rc:

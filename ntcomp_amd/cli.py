@@ -65,6 +65,23 @@ class _Stats:
             log(json.dumps({"stats": d, "wall_s": round(self.time() - self.t0, 3), **extra}))
 
 
+def _bad_args(msg):
+    """An argument error found after parsing: status 2, before anything is loaded or written
+    (the native CLI's bad_args, same messages)."""
+    log(f"ntcomp: {msg}")
+    raise SystemExit(2)
+
+
+def _check_nx_args(args):
+    """encode: --non-acgt error|mask|keep and --exceptions PATH go together only under keep."""
+    if args.non_acgt not in ("error", "mask", "keep"):
+        _bad_args("encode: --non-acgt: error, mask or keep")
+    if args.non_acgt == "keep" and not args.exceptions:
+        _bad_args("encode: --non-acgt keep requires --exceptions PATH")
+    if args.non_acgt != "keep" and args.exceptions is not None:
+        _bad_args("encode: --exceptions is only written under --non-acgt keep")
+
+
 def _read_list(path):
     """--input-list: one path, or tab-separated name and path, per line (main.rs:64-89)."""
     out = []
@@ -165,6 +182,7 @@ def cmd_encode(args):
     """main.rs:141-181 through the native pipeline (ntc_encode_file): plain FASTQ parsed
     on the GPU (--host-parse: on the host pool, as every other input is), GPU encode +
     block packer per context, deflate on the host pool, blocks written in file order."""
+    _check_nx_args(args)
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     log("Loading SBWT index...")
@@ -175,14 +193,24 @@ def cmd_encode(args):
         args.deflate = "adaptive" if nt.libdeflate_available() else "zlib"
     out = sys.stdout.buffer
     out.flush()
+    nx_file = None
     try:
+        if args.non_acgt == "keep":
+            try:
+                nx_file = open(args.exceptions, "wb")
+            except OSError:
+                raise SystemExit(f"ntcomp: encode: cannot write {args.exceptions}")
+        nx_args = {} if args.non_acgt == "error" else {"non_acgt": args.non_acgt,
+                                                       "nx_fd": nx_file.fileno() if nx_file else -1}
         res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, deflate=args.deflate,
-                                                  host_parse=args.host_parse)
+                                                  host_parse=args.host_parse, **nx_args)
     except nt.NtcError as e:
         bad = getattr(e, "bad_read", -1)
         raise SystemExit(f"ntcomp encode: {e}" + (f" (read {bad + 1})" if bad is not None and bad >= 0 else ""))
     finally:
+        if nx_file:
+            nx_file.close()
         for c in ctxs:
             c.close()
     if res["dropped_blocks"]:
@@ -193,7 +221,9 @@ def cmd_encode(args):
             st.acc[k[:-2]] = res[k]
     st.report(command="encode", gpus=len(ctxs), threads=res["threads"], reads=res["reads"], blocks=res["blocks"],
               dropped_blocks=res["dropped_blocks"], pipeline_wall_s=round(res["wall_s"], 3), deflate=args.deflate,
-              gpu_parsed_batches=res["gpu_parsed"])
+              gpu_parsed_batches=res["gpu_parsed"], non_acgt=args.non_acgt,
+              **{"nx_" + k: v for k, v in res.get("nx", dict.fromkeys(("runs", "bases", "reads",
+                                                                        "runs_in_dropped_blocks"), 0)).items()})
 
 
 def cmd_decode(args):
@@ -209,7 +239,7 @@ def cmd_decode(args):
     out.flush()
     try:
         res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, out.fileno(), threads=args.threads,
-                                                  blocks_per_batch=args.blocks_per_batch)
+                                                  blocks_per_batch=args.blocks_per_batch, nx_path=args.exceptions)
     except nt.NtcError as e:
         raise SystemExit(f"ntcomp decode: {e}")
     finally:
@@ -273,6 +303,11 @@ def main(argv=None):
     e.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
     e.add_argument("--host-parse", action="store_true",
                    help="parse a plain FASTQ on the host pool instead of the GPU")
+    e.add_argument("--non-acgt", default="error", metavar="POLICY",
+                   help="reads with N or IUPAC symbols: error (default) stops at the first, mask replaces each symbol "
+                        "by the substitute base (lossy), keep also writes the replaced symbols to the --exceptions "
+                        "file (lossless)")
+    e.add_argument("--exceptions", metavar="PATH", help="with --non-acgt keep: the side file to write")
     d = sub.add_parser("decode", help="Decode data written with Encode")
     d.add_argument("input_path", help="File with encoded fastX data.")
     d.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
@@ -283,6 +318,8 @@ def main(argv=None):
                    help="contexts per device sharing one index copy; calls alternate over them")
     d.add_argument("--blocks-per-batch", type=int, default=2, help="blocks per GPU call")
     d.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
+    d.add_argument("--exceptions", metavar="PATH",
+                   help="the side file of encode --non-acgt keep, whose symbols are put back")
     args = ap.parse_args(argv)
     if getattr(args, "threads", None) == 0:
         import ntcomp_amd as nt

@@ -28,10 +28,13 @@
 //     libdeflate), so they inflate identically but are not byte-identical to zlib-rs
 //     (parity level F is unpinned).
 #include <dlfcn.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
+#include <cstdio>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +45,7 @@
 #include "../../include/ntcomp_codec.h"
 #include "ntc_internal.h"
 #include "codec_params.h"
+#include "nonacgt_core.h"
 
 namespace {
 
@@ -793,5 +797,84 @@ int ntc_read_block_into(const uint8_t *data, uint64_t len, uint64_t *consumed, u
 }
 
 void ntc_buffer_free(void *p) { std::free(p); }
+
+// ---- exception side file "NTCX" (include/ntcomp_codec.h) ------------------------------
+static_assert(sizeof(ntc_nx_run) == 24, "ntc_nx_run is the file's run record");
+
+static bool nx_write_all(int fd, const void *p, size_t n) {
+    const uint8_t *b = (const uint8_t *)p;
+    while (n) {
+        const ssize_t w = ::write(fd, b, n);
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) return false;
+        b += w;
+        n -= (size_t)w;
+    }
+    return true;
+}
+
+int ntc_nx_write(int fd, const ntc_nx_run *runs, uint64_t n_runs, uint32_t sub, int with_header) {
+    if (fd < 0 || (n_runs && !runs) || !ntc::nx_is_base(sub)) return NTC_ERR_INVALID_ARG;
+    if (with_header) {
+        uint8_t h[32] = {'N', 'T', 'C', 'X', 1, 0, 0, 0, (uint8_t)sub};
+        if (!nx_write_all(fd, h, sizeof(h))) return NTC_ERR_IO;
+    }
+    if (n_runs) {
+        const uint64_t sec[2] = {n_runs, 0};  // little-endian hosts only, as the block container
+        if (!nx_write_all(fd, sec, sizeof(sec)) || !nx_write_all(fd, runs, n_runs * sizeof(ntc_nx_run))) return NTC_ERR_IO;
+    }
+    return NTC_OK;
+}
+
+int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t *sub) {
+    if (!path || !runs || !n_runs || !sub) return NTC_ERR_INVALID_ARG;
+    *runs = nullptr;
+    *n_runs = 0;
+    *sub = 0;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return NTC_ERR_IO;
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+    const bool io_bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (io_bad) return NTC_ERR_IO;
+    static const uint8_t magic[8] = {'N', 'T', 'C', 'X', 1, 0, 0, 0};
+    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
+    if (!ntc::nx_is_base(buf[8])) return NTC_ERR_FORMAT;
+    for (size_t i = 9; i < 32; i++)
+        if (buf[i]) return NTC_ERR_FORMAT;
+    std::vector<ntc_nx_run> all;
+    size_t at = 32;
+    while (at < buf.size()) {
+        uint64_t sec[2];
+        if (buf.size() - at < 16) return NTC_ERR_FORMAT;
+        std::memcpy(sec, buf.data() + at, 16);
+        at += 16;
+        if (sec[1] != 0 || sec[0] == 0 || sec[0] > (buf.size() - at) / sizeof(ntc_nx_run)) return NTC_ERR_FORMAT;
+        const size_t first = all.size();
+        all.resize(first + sec[0]);
+        std::memcpy(all.data() + first, buf.data() + at, sec[0] * sizeof(ntc_nx_run));
+        at += sec[0] * sizeof(ntc_nx_run);
+    }
+    for (size_t i = 0; i < all.size(); i++) {
+        const ntc_nx_run &r = all[i];
+        if (r.len == 0 || r.reserved != 0 || !ntc::nx_is_symbol(r.sym) || (uint64_t)r.pos + r.len > (1ull << 32))
+            return NTC_ERR_FORMAT;
+        if (i) {  // strictly after the run before it, and clear of it
+            const ntc_nx_run &p = all[i - 1];
+            if (r.read < p.read || (r.read == p.read && (uint64_t)r.pos < (uint64_t)p.pos + p.len)) return NTC_ERR_FORMAT;
+        }
+    }
+    if (!all.empty()) {
+        *runs = (ntc_nx_run *)std::malloc(all.size() * sizeof(ntc_nx_run));
+        if (!*runs) return NTC_ERR_CAPACITY;
+        std::memcpy(*runs, all.data(), all.size() * sizeof(ntc_nx_run));
+    }
+    *n_runs = all.size();
+    *sub = buf[8];
+    return NTC_OK;
+}
 
 }  // extern "C"

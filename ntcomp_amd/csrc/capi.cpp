@@ -19,6 +19,7 @@
 #include "codec_params.h"
 #include "derived.h"
 #include "kernels.h"
+#include "nonacgt_core.h"
 #include "ntc_internal.h"
 
 using namespace ntc;
@@ -41,7 +42,8 @@ enum WsSlot {
     WS_DEC_D, WS_Q, WS_E3, WS_NE, WS_COUNTER, WS_R2, WS_ED, WS_WAVECNT, WS_PACK_CHUNKS, WS_PACK_META,
     WS_PACK_PAYLOAD, WS_FA_BASES, WS_FA_OFFS, WS_FA_SCAN, WS_ES, WS_OBASE,
     WS_FQ_RAW, WS_FQ_TILES, WS_FQ_NL, WS_FQ_KEPT, WS_PACK_SEGS,
-    WS_UNP_PAY, WS_UNP_MARKS, WS_UNP_ST, WS_UNP_VALS, WS_UNP_RECS, WS_UNP_OUT, WS_COUNT
+    WS_UNP_PAY, WS_UNP_MARKS, WS_UNP_ST, WS_UNP_VALS, WS_UNP_RECS, WS_UNP_OUT,
+    WS_NX_BITS, WS_NX_RUNS, WS_NX_PATCH, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -117,6 +119,18 @@ struct ntc_ctx {
     int64_t upload_host_us = 0, upload_total_us = 0;  // last ntc_index_upload: host derive / total
     uint64_t max_pass_bases = 1ULL << 30;  // host-buffer calls split into device passes of at most this
     double last_pack_ms = 0;               // last ntc_pack_blocks_device: both packer kernels
+    // non-ACGT symbols (nonacgt.hip): the policy (0 error, 1 mask, 2 keep), the last encode
+    // call's counts and runs, the runs waiting for the next decode call
+    int nx_policy = 0;
+    uint64_t nx_runs = 0, nx_bases = 0;
+    uint64_t nx_cap = 0, nx_cap_hint = 0;  // the run list of the call in flight; what an earlier call needed
+    void *nx_d_runs = nullptr;
+    std::vector<ntc_nx_run> nx_list;
+    std::vector<ntc_nx_run> nx_pending;
+    std::vector<ntc_nx_run> nx_pieces;     // the slices of the decode pass in flight (source of an async copy)
+    uint32_t nx_pending_sub = 0;
+    bool nx_has_pending = false;
+    FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
 
@@ -426,6 +440,143 @@ int read_status(ntc_ctx *ctx, int64_t *bad_index) {
     }
 }
 
+
+// ---- non-ACGT symbols (nonacgt.hip) ---------------------------------------------------
+// Before an encode of staged bases (the library's own, writable copy): flag, list the runs
+// (policy keep), substitute.  Asynchronous; the counts reach the host in mailbox words 4 and
+// 5 with the encode call's own status sync (nx_collect).  Policy 0 launches nothing.
+void nx_begin(ntc_ctx *ctx) {  // a host-buffer encode call starts: nothing of the last one is left
+    ctx->nx_runs = ctx->nx_bases = 0;
+    ctx->nx_list.clear();
+}
+int nx_mask(ntc_ctx *ctx, uint8_t *d_bases, const uint64_t *d_offs, uint64_t n_reads, uint64_t total) {
+    ctx->nx_cap = 0;
+    if (ctx->nx_policy == 0) return NTC_OK;
+    ctx->h_box[4] = ctx->h_box[5] = 0;  // (the last call's kernels are done: every encode call ends synchronised)
+    if (n_reads == 0) return NTC_OK;
+    if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
+    const uint32_t sub = nx_substitute(ctx->dix.absent);
+    if (!sub) return set_err(ctx, NTC_ERR_INVALID_BASE, "the index contains none of A, C, G, T");
+    // a run's pos and len are 32-bit: a pass below 2^32 bases cannot overflow them
+    if (total >= (1ull << 32))
+        return set_err(ctx, NTC_ERR_CAPACITY, "non_acgt mask / keep: 2^32 bases or more in one device pass: split the batch");
+    NxArgs a{};
+    a.bases = d_bases;
+    a.offs = d_offs;
+    a.n_reads = n_reads;
+    a.total = total;
+    a.n_words = nx_words(total);
+    const uint64_t W = a.n_words;
+    void *p, *tmp;
+    int rc;
+    // M, S, E, soff, eoff (W + 1 words each, 8-byte aligned), counts, then cnt_s, cnt_e
+    if ((rc = ensure(ctx, WS_NX_BITS, (5 * (W + 1) + 2) * 8 + 2 * (W + 1) * 4, &p))) return rc;
+    a.M = (uint64_t *)p;
+    a.S = a.M + (W + 1);
+    a.E = a.S + (W + 1);
+    a.soff = a.E + (W + 1);
+    a.eoff = a.soff + (W + 1);
+    a.counts = a.eoff + (W + 1);
+    a.cnt_s = (uint32_t *)(a.counts + 2);
+    a.cnt_e = a.cnt_s + (W + 1);
+    if ((rc = ensure(ctx, WS_SCANTMP, scan_tmp_words(std::max(W, n_reads) + 1) * 8, &tmp))) return rc;
+    if (ctx->nx_policy == 2) {
+        // room for a run per 16 bases, or what an earlier call needed; a call that finds
+        // more is staged and run again with the exact room (nx_collect)
+        ctx->nx_cap = std::min<uint64_t>(std::max<uint64_t>(total / 16 + 4096, ctx->nx_cap_hint), total + 1);
+        if ((rc = ensure(ctx, WS_NX_RUNS, ctx->nx_cap * sizeof(ntc_nx_run), &p))) return rc;
+        ctx->nx_d_runs = p;
+        a.runs = (NxRun *)p;
+        a.run_cap = ctx->nx_cap;
+    }
+    a.box = ctx->h_box;
+    a.sub = sub;
+    a.status = ctx->d_status;
+    launch_nx_mask(a, (uint64_t *)tmp, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+
+// After the encode call's status sync: the counts, and under policy keep the runs, appended
+// to the context's list with read_base added.  *again: the list was too short -- the caller
+// stages the bases afresh (they are masked by now) and runs the call again.
+int nx_collect(ntc_ctx *ctx, uint64_t read_base, bool *again) {
+    *again = false;
+    if (ctx->nx_policy == 0) return NTC_OK;
+    const uint64_t n = ((volatile uint64_t *)ctx->h_box)[4], nb = ((volatile uint64_t *)ctx->h_box)[5];
+    if (ctx->nx_policy == 2 && n > ctx->nx_cap) {
+        ctx->nx_cap_hint = n + n / 4;
+        *again = true;
+        return NTC_OK;
+    }
+    ctx->nx_runs += n;
+    ctx->nx_bases += nb;
+    if (ctx->nx_policy != 2 || n == 0) return NTC_OK;
+    const size_t at = ctx->nx_list.size();
+    ctx->nx_list.resize(at + n);
+    HIP_TRY(ctx, hipMemcpy(ctx->nx_list.data() + at, ctx->nx_d_runs, n * sizeof(ntc_nx_run), hipMemcpyDeviceToHost));
+    if (read_base)
+        for (size_t i = at; i < at + n; i++) ctx->nx_list[i].read += read_base;
+    return NTC_OK;
+}
+
+// Decode side: the pending runs with read in [r0, r0 + n_reads) over that pass's decoded
+// bases and offsets (read offsets from 0), long runs cut into slices for k_nx_patch; then
+// the status mailbox again, as the patch may have set the status.
+int nx_patch(ntc_ctx *ctx, const std::vector<ntc_nx_run> &runs, uint32_t sub, uint64_t r0, uint64_t n_reads,
+             uint8_t *d_bases, const uint64_t *d_offs) {
+    constexpr uint32_t kSlice = 1u << 16;
+    auto lo = std::lower_bound(runs.begin(), runs.end(), r0,
+                               [](const ntc_nx_run &x, uint64_t v) { return x.read < v; });
+    auto hi = std::lower_bound(lo, runs.end(), r0 + n_reads, [](const ntc_nx_run &x, uint64_t v) { return x.read < v; });
+    if (lo == hi) return NTC_OK;
+    std::vector<ntc_nx_run> &pc = ctx->nx_pieces;
+    pc.clear();
+    pc.reserve((size_t)(hi - lo));
+    for (auto it = lo; it != hi; ++it) {
+        ntc_nx_run r = *it;
+        r.read -= r0;
+        // a slice must stay a run that fits, so pos + len overflowing 32 bits is cut to fail whole
+        if ((uint64_t)r.pos + r.len > 0xFFFFFFFFull || r.len <= kSlice) {
+            pc.push_back(r);
+            continue;
+        }
+        for (uint32_t done = 0; done < it->len; done += kSlice) {
+            r.pos = it->pos + done;
+            r.len = std::min(kSlice, it->len - done);
+            pc.push_back(r);
+        }
+    }
+    void *d_pc;
+    int rc;
+    if ((rc = ensure(ctx, WS_NX_PATCH, pc.size() * sizeof(ntc_nx_run), &d_pc))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_pc, pc.data(), pc.size() * sizeof(ntc_nx_run), hipMemcpyHostToDevice, ctx->stream));
+    NxPatchArgs a{};
+    a.runs = (const NxRun *)d_pc;
+    a.n = pc.size();
+    a.bases = d_bases;
+    a.offs = d_offs;
+    a.n_reads = n_reads;
+    a.sub = sub;
+    a.status = ctx->d_status;
+    launch_nx_patch(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ctx->box_valid && ctx->last == kDecode)
+        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
+                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+
+// the pending runs leave the context: the call that takes them uses them once
+bool nx_take_pending(ntc_ctx *ctx, std::vector<ntc_nx_run> &runs, uint32_t &sub) {
+    runs.clear();
+    if (!ctx->nx_has_pending) return false;
+    runs.swap(ctx->nx_pending);
+    sub = ctx->nx_pending_sub;
+    ctx->nx_has_pending = false;
+    return !runs.empty();
+}
 
 // GPU packer (pack.hip) over the records of n_reads reads in HBM: block b = reads
 // [b * block_reads, ...).  Pass 1 on the device, Rice parameters and payload layout on the
@@ -1103,6 +1254,11 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
         ctx->epool_per_base = ctx->rpool_per_base = 0.0;
         return NTC_OK;
     }
+    if (std::strcmp(key, "non_acgt") == 0) {  // N and IUPAC symbols: 0 error, 1 mask, 2 keep (ntcomp_gpu.h)
+        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)");
+        ctx->nx_policy = (int)value;
+        return NTC_OK;
+    }
     if (std::strcmp(key, "encode_variant") == 0) {
         if (value != 1 && value != 4)
             return set_err(ctx, NTC_ERR_INVALID_ARG, "encode_variant must be 4 (default) or 1 (A/B baseline)");
@@ -1147,6 +1303,10 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "pack_us") == 0) *value = (int64_t)(ctx->last_pack_ms * 1000.0);
     else if (std::strcmp(key, "ent_slots") == 0) *value = ent_slots(ctx);
     else if (std::strcmp(key, "spill_reruns") == 0) *value = (int64_t)ctx->spill_reruns;
+    else if (std::strcmp(key, "non_acgt") == 0) *value = ctx->nx_policy;
+    else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
+    else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
+    else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
     else if (std::strcmp(key, "pool_entries") == 0) *value = (int64_t)ctx->last4.pcap;  // last call's pools
     else if (std::strcmp(key, "pool_records") == 0) *value = (int64_t)ctx->last4.rcap;
     else if (std::strcmp(key, "workspace_bytes") == 0) {  // device workspace held now (all slots)
@@ -1173,6 +1333,9 @@ int ntc_encode_batch_device(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t
     if (!ctx || (!d_read_offsets && n_reads) || !d_rec_offsets_out)
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->nx_policy != 0)
+        return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need the host-buffer encode calls "
+                                                 "(the caller's device buffer is const)");
     if (ctx->encode_variant == 4) {
         if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
         uint64_t total = 0;
@@ -1277,6 +1440,9 @@ int ntc_encode_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_of
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
+    nx_begin(ctx);
+    if (ctx->encode_variant != 4 && ctx->nx_policy != 0)
+        return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need encode_variant 4");
     if (ctx->encode_variant != 4)
         return encode_batch_v1(ctx, bases, read_offsets, n_reads, rec_out, rec_capacity, rec_offsets_out, bad_read);
     // passes of whole reads, at most max_pass_bases each (one read may exceed it alone), so
@@ -1304,19 +1470,23 @@ int ntc_encode_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_of
         if ((rc = ensure(ctx, WS_STAGE_OFFS, (nr + 1) * 8 * 2, &d_offs))) return rc;
         if ((rc = ensure(ctx, WS_STAGE_RECS, (total + 1) * 8, &d_recs))) return rc;
         uint64_t *d_roffs = (uint64_t *)d_offs + (nr + 1);
-        if (total) HIP_TRY(ctx, hipMemcpyAsync(d_bases, bases + o0, total, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_offs, offs.data(), (nr + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        rc = encode4_impl(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, nr, total, (uint64_t *)d_recs,
-                          total + 1, d_roffs);
-        if (rc) return rc;
-        int64_t bad = -1;
-        rc = read_status(ctx, &bad);
-        if (rc) {
-            if (bad_read) *bad_read = bad + (int64_t)r0;
-            char buf[160];
-            std::snprintf(buf, sizeof(buf), "%s at index %lld", status_name(rc), (long long)(bad + (int64_t)r0));
-            ctx->err = buf;
-            return rc;
+        for (bool again = true; again;) {  // twice only when the pass holds more runs than the list had room for
+            if (total) HIP_TRY(ctx, hipMemcpyAsync(d_bases, bases + o0, total, hipMemcpyHostToDevice, ctx->stream));
+            if ((rc = nx_mask(ctx, (uint8_t *)d_bases, (const uint64_t *)d_offs, nr, total))) return rc;
+            rc = encode4_impl(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, nr, total, (uint64_t *)d_recs,
+                              total + 1, d_roffs);
+            if (rc) return rc;
+            int64_t bad = -1;
+            rc = read_status(ctx, &bad);
+            if (rc) {
+                if (bad_read) *bad_read = bad + (int64_t)r0;
+                char buf[160];
+                std::snprintf(buf, sizeof(buf), "%s at index %lld", status_name(rc), (long long)(bad + (int64_t)r0));
+                ctx->err = buf;
+                return rc;
+            }
+            if ((rc = nx_collect(ctx, r0, &again))) return rc;
         }
         roffs.resize(nr + 1);
         HIP_TRY(ctx, hipMemcpy(roffs.data(), d_roffs, (nr + 1) * 8, hipMemcpyDeviceToHost));
@@ -1415,6 +1585,10 @@ int ntc_decode_batch(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint8_
     if (n_recs && !((recs[0] >> 56) & 1)) return set_err(ctx, NTC_ERR_FORMAT, "records do not start a read");
     if (nbases > bases_capacity || nreads + 1 > offsets_capacity || !read_offsets_out || (nbases && !bases_out))
         return set_err(ctx, NTC_ERR_CAPACITY, "decode output buffers too small");
+    std::vector<ntc_nx_run> nx;  // pending exception runs: each pass patches its own reads'
+    uint32_t nx_sub = 0;
+    if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= nreads)
+        return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
     // passes of whole reads (a pass ends before a `first` record), at most max_pass_bases
     // output bases each unless one read alone is larger
     uint64_t a0 = 0, reads_done = 0, bases_done = 0;
@@ -1446,6 +1620,8 @@ int ntc_decode_batch(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint8_
         rc = ntc_decode_batch_device(ctx, (const uint64_t *)d_recs, nrec, (uint8_t *)d_out, pb, (uint64_t *)d_offs,
                                      pr + 1);
         if (rc) return rc;
+        if (!nx.empty() && (rc = nx_patch(ctx, nx, nx_sub, reads_done, pr, (uint8_t *)d_out, (const uint64_t *)d_offs)))
+            return rc;
         uint64_t nr = 0, nb = 0;
         rc = ntc_decode_status(ctx, &nr, &nb);
         if (rc) return rc;
@@ -1479,17 +1655,24 @@ namespace {
 // ntc_encode_pack_batch and ntc_encode_pack_fastq
 int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offs, uint64_t n_reads, uint64_t total,
                        uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
-                       int64_t *bad_read) {
+                       int64_t *bad_read, const std::function<int()> &restage) {
     void *d_recs, *d_payload;
     int rc;
     if ((rc = ensure(ctx, WS_STAGE_RECS, (total + 1) * 8, &d_recs))) return rc;
     uint64_t *d_roffs = (uint64_t *)d_offs + (n_reads + 1);
-    rc = encode4_impl(ctx, d_bases, d_offs, n_reads, total, (uint64_t *)d_recs, total + 1, d_roffs);
-    if (rc) return rc;
-    int64_t bad = -1;
-    if ((rc = read_status(ctx, &bad))) {
-        if (bad_read) *bad_read = bad;
-        return rc;
+    // non-ACGT symbols are masked in the staged copy first (policy 0: nothing runs); a batch
+    // with more runs than the list had room for is staged and run once more
+    for (bool again = true; again;) {
+        if ((rc = nx_mask(ctx, const_cast<uint8_t *>(d_bases), d_offs, n_reads, total))) return rc;
+        rc = encode4_impl(ctx, d_bases, d_offs, n_reads, total, (uint64_t *)d_recs, total + 1, d_roffs);
+        if (rc) return rc;
+        int64_t bad = -1;
+        if ((rc = read_status(ctx, &bad))) {
+            if (bad_read) *bad_read = bad;
+            return rc;
+        }
+        if ((rc = nx_collect(ctx, 0, &again))) return rc;
+        if (again && (rc = restage())) return rc;
     }
     // the payload never exceeds the records' 8 B each plus per-stream rounding, except for
     // malformed unary runs: size the device buffer for that and let the packer check
@@ -1545,8 +1728,13 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     if ((rc = ensure(ctx, WS_STAGE_OFFS, (n_reads + 1) * 8 * 2, &d_offs))) return rc;
     if (total) HIP_TRY(ctx, hipMemcpyAsync(d_bases, bases + o0, total, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_offs, offs.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    nx_begin(ctx);
+    const auto restage = [&]() -> int {
+        if (total) HIP_TRY(ctx, hipMemcpyAsync(d_bases, bases + o0, total, hipMemcpyHostToDevice, ctx->stream));
+        return NTC_OK;
+    };
     return encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads,
-                              meta, payload, payload_bytes, bad_read);
+                              meta, payload, payload_bytes, bad_read, restage);
 }
 
 }  // extern "C"
@@ -1590,6 +1778,7 @@ int fastq_stage(ntc_ctx *ctx, const uint8_t *fastq, uint64_t bytes, uint64_t n_r
     a.status = ctx->d_status;
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
     if (bytes) HIP_TRY(ctx, hipMemcpyAsync(raw, fastq, bytes, hipMemcpyHostToDevice, ctx->stream));
+    ctx->fq_last = a;
     launch_fastq_parse(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     launch_status_box(ctx->d_status, a.offs + n_reads, nullptr, nullptr, ctx->h_box, ctx->stream);
@@ -1643,9 +1832,17 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     int rc = fastq_stage(ctx, fastq, fastq_bytes, n_reads, &d_bases, &d_offs, &total, bad_read);
     if (rc) return rc;
     if (n_bases) *n_bases = total;
+    nx_begin(ctx);
     if (n_reads == 0) return NTC_OK;
+    const auto restage = [&]() -> int {  // the text is still in HBM: parse it again (it parsed clean once)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
+        ctx->fq_last.tmp = (uint64_t *)ctx->ws[WS_SCANTMP].p;  // the scan scratch may have grown (never shrinks) since
+        launch_fastq_parse(ctx->fq_last, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+        return NTC_OK;
+    };
     return encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads,
-                              meta, payload, payload_bytes, bad_read);
+                              meta, payload, payload_bytes, bad_read, restage);
 }
 
 }  // extern "C"
@@ -1672,8 +1869,15 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if ((rc = ensure(ctx, WS_FA_OFFS, (n_reads + 2) * 8, &d_offs))) return rc;
     if ((rc = ensure(ctx, WS_FA_SCAN, (2 * (n_reads + 1) + scan_tmp_words(n_reads + 1)) * 8, &d_scan))) return rc;
     if ((rc = ensure(ctx, WS_STAGE_BASES, need + 64, &d_out))) return rc;
+    std::vector<ntc_nx_run> nx;
+    uint32_t nx_sub = 0;
+    if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= n_reads)
+        return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
     if ((rc = ntc_decode_batch_device(ctx, d_recs, n_recs, (uint8_t *)d_bases, n_bases + 64, (uint64_t *)d_offs,
                                       n_reads + 2)))
+        return rc;
+    // exception runs go over the substitute bases before the text is formatted
+    if (!nx.empty() && (rc = nx_patch(ctx, nx, nx_sub, 0, n_reads, (uint8_t *)d_bases, (const uint64_t *)d_offs)))
         return rc;
     uint64_t *sizes = (uint64_t *)d_scan, *out_offs = sizes + (n_reads + 1), *tmp = out_offs + (n_reads + 1);
     launch_fasta((const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status, sizes, out_offs,
@@ -1863,6 +2067,27 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     if (ctx->unp_recs == 0) return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     return decode_fasta_dev(ctx, ctx->unp_d_recs, ctx->unp_recs, ctx->unp_reads, ctx->unp_bases, first_id, out, need);
+}
+
+int ntc_encode_exceptions(ntc_ctx *ctx, ntc_nx_run *out, uint64_t capacity, uint64_t *n_runs) {
+    if (!ctx || !n_runs || (capacity && !out)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_runs = ctx->nx_list.size();
+    if (ctx->nx_list.size() > capacity) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the exception runs");
+    if (!ctx->nx_list.empty()) std::memcpy(out, ctx->nx_list.data(), ctx->nx_list.size() * sizeof(ntc_nx_run));
+    return NTC_OK;
+}
+
+int ntc_decode_set_exceptions(ntc_ctx *ctx, const ntc_nx_run *runs, uint64_t n_runs, uint32_t sub) {
+    if (!ctx || (n_runs && !runs)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    ctx->nx_pending.assign(runs, runs + n_runs);
+    // each decode pass finds its runs by read: keep them in (read, pos) order (the canonical
+    // lists already are)
+    const auto less = [](const ntc_nx_run &a, const ntc_nx_run &b) { return a.read != b.read ? a.read < b.read : a.pos < b.pos; };
+    if (!std::is_sorted(ctx->nx_pending.begin(), ctx->nx_pending.end(), less))
+        std::stable_sort(ctx->nx_pending.begin(), ctx->nx_pending.end(), less);
+    ctx->nx_pending_sub = sub;
+    ctx->nx_has_pending = n_runs != 0;
+    return NTC_OK;
 }
 
 int ntc_last_timing(ntc_ctx *ctx, ntc_timing *out) {
@@ -2111,3 +2336,21 @@ int ntc_index_load(const char *prefix, ntc_index_host **out) {
 }
 
 }  // extern "C"
+
+// the pipelines' way to the non-ACGT entry points (ntc_internal.h NxHooks), set at load
+namespace {
+struct NxHookFill {
+    NxHookFill() {
+        ntc::g_nx_hooks.set_policy = [](ntc_ctx *ctx, int policy) { return ntc_ctx_set_option(ctx, "non_acgt", policy); };
+        ntc::g_nx_hooks.last_counts = [](ntc_ctx *ctx, uint32_t *sub, uint64_t *runs, uint64_t *bases) {
+            if (!ctx) return (int)NTC_ERR_INVALID_ARG;
+            if (sub) *sub = ctx->has_index ? nx_substitute(ctx->dix.absent) : 0;
+            if (runs) *runs = ctx->nx_runs;
+            if (bases) *bases = ctx->nx_bases;
+            return (int)NTC_OK;
+        };
+        ntc::g_nx_hooks.encode_exceptions = ntc_encode_exceptions;
+        ntc::g_nx_hooks.decode_set_exceptions = ntc_decode_set_exceptions;
+    }
+} g_nx_hook_fill;
+}  // namespace

@@ -221,6 +221,42 @@ struct FastqArgs {
 uint64_t fastq_tiles(uint64_t n_raw);
 void launch_fastq_parse(const FastqArgs &a, hipStream_t s);
 
+// Non-ACGT symbols (nonacgt.hip, nonacgt_core.h).  Encode side, over staged (writable)
+// bases: M / S / E bitmaps of nx_words(total) words each, cnt_s / cnt_e as many u32, soff /
+// eoff one word more (exclusive scans, scan_tmp: scan_tmp_words(words)), counts[0] = runs
+// found, counts[1] = bases flagged.  The first run_cap runs go to runs (null: none are
+// listed, policy mask); then every flagged byte becomes sub.
+struct NxRun;
+struct NxArgs {
+    uint8_t *bases;
+    const uint64_t *offs;   // [n_reads + 1], absolute into bases
+    uint64_t n_reads, total, n_words;
+    uint64_t *M, *S, *E;
+    uint32_t *cnt_s, *cnt_e;
+    uint64_t *soff, *eoff;
+    uint64_t *counts;
+    uint64_t *box;          // the context's host mailbox: words 4, 5 = counts (k_status_box fills 0..3)
+    NxRun *runs;
+    uint64_t run_cap;
+    uint32_t sub;
+    unsigned long long *status;
+};
+uint64_t nx_words(uint64_t total);
+void launch_nx_mask(const NxArgs &a, uint64_t *scan_tmp, hipStream_t s);
+// Decode side: n pieces (runs, long ones cut into slices) over the decoded bases and read
+// offsets; a piece that does not fit, or covers a byte other than sub, sets status to
+// read << 8 | NTC_ERR_FORMAT and writes nothing.
+struct NxPatchArgs {
+    const NxRun *runs;
+    uint64_t n;
+    uint8_t *bases;
+    const uint64_t *offs;   // [n_reads + 1]
+    uint64_t n_reads;
+    uint32_t sub;
+    unsigned long long *status;
+};
+void launch_nx_patch(const NxPatchArgs &a, hipStream_t s);
+
 void launch_encode(const EncodeArgs &a, hipStream_t s);
 void launch_encode4(const Enc4Args &a, uint64_t total, uint32_t ms_blocks, hipStream_t s,
                     hipEvent_t ev_ms_begin, hipEvent_t ev_ms_end);

@@ -91,6 +91,7 @@ struct Gang {
 struct ntc_fastx;
 struct ntc_block_meta;
 struct ntc_ctx;
+struct ntc_nx_run;
 namespace ntc {
 // a plain FASTQ that ntc_fastx_open mapped: its bytes (null for any other input), and
 // moving the mapped parser to byte pos (a record start) -- pipeline.cpp's GPU-parse reader
@@ -115,6 +116,18 @@ int unpack_block_host(const ::ntc_block_meta &m, const uint8_t *payload, std::ve
 // takes one copy each way of up to 4 MiB: the process's first large copies start the DMA
 // engines (7.7 ms before the first batch's text came back otherwise).
 int reserve_decode(::ntc_ctx *ctx, uint64_t pay_bytes, uint64_t n_recs, uint8_t *host, uint64_t host_bytes);
+// The GPU stage's non-ACGT entry points as the pipelines reach them (pipeline.cpp defines
+// the table, all null; capi.cpp fills it when the library loads).  A build of pipeline.cpp
+// without capi.cpp -- the sanitizer build over tests/san/gpu_stub.cpp -- links without them,
+// and ntc_encode_file_nx / ntc_decode_file_nx then answer NTC_ERR_UNSUPPORTED to a policy
+// other than error or to a side file.
+struct NxHooks {
+    int (*set_policy)(::ntc_ctx *ctx, int policy);                      // ctx option "non_acgt"
+    int (*last_counts)(::ntc_ctx *ctx, uint32_t *sub, uint64_t *runs, uint64_t *bases);  // "nx_sub", "nx_runs", "nx_bases"
+    int (*encode_exceptions)(::ntc_ctx *ctx, ::ntc_nx_run *out, uint64_t capacity, uint64_t *n_runs);
+    int (*decode_set_exceptions)(::ntc_ctx *ctx, const ::ntc_nx_run *runs, uint64_t n_runs, uint32_t sub);
+};
+extern NxHooks g_nx_hooks;
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

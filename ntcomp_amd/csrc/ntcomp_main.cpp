@@ -7,9 +7,12 @@
 //   ntcomp build -o P [-k 31] [-p 8] [-d] [-t 1] [-m 4] [--temp-dir D] [--verbose]
 //                [-l LIST] [--builder auto|host|gpu] [--device N] [--index-format own|sbwt-rs] FILES...
 //   ntcomp encode -i P [--gpus N | --devices 0,0,..] [--threads T] [--blocks-per-batch B]
-//                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats] FILE > encoded.dat
-//   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats] FILE > out.fasta
+//                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
+//                 [--non-acgt error|mask|keep] [--exceptions PATH] FILE > encoded.dat
+//   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
+//                 [--exceptions PATH] FILE > out.fasta
 #include <dlfcn.h>
+#include <fcntl.h>
 #include <unistd.h>
 
 #include <chrono>
@@ -38,6 +41,11 @@ double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::
     std::exit(1);
 }
 void info(const char *msg) { std::fprintf(stderr, "%s\n", msg); }
+// an argument error found after parsing: status 2, before anything is loaded or written
+[[noreturn]] void bad_args(const std::string &msg) {
+    std::fprintf(stderr, "ntcomp: %s\n", msg.c_str());
+    std::exit(2);
+}
 
 struct Args {
     std::vector<std::string> pos;
@@ -61,7 +69,7 @@ bool takes_value(const std::string &o) {
     static const char *v[] = {"-o", "--output-prefix", "-k", "-p", "--prefix-precalc", "-t", "--threads", "-m",
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
-                              "--deflate", "--contexts-per-gpu"};
+                              "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -217,6 +225,13 @@ int cmd_encode(const Args &a) {
     if (a.pos.size() != 1) die("encode: one query file");
     const std::string prefix = a.get("-i", "--index", "");
     if (prefix.empty()) die("encode: -i/--index is required");
+    // N and IUPAC symbols: error (default), mask, or keep with the exception runs in a side file
+    const std::string nx_name = a.get("--non-acgt", nullptr, "error"), nx_path = a.get("--exceptions", nullptr, "");
+    const int policy = nx_name == "error" ? NTC_NX_ERROR : nx_name == "mask" ? NTC_NX_MASK : nx_name == "keep" ? NTC_NX_KEEP : -1;
+    if (policy < 0) bad_args("encode: --non-acgt: error, mask or keep");
+    if (policy == NTC_NX_KEEP && nx_path.empty()) bad_args("encode: --non-acgt keep requires --exceptions PATH");
+    if (policy != NTC_NX_KEEP && a.flag("--exceptions"))
+        bad_args("encode: --exceptions is only written under --non-acgt keep");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
@@ -236,8 +251,15 @@ int cmd_encode(const Args &a) {
     if (o.deflate_engine < 0) die("--deflate: auto, zlib, libdeflate or adaptive");
     o.host_parse = a.flag("--host-parse") ? 1 : 0;
     ntc_pipeline_stats st{};
+    ntc_nx_stats nx{};
+    int nx_fd = -1;
+    if (policy == NTC_NX_KEEP && (nx_fd = ::open(nx_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
+        die("encode: cannot write " + nx_path);
     std::fflush(stdout);
-    const int rc = ntc_encode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st);
+    const int rc = policy == NTC_NX_ERROR
+                       ? ntc_encode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
+                       : ntc_encode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, policy, nx_fd, &o, &st, &nx);
+    if (nx_fd >= 0 && ::close(nx_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + nx_path);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -254,10 +276,14 @@ int cmd_encode(const Args &a) {
                      "{\"stats\": {\"index_load\": %.3f, \"gpu_init_upload\": %.3f, \"parse\": %.3f, \"gpu\": %.3f, "
                      "\"deflate\": %.3f, \"write\": %.3f}, \"command\": \"encode\", \"native\": true, \"gpus\": %zu, "
                      "\"threads\": %d, \"reads\": %llu, \"blocks\": %llu, \"dropped_blocks\": %llu, "
-                     "\"pipeline_wall_s\": %.3f, \"deflate\": \"%s\", \"gpu_parsed_batches\": %d, \"process_s\": %.3f}\n",
+                     "\"pipeline_wall_s\": %.3f, \"deflate\": \"%s\", \"gpu_parsed_batches\": %d, \"non_acgt\": \"%s\", "
+                     "\"nx_runs\": %llu, \"nx_bases\": %llu, \"nx_reads\": %llu, \"nx_runs_in_dropped_blocks\": %llu, "
+                     "\"process_s\": %.3f}\n",
                      t_load, t_gpu - t_load, st.parse_s, st.gpu_s, st.deflate_s, st.write_s, ctxs.size(), st.threads,
                      (unsigned long long)st.reads, (unsigned long long)st.blocks,
-                     (unsigned long long)st.dropped_blocks, st.wall_s, engine.c_str(), st.gpu_parsed, since(t0));
+                     (unsigned long long)st.dropped_blocks, st.wall_s, engine.c_str(), st.gpu_parsed, nx_name.c_str(),
+                     (unsigned long long)nx.runs, (unsigned long long)nx.bases, (unsigned long long)nx.reads,
+                     (unsigned long long)nx.runs_in_dropped_blocks, since(t0));
     return 0;
 }
 
@@ -282,8 +308,11 @@ int cmd_decode(const Args &a) {
     o.threads = std::atoi(a.get("--threads", nullptr, "0").c_str());
     o.blocks_per_batch = std::atoi(a.get("--blocks-per-batch", nullptr, "2").c_str());
     ntc_pipeline_stats st{};
+    const std::string nx_path = a.get("--exceptions", nullptr, "");  // the side file of encode --non-acgt keep
     std::fflush(stdout);
-    const int rc = ntc_decode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st);
+    const int rc = nx_path.empty()
+                       ? ntc_decode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
+                       : ntc_decode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), nx_path.c_str(), 1, &o, &st);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) die(std::string("decode: ") + st.error);
@@ -399,8 +428,13 @@ void usage(FILE *f) {
     std::fprintf(f,
                  "Sequencing data compression with SBWT + k-bounded matching statistics; encode/decode hot path on "
                  "MI355X.\n\nusage: ntcomp build -o PREFIX [-k K] [-m MEM_GB] [--temp-dir DIR] FILES...\n"
-                 "       ntcomp encode -i PREFIX FILE > encoded.dat\n"
-                 "       ntcomp decode -i PREFIX FILE > out.fasta\n");
+                 "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH] FILE > encoded.dat\n"
+                 "       ntcomp decode -i PREFIX [--exceptions PATH] FILE > out.fasta\n\n"
+                 "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
+                 "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
+                 "                     the replaced symbols to the --exceptions file (lossless)\n"
+                 "  --exceptions PATH  encode --non-acgt keep: the side file to write; decode: the side file whose\n"
+                 "                     symbols are put back\n");
 }
 
 }  // namespace

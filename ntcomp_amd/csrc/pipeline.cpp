@@ -46,6 +46,10 @@
 #include "../../include/ntcomp_pipeline.h"
 #include "ntc_internal.h"
 
+namespace ntc {
+NxHooks g_nx_hooks = {nullptr, nullptr, nullptr, nullptr};  // capi.cpp fills it at load
+}
+
 namespace {
 
 using Clock = std::chrono::steady_clock;
@@ -201,6 +205,8 @@ struct BlockOut {  // a deflated block (its four streams' parts), or a dropped o
     uint64_t len[4] = {0, 0, 0, 0};
     int status = NTC_OK;
     int left = 0;  // parts not yet deflated
+    uint64_t n_reads = 0;            // the block's reads
+    std::vector<ntc_nx_run> nx;      // its exception runs (policy keep), read relative to the block
 };
 
 struct Shared {
@@ -224,11 +230,40 @@ struct Shared {
 
 extern "C" {
 
-int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_pipeline_opts *opts,
-                    ntc_pipeline_stats *stats) {
+// policy / nx_fd / nx: ntc_encode_file_nx; ntc_encode_file passes policy -1 = the contexts as
+// they are, no side file
+static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
+                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
+    const bool keep = policy == NTC_NX_KEEP;
+    ntc_nx_stats NX{};
+    uint32_t nx_sub = 0;
+    if (policy >= 0) {
+        if (policy > NTC_NX_KEEP || (keep ? nx_fd < 0 : nx_fd != -1)) return NTC_ERR_INVALID_ARG;
+        const ntc::NxHooks &hk = ntc::g_nx_hooks;
+        if (policy != NTC_NX_ERROR && (!hk.set_policy || !hk.last_counts || !hk.encode_exceptions))
+            return NTC_ERR_UNSUPPORTED;
+        if (hk.set_policy)
+            for (int i = 0; i < n_ctx; i++)
+                if (int r = hk.set_policy(ctxs[i], policy)) return r;
+        if (policy != NTC_NX_ERROR) {
+            hk.last_counts(ctxs[0], &nx_sub, nullptr, nullptr);
+            if (!nx_sub) {
+                for (int i = 0; i < n_ctx; i++) hk.set_policy(ctxs[i], 0);
+                return NTC_ERR_NO_INDEX;
+            }
+        }
+    }
+    struct PolicyReset {  // the contexts leave the call under policy error
+        ntc_ctx *const *ctxs;
+        int n;
+        ~PolicyReset() {
+            if (n > 0 && ntc::g_nx_hooks.set_policy)
+                for (int i = 0; i < n; i++) ntc::g_nx_hooks.set_policy(ctxs[i], 0);
+        }
+    } policy_reset{ctxs, policy > 0 ? n_ctx : 0};
     ntc_pipeline_opts o{};
     if (opts) o = *opts;
     const int T = o.threads > 0 ? o.threads : ntc_host_threads();
@@ -618,15 +653,40 @@ int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
                     return;
                 }
                 std::shared_ptr<uint8_t> pl(payload, ntc_buffer_free);
+                // the batch's exception runs (policy keep) and counts, before the context's next call
+                std::vector<ntc_nx_run> runs;
+                uint64_t nx_runs = 0, nx_bases = 0;
+                if (policy > 0) {
+                    const ntc::NxHooks &hk = ntc::g_nx_hooks;
+                    hk.last_counts(ctxs[c], nullptr, &nx_runs, &nx_bases);
+                    uint64_t nrun = 0;
+                    int rx = NTC_OK;
+                    if (keep && hk.encode_exceptions(ctxs[c], nullptr, 0, &nrun) == NTC_ERR_CAPACITY) {
+                        runs.resize(nrun);
+                        rx = hk.encode_exceptions(ctxs[c], runs.data(), nrun, &nrun);
+                    }
+                    if (rx) {
+                        sh.fail(rx, std::string("encode: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                }
                 etrace("gpu done, first block", b.first_block);
                 std::lock_guard<std::mutex> g(sh.mu);
                 S.gpu_done_s = secs(t0, Clock::now());
                 S.bases += b.is_text ? nb : b.offs[b.n_process] - b.offs[0];
+                NX.bases += nx_bases;
+                if (policy == NTC_NX_MASK) NX.runs += nx_runs;
                 b.busy = false;
+                size_t run_at = 0;
                 for (uint64_t k = 0; k < nblk; k++) {  // streams of the largest payload first
                     const bool ok = metas[k].status == NTC_OK;
                     BlockOut &bo = done[b.first_block + k];
                     bo.status = metas[k].status;
+                    bo.n_reads = metas[k].num_records;
+                    for (; run_at < runs.size() && runs[run_at].read < (k + 1) * (uint64_t)BR; run_at++) {
+                        bo.nx.push_back(runs[run_at]);
+                        bo.nx.back().read -= k * (uint64_t)BR;
+                    }
                     bo.left = ok ? 4 : 1;
                     int order[4] = {0, 1, 2, 3};
                     std::sort(order, order + 4, [&](int x, int y) {
@@ -691,6 +751,10 @@ int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
     ntc_file_header(header);
     if (!write_all(header, 32)) sh.fail(NTC_ERR_IO, "write failed");
     S.bytes_out = 32;
+    // the side file: its header now, then a section per written block that has runs, `read`
+    // counted over the reads of the blocks written so far (what decode will print as seq.N - 1)
+    if (keep && ntc_nx_write(nx_fd, nullptr, 0, nx_sub, 1)) sh.fail(NTC_ERR_IO, "exceptions: write failed");
+    uint64_t reads_written = 0;
     for (uint64_t blk = 0;; blk++) {
         BlockOut out;
         {
@@ -701,7 +765,7 @@ int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
             });
             if (sh.error != NTC_OK) break;
             if (!done.count(blk)) break;  // all blocks written
-            out = done[blk];
+            out = std::move(done[blk]);
             done.erase(blk);
             pending_tasks--;
             writer_at = blk + 1;
@@ -714,8 +778,20 @@ int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
                 S.bytes_out += out.len[q];
             }
             S.blocks++;
+            if (!out.nx.empty()) {
+                uint64_t last_read = UINT64_MAX;
+                for (auto &r : out.nx) {
+                    NX.reads += r.read != last_read;
+                    last_read = r.read;
+                    r.read += reads_written;
+                }
+                if (ntc_nx_write(nx_fd, out.nx.data(), out.nx.size(), nx_sub, 0)) sh.fail(NTC_ERR_IO, "exceptions: write failed");
+                NX.runs += out.nx.size();
+            }
+            reads_written += out.n_reads;
         } else {
             S.dropped_blocks++;
+            NX.runs_in_dropped_blocks += out.nx.size();
         }
         for (int q = 0; q < 4; q++) ntc_buffer_free(out.part[q]);
         add_time(t_write, secs(tw, Clock::now()));
@@ -755,7 +831,19 @@ int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
     S.bad_read = sh.bad_read;
     std::snprintf(S.error, sizeof(S.error), "%s", result == NTC_OK ? "" : sh.msg.c_str());
     if (stats) *stats = S;
+    if (nx) *nx = NX;
     return result;
+}
+
+int ntc_encode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_pipeline_opts *opts,
+                    ntc_pipeline_stats *stats) {
+    return encode_file_impl(ctxs, n_ctx, in_path, out_fd, -1, -1, opts, stats, nullptr);
+}
+
+int ntc_encode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx) {
+    if (policy < 0) return NTC_ERR_INVALID_ARG;
+    return encode_file_impl(ctxs, n_ctx, in_path, out_fd, policy, nx_fd, opts, stats, nx);
 }
 
 }  // extern "C"
@@ -844,11 +932,41 @@ uint64_t digits_total(uint64_t first, uint64_t n) {  // decimal digits of first 
 
 extern "C" {
 
-int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_pipeline_opts *opts,
-                    ntc_pipeline_stats *stats) {
+// nx_path: ntc_decode_file_nx's side file (null: none)
+static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
+                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
+    // the exception runs, read once; each batch finds its own by its first read (put_runs)
+    struct NxFile {
+        ntc_nx_run *runs = nullptr;
+        uint64_t n = 0;
+        uint32_t sub = 0;
+        ~NxFile() { ntc_buffer_free(runs); }
+    } nxf;
+    if (nx_path) {
+        if (!ntc::g_nx_hooks.decode_set_exceptions) return NTC_ERR_UNSUPPORTED;
+        if (const int r = ntc_nx_read(nx_path, &nxf.runs, &nxf.n, &nxf.sub)) {
+            if (stats) {
+                std::memset(stats, 0, sizeof(*stats));
+                stats->bad_read = -1;
+                std::snprintf(stats->error, sizeof(stats->error), "exceptions: %s",
+                              r == NTC_ERR_IO ? "cannot read the side file" : "malformed side file");
+            }
+            return r;
+        }
+    }
+    // hands ctx the runs of reads [first, first + n) (file numbering), read relative to first
+    auto put_runs = [&](ntc_ctx *ctx, uint64_t first, uint64_t n, std::vector<ntc_nx_run> &tmp) -> int {
+        if (!nxf.n) return NTC_OK;
+        const auto less = [](const ntc_nx_run &x, uint64_t v) { return x.read < v; };
+        const ntc_nx_run *lo = std::lower_bound(nxf.runs, nxf.runs + nxf.n, first, less);
+        const ntc_nx_run *hi = std::lower_bound(lo, (const ntc_nx_run *)(nxf.runs + nxf.n), first + n, less);
+        tmp.assign(lo, hi);
+        for (auto &r : tmp) r.read -= first;
+        return ntc::g_nx_hooks.decode_set_exceptions(ctx, tmp.data(), tmp.size(), nxf.sub);
+    };
     ntc_pipeline_opts o{};
     if (opts) o = *opts;
     const int T = o.threads > 0 ? o.threads : ntc_host_threads();
@@ -1032,6 +1150,7 @@ int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
                     return;
                 }
             }
+            std::vector<ntc_nx_run> nx_tmp;  // a batch's exception runs, renumbered from its first read
             for (uint64_t b = (uint64_t)c;; b += (uint64_t)n_ctx) {
                 DSlot *slp;
                 if (gpu_unpack) {
@@ -1078,6 +1197,10 @@ int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
                         return;
                     }
                     uint64_t len = 0;
+                    if (const int rx = put_runs(ctxs[c], sl.first_id - 1, sl.n_reads, nx_tmp)) {
+                        sh.fail(rx, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
                     const int rf = ntc_decode_fasta_unpacked(ctxs[c], sl.first_id, sl.text, sl.cap_text, &len);
                     add_time(t_gpu, secs(tf, Clock::now()));
                     if (rf) {
@@ -1110,6 +1233,10 @@ int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
                     return;
                 }
                 uint64_t len = 0;
+                if (const int rx = put_runs(ctxs[c], sl.first_id - 1, sl.n_reads, nx_tmp)) {
+                    sh.fail(rx, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                    return;
+                }
                 const int rc = ntc_decode_fasta(ctxs[c], sl.recs, nrec, sl.n_reads, sl.n_bases, sl.first_id, sl.text,
                                                 sl.cap_text, &len);
                 add_time(t_gpu, secs(tg, Clock::now()));
@@ -1321,7 +1448,12 @@ int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
     }
     if (data) munmap((void *)data, fsize);
     if (seekable) (void)lseek(out_fd, out_pos, SEEK_SET);
-    const int result = sh.error == -1 ? NTC_OK : sh.error;
+    int result = sh.error == -1 ? NTC_OK : sh.error;
+    // every batch checked its own runs; one past the file's last read belongs to another encoding
+    if (result == NTC_OK && stop_batch < 0 && nxf.n && nxf.runs[nxf.n - 1].read >= S.reads) {
+        result = NTC_ERR_FORMAT;
+        sh.msg = "exceptions: a run past the last read (the side file belongs to another encoding)";
+    }
     S.dropped_blocks = blocks.size() - S.blocks;  // after a damaged block (or none)
     S.alloc_s += t_pin.load();
     S.parse_s = t_unzip.load();
@@ -1337,6 +1469,16 @@ int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
                       (unsigned long long)S.blocks);
     if (stats) *stats = S;
     return result;
+}
+
+int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_pipeline_opts *opts,
+                    ntc_pipeline_stats *stats) {
+    return decode_file_impl(ctxs, n_ctx, in_path, nullptr, out_fd, opts, stats);
+}
+
+int ntc_decode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
+    return decode_file_impl(ctxs, n_ctx, in_path, nx_path, out_fd, opts, stats);
 }
 
 }  // extern "C"
