@@ -188,6 +188,76 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
 int ntc_nx_write(int fd, const ntc_nx_run *runs, uint64_t n_runs, uint32_t sub, int with_header);
 int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t *sub);
 
+/* ---- FASTQ quality scores ------------------------------------------------------------------ */
+/* ntc_ctx_set_option(ctx, "qualities", mode) says what ntc_encode_pack_fastq does with the
+ * quality lines of its text:
+ *   0  drop (default): they are skipped, as ever; neither their length against the bases kept
+ *      nor their bytes are checked.
+ *   1  keep (lossless): every block of block_reads reads also yields a quality section.
+ *   2  bin8 (lossy): Phred q = byte - 33 is first mapped to 8 levels (q < 2 stays, 2-9 -> 6,
+ *      10-19 -> 15, 20-24 -> 22, 25-29 -> 27, 30-34 -> 33, 35-39 -> 37, >= 40 -> 40), then as 1.
+ * A read's qualities are its quality line without one trailing '\r'; under 1 and 2 their
+ * number must equal the read's bases after normalisation and every byte must lie in '!'..'~',
+ * else the call returns NTC_ERR_FORMAT with that read as bad_read.  The calls that take bases
+ * without qualities (ntc_encode_batch, ntc_encode_batch_device, ntc_encode_pack_batch) return
+ * NTC_ERR_UNSUPPORTED under 1 and 2.
+ *
+ * A section, the canonical packed form of one block: alphabet = the distinct quality bytes of
+ * the block, ascending (n_syms of them, 1..94); width = 0, 1, 2, 4 or 8 bits for n_syms = 1,
+ * 2, 3-4, 5-16, more; quality i of the block (read by read) has the rank of its byte in the
+ * alphabet as its code, in bits [i width, i width + width) of a little-endian bit stream of
+ * ceil(n_quals width / 64) 64-bit words, unused high bits zero.  The packing runs on the GPU. */
+typedef struct ntc_qual_meta {
+    uint64_t n_reads;       /* reads of the block                                          */
+    uint64_t n_quals;       /* their quality bytes (= their bases)                         */
+    uint64_t payload_off;   /* byte offset of the section's words in the payload buffer    */
+    uint64_t payload_bytes; /* 8 * ceil(n_quals * width / 64)                              */
+    uint8_t width, n_syms;
+    uint8_t reserved[6];    /* 0                                                           */
+    uint8_t alphabet[96];   /* n_syms bytes ascending, then zeros                          */
+} ntc_qual_meta;            /* 136 bytes */
+/* The sections of the last ntc_encode_pack_fastq call on this context under mode 1 or 2, one
+ * per block (none under mode 0, or when that call failed): metas[0 .. *n_blocks) and their
+ * words in payload, *payload_bytes in all.  NTC_ERR_CAPACITY (sizes set, nothing copied) when
+ * meta_cap or payload_cap is smaller.                                                      */
+int ntc_encode_qualities(ntc_ctx *ctx, ntc_qual_meta *metas, uint64_t meta_cap, uint8_t *payload,
+                         uint64_t payload_cap, uint64_t *n_blocks, uint64_t *payload_bytes);
+/* Sections (copied) for the next ntc_decode_fasta or ntc_decode_fasta_unpacked call on this
+ * context: section i covers the next metas[i].n_reads reads of that call, which then writes
+ * FASTQ -- "@seq.{id}\n{read}\n+\n{qualities}\n" -- instead of FASTA, and returns
+ * NTC_ERR_FORMAT (no text) when the sections do not cover exactly its reads, a block's
+ * n_quals differs from the bases decoded for its reads, or a code is >= n_syms.  Checked here,
+ * NTC_ERR_FORMAT: each width against n_syms, an ascending alphabet within '!'..'~',
+ * payload_bytes of every section, and that it lies 8-byte aligned inside the payload.  The
+ * sections are dropped by the call that used them, whatever it returned (a call that only
+ * reports sizes keeps them); ntc_decode_batch and ntc_decode_batch_device ignore them.
+ * n_blocks = 0 drops pending sections.                                                      */
+int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t n_blocks, const uint8_t *payload,
+                             uint64_t payload_bytes);
+
+/* ---- quality side file ("NTCQ", version 1) -------------------------------------------------- */
+/* The quality sections of an encoded.dat, beside it.  Everything little-endian:
+ *   header, 32 bytes: "NTCQ", u32 version = 1, u8 mode (1 keep, 2 bin8), 23 zero bytes
+ *   sections until the end of the file, section i for block i of encoded.dat:
+ *     24 bytes: u64 n_reads, u64 n_quals, u8 width, u8 n_syms, u16 0, u32 gz_bytes
+ *     n_syms alphabet bytes
+ *     one gzip member of gz_bytes bytes holding the section's words (gz_bytes = 0 at width 0)
+ * ntc_q_write_header / ntc_q_write_section (host) write them to fd; ntc_q_deflate_section
+ * returns a section's bytes (free with ntc_buffer_free) so that a thread pool can make them.
+ * words = the section's payload_bytes bytes; engine as for ntc_deflate_block.  NTC_ERR_IO on a
+ * short write, NTC_ERR_INVALID_ARG for a meta that is not canonical.
+ * ntc_q_read (host) parses and validates the file at path: *metas (payload_off into *payload;
+ * both freed with ntc_buffer_free, null when empty), *mode.  NTC_ERR_IO if it cannot be read;
+ * NTC_ERR_FORMAT for a bad magic, version or mode, a truncated header, alphabet or member, a
+ * width that does not follow from n_syms, an alphabet that is not ascending or leaves
+ * '!'..'~', a member that does not inflate to exactly payload_bytes, non-zero padding bits.  */
+int ntc_q_write_header(int fd, int mode);
+int ntc_q_deflate_section(const ntc_qual_meta *meta, const uint8_t *words, int engine, uint8_t **out,
+                          uint64_t *out_len);
+int ntc_q_write_section(int fd, const ntc_qual_meta *meta, const uint8_t *words, int engine);
+int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_blocks, uint8_t **payload,
+               uint64_t *payload_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,42 @@ int ntc_encode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int
 int ntc_decode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats);
 
+/* ---- both side files: exceptions and quality scores ----------------------------------------- */
+/* ntc_encode_file_ex / ntc_decode_file_ex take both side files in one options struct, so that
+ * --non-acgt keep and --qualities keep work together.
+ * Encode: nx_policy / nx_fd as ntc_encode_file_nx takes them.  q_mode 0 (drop): no quality
+ * file, q_fd must be -1.  q_mode 1 (keep) or 2 (bin8, ntcomp_codec.h): every block written to
+ * encoded.dat gets its quality section in the "NTCQ" file at q_fd (>= 0, not closed), packed
+ * on the GPU and deflated by the pipeline's pool with the block's streams; a block the
+ * pipeline drops takes its section with it.  encoded.dat is byte for byte that of a run
+ * without qualities, and the side file does not depend on the number of contexts or on
+ * whether the same text came plain or compressed.  Qualities exist only where the GPU parses
+ * the FASTQ text: host_parse = 1, an input that is not FASTQ, and a batch that falls back to
+ * the host parser (a blank line) are NTC_ERR_UNSUPPORTED under modes 1 and 2, with the case
+ * in stats->error.  The contexts' "qualities" option is set for the call and left at 0.
+ * q (may be NULL): sections and qualities written, their packed and deflated bytes.
+ * Decode: nx_path as for ntc_decode_file_nx; q_path (NULL: none) = the "NTCQ" file, read once
+ * (ntc_q_read); section i belongs to block i of encoded.dat, each batch gets its blocks'
+ * sections and the output is FASTQ, "@seq.N\n{read}\n+\n{qualities}\n".  An input that ended
+ * cleanly must have used exactly all sections, else NTC_ERR_FORMAT; a damaged encoded.dat
+ * keeps ntc_decode_file's semantics (the output ends, dropped_blocks > 0).  The fds and
+ * paths of the other direction are ignored.                                                   */
+typedef struct ntc_file_opts {
+    int32_t nx_policy;   /* NTC_NX_*                                         */
+    int32_t nx_fd;       /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;      /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;        /* encode: quality file, -1 = none                  */
+    const char *nx_path; /* decode: exceptions file, NULL = none             */
+    const char *q_path;  /* decode: quality file, NULL = none                */
+} ntc_file_opts;
+typedef struct ntc_q_stats {
+    uint64_t sections, quals, packed_bytes, deflated_bytes;
+} ntc_q_stats;
+int ntc_encode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts *fo,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q);
+int ntc_decode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts *fo,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

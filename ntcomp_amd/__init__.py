@@ -49,6 +49,8 @@ EXPORTED = [
     "ntc_index_prefix_table", "ntc_index_share", "ntc_index_prepare", "ntc_index_upload_prepared", "ntc_index_prep_free",
     "ntc_encode_exceptions", "ntc_decode_set_exceptions", "ntc_nx_write", "ntc_nx_read", "ntc_encode_file_nx",
     "ntc_decode_file_nx",
+    "ntc_encode_qualities", "ntc_decode_set_qualities", "ntc_q_write_header", "ntc_q_deflate_section",
+    "ntc_q_write_section", "ntc_q_read", "ntc_encode_file_ex", "ntc_decode_file_ex",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -56,6 +58,14 @@ NON_ACGT = {"error": 0, "mask": 1, "keep": 2}
 NX_SYMBOLS = b"N-BDHVRYSWKM"
 # ntc_nx_run: an exception run, 24 bytes
 NX_RUN = np.dtype([("read", "<u8"), ("pos", "<u4"), ("len", "<u4"), ("sym", "<u4"), ("reserved", "<u4")])
+
+
+# quality modes (ctx option "qualities", include/ntcomp_codec.h)
+QUALITIES = {"drop": 0, "keep": 1, "bin8": 2}
+
+
+def _quality_code(qualities):
+    return QUALITIES[qualities] if isinstance(qualities, str) else int(qualities)
 
 
 def _policy_code(non_acgt):
@@ -84,6 +94,13 @@ class BlockMeta(ctypes.Structure):
                 ("status", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
 
 
+class QualMeta(ctypes.Structure):
+    """ntc_qual_meta (include/ntcomp_codec.h): the quality section of one block."""
+    _fields_ = [("n_reads", ctypes.c_uint64), ("n_quals", ctypes.c_uint64), ("payload_off", ctypes.c_uint64),
+                ("payload_bytes", ctypes.c_uint64), ("width", ctypes.c_uint8), ("n_syms", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 6), ("alphabet", ctypes.c_uint8 * 96)]
+
+
 DEFLATE_ENGINES = {"zlib": 0, "libdeflate": 1, "adaptive": 2}  # NTC_DEFLATE_* (include/ntcomp_codec.h)
 
 
@@ -104,6 +121,17 @@ class PipelineStats(ctypes.Structure):
 class NxStats(ctypes.Structure):
     """ntc_nx_stats (include/ntcomp_pipeline.h)."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("runs", "bases", "reads", "runs_in_dropped_blocks")]
+
+
+class FileOpts(ctypes.Structure):
+    """ntc_file_opts (include/ntcomp_pipeline.h): both side files of a file-to-file call."""
+    _fields_ = [("nx_policy", ctypes.c_int32), ("nx_fd", ctypes.c_int32), ("q_mode", ctypes.c_int32),
+                ("q_fd", ctypes.c_int32), ("nx_path", ctypes.c_char_p), ("q_path", ctypes.c_char_p)]
+
+
+class QStats(ctypes.Structure):
+    """ntc_q_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("sections", "quals", "packed_bytes", "deflated_bytes")]
 
 
 class BuildOpts(ctypes.Structure):
@@ -245,10 +273,21 @@ def lib():
         "ntc_decode_fasta_unpacked": (I, [P, u64, P, u64, ctypes.POINTER(u64)]),
         "ntc_encode_exceptions": (I, [P, P, u64, ctypes.POINTER(u64)]),
         "ntc_decode_set_exceptions": (I, [P, P, u64, u32]),
+        "ntc_encode_qualities": (I, [P, P, u64, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "ntc_decode_set_qualities": (I, [P, P, u64, P, u64]),
+        "ntc_q_write_header": (I, [I, I]),
+        "ntc_q_deflate_section": (I, [P, P, I, ctypes.POINTER(P), ctypes.POINTER(u64)]),
+        "ntc_q_write_section": (I, [I, P, P, I]),
+        "ntc_q_read": (I, [ctypes.c_char_p, ctypes.POINTER(I), ctypes.POINTER(P), ctypes.POINTER(u64),
+                           ctypes.POINTER(P), ctypes.POINTER(u64)]),
         "ntc_nx_write": (I, [I, P, u64, u32, I]),
         "ntc_nx_read": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "ntc_encode_file_nx": (I, [P, I, ctypes.c_char_p, I, I, I, ctypes.POINTER(PipelineOpts),
                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats)]),
+        "ntc_encode_file_ex": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts), ctypes.POINTER(PipelineOpts),
+                                   ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats)]),
+        "ntc_decode_file_ex": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts), ctypes.POINTER(PipelineOpts),
+                                   ctypes.POINTER(PipelineStats)]),
         "ntc_decode_file_nx": (I, [P, I, ctypes.c_char_p, ctypes.c_char_p, I, ctypes.POINTER(PipelineOpts),
                                    ctypes.POINTER(PipelineStats)]),
     }
@@ -467,6 +506,47 @@ class GpuContext:
     def _policy(self, non_acgt):
         return GpuContext._Policy(self, non_acgt)
 
+    # ---- quality scores -------------------------------------------------------------
+    class _Option:
+        """`with ctx._option(key, v)`: the context's option is v inside (None: left alone)."""
+
+        def __init__(self, ctx, key, value):
+            self.ctx, self.key, self.new = ctx, key, value
+
+        def __enter__(self):
+            if self.new is not None:
+                self.old = self.ctx.get_option(self.key)
+                self.ctx.set_option(self.key, self.new)
+
+        def __exit__(self, *exc):
+            if self.new is not None:
+                self.ctx.set_option(self.key, self.old)
+
+    def _qmode(self, qualities):
+        return GpuContext._Option(self, "qualities", None if qualities is None else _quality_code(qualities))
+
+    def qualities(self):
+        """The quality sections of the last encode_pack_fastq call under "keep" or "bin8"
+        (ntc_encode_qualities) -> (list of QualMeta, their packed words as bytes)."""
+        nb, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.L.ntc_encode_qualities(self.h, None, 0, None, 0, ctypes.byref(nb), ctypes.byref(nbytes))
+        if rc not in (0, 5):
+            self._check(rc, "ntc_encode_qualities")
+        metas = (QualMeta * max(nb.value, 1))()
+        pay = np.zeros(max(nbytes.value, 8), dtype=np.uint8)
+        if nb.value:
+            self._check(self.L.ntc_encode_qualities(self.h, metas, nb.value, _p(pay), len(pay), ctypes.byref(nb),
+                                                    ctypes.byref(nbytes)), "ntc_encode_qualities")
+        return list(metas)[:nb.value], pay[:nbytes.value].tobytes()
+
+    def set_qualities(self, metas, payload):
+        """Quality sections (QualMeta, in read order) for the next decode_fasta /
+        decode_fasta_unpacked call, which then returns FASTQ (ntc_decode_set_qualities)."""
+        arr = (QualMeta * max(len(metas), 1))(*metas)
+        buf = np.frombuffer(bytes(payload), dtype=np.uint8) if len(payload) else np.zeros(8, dtype=np.uint8)
+        self._check(self.L.ntc_decode_set_qualities(self.h, arr, len(metas), _p(buf), len(payload)),
+                    "ntc_decode_set_qualities")
+
     def exceptions(self):
         """The exception runs of the last encode / encode_pack / encode_pack_fastq call under
         policy keep (ntc_encode_exceptions), as a structured array of dtype NX_RUN in (read,
@@ -615,15 +695,16 @@ class GpuContext:
             raise e
         return bases[:nb.value].copy(), offs
 
-    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None):
+    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None):
         """encode_pack on FASTQ text parsed on the GPU (ntc_encode_pack_fastq) -> (list of
         BlockMeta, payload bytes, bases encoded).  With non_acgt (as for encode) the exception
-        runs come fourth."""
+        runs come fourth.  With qualities ("drop", "keep" or "bin8"; the call runs under that
+        mode) the quality sections come last, as qualities() returns them."""
         t = np.frombuffer(bytes(text), dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
         nb = (n_reads + block_reads - 1) // block_reads
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
-        with self._policy(non_acgt):
+        with self._policy(non_acgt), self._qmode(qualities):
             rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas,
                                               ctypes.byref(out), ctypes.byref(used), ctypes.byref(nbases),
                                               ctypes.byref(bad))
@@ -636,9 +717,12 @@ class GpuContext:
             payload = ctypes.string_at(out.value, used.value) if used.value else b""
         finally:
             self.L.ntc_buffer_free(out)
+        out = (list(metas)[:nb], payload, int(nbases.value))
         if non_acgt is not None:
-            return list(metas)[:nb], payload, int(nbases.value), self.exceptions()
-        return list(metas)[:nb], payload, int(nbases.value)
+            out += (self.exceptions(),)
+        if qualities is not None:
+            out += (self.qualities(),)
+        return out
 
     def encode_status(self):
         bad, n = ctypes.c_int64(-1), ctypes.c_uint64()
@@ -899,15 +983,25 @@ def concat_streams(blocks):
 
 # ---- FASTX ingest ---------------------------------------------------------------------
 def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_bases=0, deflate="zlib",
-                host_parse=False, non_acgt=None, nx_fd=-1):
+                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1):
     """`ntcomp encode` file to file (ntc_encode_file, include/ntcomp_pipeline.h): FASTX ->
     GPU encode + block packer on every context -> deflate pool -> encoded.dat on out_fd.
     A plain FASTQ is parsed on the GPU unless host_parse.  Returns the per-stage stats as
     a dict (gpu_parsed = batches parsed on the GPU); raises NtcError (with .bad_read).
     non_acgt ("error", "mask", "keep"; ntc_encode_file_nx): what becomes of N and IUPAC
     symbols; "keep" writes their exception runs to nx_fd, and the stats gain an "nx" dict
-    (ntc_nx_stats)."""
+    (ntc_nx_stats).  qualities ("drop", "keep", "bin8"; ntc_encode_file_ex): "keep" and "bin8"
+    write the blocks' quality sections to q_fd ("NTCQ"), and the stats gain a "q" dict
+    (ntc_q_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
+    if qualities is not None:
+        fo = FileOpts(_policy_code(non_acgt or 0), nx_fd, _quality_code(qualities), q_fd, None, None)
+        nx, q = NxStats(), QStats()
+        d = _run_pipeline("ntc_encode_file_ex", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                          tail=(ctypes.byref(nx), ctypes.byref(q)))
+        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
+        d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
+        return d
     if non_acgt is None:
         return _run_pipeline("ntc_encode_file", ctxs, in_path, out_fd, o)
     nx = NxStats()
@@ -917,15 +1011,19 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     return d
 
 
-def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None):
+def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
     blocks before it without an error, like decode_block's Err ends the reference's loop
     (src/main.rs:202): stats["dropped_blocks"] > 0 and stats["error"] say so.  nx_path: the
     exception side file written by encode_file(non_acgt="keep"), whose symbols are put back
-    (ntc_decode_file_nx)."""
+    (ntc_decode_file_nx).  q_path: the quality side file written by encode_file(qualities=
+    "keep" / "bin8"); the output is then FASTQ (ntc_decode_file_ex)."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
+    if q_path is not None:
+        fo = FileOpts(0, -1, 0, -1, None if nx_path is None else os.fsencode(nx_path), os.fsencode(q_path))
+        return _run_pipeline("ntc_decode_file_ex", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),))
     if nx_path is None:
         return _run_pipeline("ntc_decode_file", ctxs, in_path, out_fd, o)
     return _run_pipeline("ntc_decode_file_nx", ctxs, in_path, out_fd, o, pre_fd=(os.fsencode(nx_path),))
@@ -945,6 +1043,42 @@ def read_exceptions(path):
     finally:
         lib().ntc_buffer_free(p)
     return runs, int(sub.value)
+
+
+def read_qualities(path):
+    """The quality side file ("NTCQ", include/ntcomp_codec.h) written beside an encoded.dat:
+    ntc_q_read -> (mode as an int, list of QualMeta, the inflated words as bytes);
+    NtcError(NTC_ERR_FORMAT) for a malformed file."""
+    mode, pm, nb, pp, nbytes = ctypes.c_int(), ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_uint64()
+    rc = lib().ntc_q_read(os.fsencode(path), ctypes.byref(mode), ctypes.byref(pm), ctypes.byref(nb), ctypes.byref(pp),
+                          ctypes.byref(nbytes))
+    if rc:
+        raise NtcError(rc, f"ntc_q_read({path})")
+    try:
+        metas = [QualMeta.from_buffer_copy(ctypes.string_at(pm.value + i * ctypes.sizeof(QualMeta), ctypes.sizeof(QualMeta)))
+                 for i in range(nb.value)]
+        payload = ctypes.string_at(pp.value, nbytes.value) if nbytes.value else b""
+    finally:
+        lib().ntc_buffer_free(pm)
+        lib().ntc_buffer_free(pp)
+    return int(mode.value), metas, payload
+
+
+def write_qualities(fd, mode, metas, payload, header=True, engine="libdeflate"):
+    """The "NTCQ" header (when header) and one section per QualMeta to fd (ntc_q_write_header,
+    ntc_q_write_section); payload: the words the metas' payload_off point into."""
+    if header:
+        rc = lib().ntc_q_write_header(fd, _quality_code(mode))
+        if rc:
+            raise NtcError(rc, "ntc_q_write_header")
+    buf = np.frombuffer(bytes(payload), dtype=np.uint8) if len(payload) else np.zeros(8, dtype=np.uint8)
+    for m in metas:
+        if m.payload_off + m.payload_bytes > len(payload):
+            raise NtcError(1, "section outside the payload")
+        rc = lib().ntc_q_write_section(fd, ctypes.byref(m), ctypes.c_void_p(buf.ctypes.data + m.payload_off),
+                                       DEFLATE_ENGINES[engine])
+        if rc:
+            raise NtcError(rc, "ntc_q_write_section")
 
 
 def write_exceptions(fd, runs, sub, header=True):

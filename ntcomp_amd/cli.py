@@ -178,11 +178,22 @@ def _devices(args):
     return list(range(args.gpus))
 
 
+def _check_q_args(args):
+    """encode: --qualities drop|keep|bin8 and --quality-file PATH go together under keep and bin8."""
+    if args.qualities not in ("drop", "keep", "bin8"):
+        _bad_args("encode: --qualities: drop, keep or bin8")
+    if args.qualities != "drop" and not args.quality_file:
+        _bad_args(f"encode: --qualities {args.qualities} requires --quality-file PATH")
+    if args.qualities == "drop" and args.quality_file is not None:
+        _bad_args("encode: --quality-file is only written under --qualities keep or bin8")
+
+
 def cmd_encode(args):
     """main.rs:141-181 through the native pipeline (ntc_encode_file): plain FASTQ parsed
     on the GPU (--host-parse: on the host pool, as every other input is), GPU encode +
     block packer per context, deflate on the host pool, blocks written in file order."""
     _check_nx_args(args)
+    _check_q_args(args)
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     log("Loading SBWT index...")
@@ -193,8 +204,13 @@ def cmd_encode(args):
         args.deflate = "adaptive" if nt.libdeflate_available() else "zlib"
     out = sys.stdout.buffer
     out.flush()
-    nx_file = None
+    nx_file = q_file = None
     try:
+        if args.qualities != "drop":
+            try:
+                q_file = open(args.quality_file, "wb")
+            except OSError:
+                raise SystemExit(f"ntcomp: encode: cannot write {args.quality_file}")
         if args.non_acgt == "keep":
             try:
                 nx_file = open(args.exceptions, "wb")
@@ -202,6 +218,8 @@ def cmd_encode(args):
                 raise SystemExit(f"ntcomp: encode: cannot write {args.exceptions}")
         nx_args = {} if args.non_acgt == "error" else {"non_acgt": args.non_acgt,
                                                        "nx_fd": nx_file.fileno() if nx_file else -1}
+        if q_file:
+            nx_args.update(qualities=args.qualities, q_fd=q_file.fileno())
         res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, deflate=args.deflate,
                                                   host_parse=args.host_parse, **nx_args)
@@ -211,6 +229,8 @@ def cmd_encode(args):
     finally:
         if nx_file:
             nx_file.close()
+        if q_file:
+            q_file.close()
         for c in ctxs:
             c.close()
     if res["dropped_blocks"]:
@@ -223,7 +243,8 @@ def cmd_encode(args):
               dropped_blocks=res["dropped_blocks"], pipeline_wall_s=round(res["wall_s"], 3), deflate=args.deflate,
               gpu_parsed_batches=res["gpu_parsed"], non_acgt=args.non_acgt,
               **{"nx_" + k: v for k, v in res.get("nx", dict.fromkeys(("runs", "bases", "reads",
-                                                                        "runs_in_dropped_blocks"), 0)).items()})
+                                                                        "runs_in_dropped_blocks"), 0)).items()},
+              **({"qualities": args.qualities, **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}))
 
 
 def cmd_decode(args):
@@ -239,7 +260,8 @@ def cmd_decode(args):
     out.flush()
     try:
         res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, out.fileno(), threads=args.threads,
-                                                  blocks_per_batch=args.blocks_per_batch, nx_path=args.exceptions)
+                                                  blocks_per_batch=args.blocks_per_batch, nx_path=args.exceptions,
+                                                  q_path=args.quality_file)
     except nt.NtcError as e:
         raise SystemExit(f"ntcomp decode: {e}")
     finally:
@@ -308,6 +330,10 @@ def main(argv=None):
                         "by the substitute base (lossy), keep also writes the replaced symbols to the --exceptions "
                         "file (lossless)")
     e.add_argument("--exceptions", metavar="PATH", help="with --non-acgt keep: the side file to write")
+    e.add_argument("--qualities", default="drop", metavar="MODE",
+                   help="FASTQ quality scores: drop (default), keep (lossless) or bin8 (Phred scores binned to 8 levels, "
+                        "lossy); keep and bin8 write them, packed on the GPU, to the --quality-file")
+    e.add_argument("--quality-file", metavar="PATH", help="with --qualities keep or bin8: the side file to write")
     d = sub.add_parser("decode", help="Decode data written with Encode")
     d.add_argument("input_path", help="File with encoded fastX data.")
     d.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
@@ -318,6 +344,8 @@ def main(argv=None):
                    help="contexts per device sharing one index copy; calls alternate over them")
     d.add_argument("--blocks-per-batch", type=int, default=2, help="blocks per GPU call")
     d.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
+    d.add_argument("--quality-file", metavar="PATH",
+                   help="the side file of encode --qualities keep or bin8: the output is then FASTQ")
     d.add_argument("--exceptions", metavar="PATH",
                    help="the side file of encode --non-acgt keep, whose symbols are put back")
     args = ap.parse_args(argv)

@@ -32,6 +32,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -40,12 +41,15 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ntcomp_codec.h"
+#include "../../include/ntcomp_host.h"
 #include "ntc_internal.h"
 #include "codec_params.h"
 #include "nonacgt_core.h"
+#include "quality_core.h"
 
 namespace {
 
@@ -874,6 +878,153 @@ int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t 
     }
     *n_runs = all.size();
     *sub = buf[8];
+    return NTC_OK;
+}
+
+// ---- quality side file "NTCQ" (include/ntcomp_codec.h) --------------------------------
+int ntc_q_write_header(int fd, int mode) {
+    if (fd < 0 || mode < 1 || mode > 2) return NTC_ERR_INVALID_ARG;
+    const uint8_t h[32] = {'N', 'T', 'C', 'Q', 1, 0, 0, 0, (uint8_t)mode};
+    return nx_write_all(fd, h, sizeof(h)) ? NTC_OK : NTC_ERR_IO;
+}
+
+int ntc_q_deflate_section(const ntc_qual_meta *meta, const uint8_t *words, int engine, uint8_t **out, uint64_t *out_len) {
+    if (!meta || !out || !out_len || (meta->payload_bytes && !words)) return NTC_ERR_INVALID_ARG;
+    *out = nullptr;
+    *out_len = 0;
+    if (!ntc::q_meta_ok(meta->n_quals, meta->width, meta->n_syms, meta->alphabet) ||
+        meta->payload_bytes != ntc::q_words(meta->n_quals, meta->width) * 8)
+        return NTC_ERR_INVALID_ARG;
+    std::vector<uint8_t> buf(24);
+    buf.insert(buf.end(), meta->alphabet, meta->alphabet + meta->n_syms);
+    if (meta->width && !gzip_append(words, meta->payload_bytes, engine, buf)) return NTC_ERR_FORMAT;
+    const uint64_t gz = buf.size() - 24 - meta->n_syms;
+    if (gz >> 32) return NTC_ERR_CAPACITY;
+    std::memcpy(buf.data(), &meta->n_reads, 8);  // little-endian hosts only, as the block container
+    std::memcpy(buf.data() + 8, &meta->n_quals, 8);
+    buf[16] = meta->width;
+    buf[17] = meta->n_syms;
+    const uint32_t gz32 = (uint32_t)gz;
+    std::memcpy(buf.data() + 20, &gz32, 4);
+    return hand_out(buf, out, out_len);
+}
+
+int ntc_q_write_section(int fd, const ntc_qual_meta *meta, const uint8_t *words, int engine) {
+    if (fd < 0) return NTC_ERR_INVALID_ARG;
+    uint8_t *sec = nullptr;
+    uint64_t n = 0;
+    const int rc = ntc_q_deflate_section(meta, words, engine, &sec, &n);
+    if (rc) return rc;
+    const bool ok = nx_write_all(fd, sec, n);
+    std::free(sec);
+    return ok ? NTC_OK : NTC_ERR_IO;
+}
+
+int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_blocks, uint8_t **payload,
+               uint64_t *payload_bytes) {
+    if (!path || !mode || !metas || !n_blocks || !payload || !payload_bytes) return NTC_ERR_INVALID_ARG;
+    *mode = 0;
+    *metas = nullptr;
+    *n_blocks = 0;
+    *payload = nullptr;
+    *payload_bytes = 0;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return NTC_ERR_IO;
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+    const bool io_bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (io_bad) return NTC_ERR_IO;
+    static const uint8_t magic[8] = {'N', 'T', 'C', 'Q', 1, 0, 0, 0};
+    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
+    if (buf[8] < 1 || buf[8] > 2) return NTC_ERR_FORMAT;
+    for (size_t i = 9; i < 32; i++)
+        if (buf[i]) return NTC_ERR_FORMAT;
+    // pass 1: the headers and alphabets, and where each member lies and inflates to
+    std::vector<ntc_qual_meta> all;
+    std::vector<uint64_t> gz_at, gz_len;
+    uint64_t pay_bytes = 0;
+    size_t at = 32;
+    while (at < buf.size()) {
+        if (buf.size() - at < 24) return NTC_ERR_FORMAT;
+        ntc_qual_meta m;
+        std::memset(&m, 0, sizeof(m));
+        const uint8_t *h = buf.data() + at;
+        std::memcpy(&m.n_reads, h, 8);
+        std::memcpy(&m.n_quals, h + 8, 8);
+        m.width = h[16];
+        m.n_syms = h[17];
+        uint32_t gz;
+        std::memcpy(&gz, h + 20, 4);
+        at += 24;
+        if (h[18] || h[19] || m.n_syms > 94 || buf.size() - at < m.n_syms) return NTC_ERR_FORMAT;
+        std::memcpy(m.alphabet, buf.data() + at, m.n_syms);
+        at += m.n_syms;
+        if (!ntc::q_meta_ok(m.n_quals, m.width, m.n_syms, m.alphabet) || m.n_quals > m.n_reads * (1ull << 32))
+            return NTC_ERR_FORMAT;
+        if (buf.size() - at < gz || (gz == 0) != (m.width == 0)) return NTC_ERR_FORMAT;
+        const uint64_t nw = ntc::q_words(m.n_quals, m.width);
+        if (nw * 8 > (uint64_t)gz * 1100 + 4096) return NTC_ERR_FORMAT;  // past deflate's best ratio: not this member
+        m.payload_off = pay_bytes;
+        m.payload_bytes = nw * 8;
+        pay_bytes += nw * 8;
+        gz_at.push_back(at);
+        gz_len.push_back(gz);
+        at += gz;
+        all.push_back(m);
+    }
+    // pass 2: the members inflate side by side (a file of whole blocks holds ~10 MB each)
+    std::vector<uint8_t> pay(pay_bytes);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> bad{false};
+    const auto work = [&] {
+        std::vector<uint8_t> words;
+        for (size_t i; (i = next.fetch_add(1)) < all.size() && !bad;) {
+            const ntc_qual_meta &m = all[i];
+            if (!m.width) continue;
+            if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, words)) {
+                bad = true;
+                return;
+            }
+            const uint64_t bits = m.n_quals * m.width;  // padding bits of the last word
+            if (bits & 63) {
+                uint64_t last;
+                std::memcpy(&last, words.data() + m.payload_bytes - 8, 8);
+                if (last >> (bits & 63)) {
+                    bad = true;
+                    return;
+                }
+            }
+            std::memcpy(pay.data() + m.payload_off, words.data(), m.payload_bytes);
+        }
+    };
+    {
+        const size_t T = std::min<size_t>(all.size(), (size_t)std::max(1, std::min(16, ntc_host_threads())));
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < T; t++) pool.emplace_back(work);
+        work();
+        for (auto &t : pool) t.join();
+    }
+    if (bad) return NTC_ERR_FORMAT;
+    if (!all.empty()) {
+        *metas = (ntc_qual_meta *)std::malloc(all.size() * sizeof(ntc_qual_meta));
+        if (!*metas) return NTC_ERR_CAPACITY;
+        std::memcpy(*metas, all.data(), all.size() * sizeof(ntc_qual_meta));
+    }
+    if (!pay.empty()) {
+        *payload = (uint8_t *)std::malloc(pay.size());
+        if (!*payload) {
+            std::free(*metas);
+            *metas = nullptr;
+            return NTC_ERR_CAPACITY;
+        }
+        std::memcpy(*payload, pay.data(), pay.size());
+    }
+    *mode = buf[8];
+    *n_blocks = all.size();
+    *payload_bytes = pay.size();
     return NTC_OK;
 }
 

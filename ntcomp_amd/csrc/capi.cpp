@@ -20,6 +20,7 @@
 #include "derived.h"
 #include "kernels.h"
 #include "nonacgt_core.h"
+#include "quality_core.h"
 #include "ntc_internal.h"
 
 using namespace ntc;
@@ -43,7 +44,8 @@ enum WsSlot {
     WS_PACK_PAYLOAD, WS_FA_BASES, WS_FA_OFFS, WS_FA_SCAN, WS_ES, WS_OBASE,
     WS_FQ_RAW, WS_FQ_TILES, WS_FQ_NL, WS_FQ_KEPT, WS_PACK_SEGS,
     WS_UNP_PAY, WS_UNP_MARKS, WS_UNP_ST, WS_UNP_VALS, WS_UNP_RECS, WS_UNP_OUT,
-    WS_NX_BITS, WS_NX_RUNS, WS_NX_PATCH, WS_COUNT
+    WS_NX_BITS, WS_NX_RUNS, WS_NX_PATCH,
+    WS_Q_QUALS, WS_Q_BLOCKS, WS_Q_PAYLOAD, WS_QD_IN, WS_QD_QUALS, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -130,6 +132,15 @@ struct ntc_ctx {
     std::vector<ntc_nx_run> nx_pieces;     // the slices of the decode pass in flight (source of an async copy)
     uint32_t nx_pending_sub = 0;
     bool nx_has_pending = false;
+    // quality scores (quality.hip): the mode (0 drop, 1 keep, 2 bin8), the sections the last
+    // ntc_encode_pack_fastq left in WS_Q_BLOCKS / WS_Q_PAYLOAD, the sections waiting for the
+    // next FASTA decode call (which then writes FASTQ)
+    int q_mode = 0;
+    uint64_t q_blocks = 0, q_words = 0, q_reads = 0;
+    uint32_t q_block_reads = 0;
+    std::vector<ntc_qual_meta> qd_metas;
+    std::vector<uint64_t> qd_payload;
+    bool qd_has_pending = false;
     FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
@@ -576,6 +587,129 @@ bool nx_take_pending(ntc_ctx *ctx, std::vector<ntc_nx_run> &runs, uint32_t &sub)
     sub = ctx->nx_pending_sub;
     ctx->nx_has_pending = false;
     return !runs.empty();
+}
+
+// ---- quality scores (quality.hip) -------------------------------------------------------
+// After a GPU FASTQ parse (the text, its newline table and the read offsets are in HBM):
+// gather, alphabets, pack.  Asynchronous: the pass has a status word of its own (d_status is
+// preset again by the encode that follows), which reaches the host with the payload's size
+// in mailbox words 6 and 7 at the encode call's own status sync (q_collect).  Mode 0 returns
+// before anything is launched.
+void q_begin(ntc_ctx *ctx) {  // an encode call starts: the last call's sections are gone
+    ctx->q_blocks = ctx->q_words = ctx->q_reads = 0;
+}
+int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t total, uint32_t block_reads) {
+    if (ctx->q_mode == 0 || n_reads == 0) return NTC_OK;
+    const uint64_t nb = (n_reads + block_reads - 1) / block_reads;
+    void *quals, *blk, *pay;
+    int rc;
+    if ((rc = ensure(ctx, WS_Q_QUALS, total + 64, &quals))) return rc;
+    // the status word, the presence maps (16 B per block), the blocks and their totals
+    if ((rc = ensure(ctx, WS_Q_BLOCKS, 64 + nb * 16 + (nb + 1) * sizeof(QBlock), &blk))) return rc;
+    if ((rc = ensure(ctx, WS_Q_PAYLOAD, q_payload_words_max(total, nb) * 8, &pay))) return rc;
+    const FastqArgs &f = ctx->fq_last;
+    QEncArgs a{};
+    a.raw = f.raw;
+    a.n_raw = f.n_raw;
+    a.nl = f.nl;
+    a.n_nl_p = f.tile_base + fastq_tiles(f.n_raw);
+    a.offs = d_offs;
+    a.n_reads = n_reads;
+    a.n_blocks = nb;
+    a.block_reads = block_reads;
+    a.mode = (uint32_t)ctx->q_mode;
+    a.quals = (uint8_t *)quals;
+    a.status = (unsigned long long *)blk;
+    a.pres = (uint32_t *)((uint8_t *)blk + 64);
+    a.blocks = (QBlock *)((uint8_t *)blk + 64 + nb * 16);
+    a.payload = (uint64_t *)pay;
+    a.box = ctx->h_box;
+    ctx->h_box[6] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
+    ctx->h_box[7] = 0;
+    launch_quality_pack(a, total, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+// After the encode call's sync: the quality pass's verdict.  A read it refused fails the call.
+int q_collect(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads, int64_t *bad_read) {
+    if (ctx->q_mode == 0 || n_reads == 0) return NTC_OK;
+    const uint64_t st = ((volatile uint64_t *)ctx->h_box)[6];
+    if (st != ~0ull) {
+        if (bad_read) *bad_read = (int64_t)(st >> 8);
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "quality line of read %lld: its length differs from the bases kept, or a "
+                                        "byte lies outside '!'..'~'", (long long)(st >> 8));
+        return set_err(ctx, (int)(st & 0xFF), buf);
+    }
+    ctx->q_blocks = (n_reads + block_reads - 1) / block_reads;
+    ctx->q_words = ((volatile uint64_t *)ctx->h_box)[7];
+    ctx->q_reads = n_reads;
+    ctx->q_block_reads = block_reads;
+    return NTC_OK;
+}
+int q_unsupported(ntc_ctx *ctx, const char *call) {
+    return set_err(ctx, NTC_ERR_UNSUPPORTED, std::string(call) + " takes bases without quality lines: qualities keep / "
+                                             "bin8 need ntc_encode_pack_fastq");
+}
+
+// the pending sections leave the context: the call that takes them uses them once
+bool q_take_pending(ntc_ctx *ctx, std::vector<ntc_qual_meta> &metas, std::vector<uint64_t> &payload) {
+    metas.clear();
+    payload.clear();
+    if (!ctx->qd_has_pending) return false;
+    metas.swap(ctx->qd_metas);
+    payload.swap(ctx->qd_payload);
+    ctx->qd_has_pending = false;
+    return true;
+}
+
+// Decode side: the sections over the decoded reads' offsets -> quality bytes (WS_QD_QUALS);
+// then the status mailbox again, as the unpack may have set the status.
+int q_unpack(ntc_ctx *ctx, const std::vector<ntc_qual_meta> &metas, const std::vector<uint64_t> &payload,
+             uint64_t n_reads, uint64_t n_bases, const uint64_t *d_offs, uint8_t **d_quals) {
+    const uint64_t nb = metas.size();
+    std::vector<uint8_t> up(nb * sizeof(QDecBlock));
+    uint64_t r = 0, max_q = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+        const ntc_qual_meta &m = metas[b];
+        QDecBlock k{};
+        k.r0 = r;
+        k.r1 = r += m.n_reads;
+        k.n_quals = m.n_quals;
+        k.word_off = m.payload_off / 8;
+        k.w = m.width;
+        k.n_syms = m.n_syms;
+        std::memcpy(k.alphabet, m.alphabet, 96);
+        std::memcpy(up.data() + b * sizeof(QDecBlock), &k, sizeof(k));
+        max_q = std::max(max_q, m.n_quals);
+        if (r > n_reads) break;
+    }
+    if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "the quality sections do not cover exactly the reads decoded");
+    void *in, *quals;
+    int rc;
+    const uint64_t blk_bytes = (up.size() + 63) & ~63ull;
+    if ((rc = ensure(ctx, WS_QD_IN, blk_bytes + payload.size() * 8 + 64, &in))) return rc;
+    if ((rc = ensure(ctx, WS_QD_QUALS, n_bases + 64, &quals))) return rc;
+    if (!up.empty()) HIP_TRY(ctx, hipMemcpy(in, up.data(), up.size(), hipMemcpyHostToDevice));
+    if (!payload.empty())
+        HIP_TRY(ctx, hipMemcpy((uint8_t *)in + blk_bytes, payload.data(), payload.size() * 8, hipMemcpyHostToDevice));
+    QDecArgs a{};
+    a.blocks = (const QDecBlock *)in;
+    a.n_blocks = nb;
+    a.tiles = quality_unpack_tiles(max_q);
+    a.payload = (const uint64_t *)((uint8_t *)in + blk_bytes);
+    a.offs = d_offs;
+    a.n_reads = n_reads;
+    a.quals = (uint8_t *)quals;
+    a.status = ctx->d_status;
+    launch_quality_unpack(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ctx->box_valid && ctx->last == kDecode)
+        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
+                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    *d_quals = (uint8_t *)quals;
+    return NTC_OK;
 }
 
 // GPU packer (pack.hip) over the records of n_reads reads in HBM: block b = reads
@@ -1254,6 +1388,11 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
         ctx->epool_per_base = ctx->rpool_per_base = 0.0;
         return NTC_OK;
     }
+    if (std::strcmp(key, "qualities") == 0) {  // FASTQ quality scores: 0 drop, 1 keep, 2 bin8 (ntcomp_codec.h)
+        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "qualities must be 0 (drop), 1 (keep) or 2 (bin8)");
+        ctx->q_mode = (int)value;
+        return NTC_OK;
+    }
     if (std::strcmp(key, "non_acgt") == 0) {  // N and IUPAC symbols: 0 error, 1 mask, 2 keep (ntcomp_gpu.h)
         if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)");
         ctx->nx_policy = (int)value;
@@ -1304,6 +1443,7 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "ent_slots") == 0) *value = ent_slots(ctx);
     else if (std::strcmp(key, "spill_reruns") == 0) *value = (int64_t)ctx->spill_reruns;
     else if (std::strcmp(key, "non_acgt") == 0) *value = ctx->nx_policy;
+    else if (std::strcmp(key, "qualities") == 0) *value = ctx->q_mode;
     else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
     else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
     else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
@@ -1333,6 +1473,7 @@ int ntc_encode_batch_device(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t
     if (!ctx || (!d_read_offsets && n_reads) || !d_rec_offsets_out)
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_batch_device");
     if (ctx->nx_policy != 0)
         return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need the host-buffer encode calls "
                                                  "(the caller's device buffer is const)");
@@ -1440,6 +1581,7 @@ int ntc_encode_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_of
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
+    if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_batch");
     nx_begin(ctx);
     if (ctx->encode_variant != 4 && ctx->nx_policy != 0)
         return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need encode_variant 4");
@@ -1715,6 +1857,7 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
+    if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_pack_batch");
     for (uint64_t r = 0; r < n_reads; r++)
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
@@ -1833,7 +1976,10 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     if (rc) return rc;
     if (n_bases) *n_bases = total;
     nx_begin(ctx);
+    q_begin(ctx);
     if (n_reads == 0) return NTC_OK;
+    // the quality lines are packed from the text while the reads are encoded (mode 0: nothing runs)
+    if ((rc = q_pack(ctx, (const uint64_t *)d_offs, n_reads, total, block_reads))) return rc;
     const auto restage = [&]() -> int {  // the text is still in HBM: parse it again (it parsed clean once)
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
         ctx->fq_last.tmp = (uint64_t *)ctx->ws[WS_SCANTMP].p;  // the scan scratch may have grown (never shrinks) since
@@ -1841,8 +1987,19 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
         HIP_TRY(ctx, hipGetLastError());
         return NTC_OK;
     };
-    return encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads,
-                              meta, payload, payload_bytes, bad_read, restage);
+    rc = encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads, meta,
+                            payload, payload_bytes, bad_read, restage);
+    if (ctx->q_mode == 0) return rc;
+    // a read the quality pass refused fails the call, whatever the encode said of it
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (an encode that failed early may not have synchronised)
+    const int qrc = q_collect(ctx, n_reads, block_reads, bad_read);
+    if (rc) q_begin(ctx);  // a failed call leaves no sections
+    if (qrc && !rc) {
+        std::free(*payload);
+        *payload = nullptr;
+        *payload_bytes = 0;
+    }
+    return qrc ? qrc : rc;
 }
 
 }  // extern "C"
@@ -1860,6 +2017,12 @@ uint64_t fasta_bytes(uint64_t n_reads, uint64_t n_bases, uint64_t first_id) {
     return need;
 }
 
+// the text a decode call writes: FASTQ when quality sections are pending ("\n+\n" and the
+// qualities more per read)
+uint64_t text_bytes(const ntc_ctx *ctx, uint64_t n_reads, uint64_t n_bases, uint64_t first_id) {
+    return fasta_bytes(n_reads, n_bases, first_id) + (ctx->qd_has_pending ? n_bases + 3 * n_reads : 0);
+}
+
 // walk + FASTA text of records already in HBM (d_recs), text D2H into out (need bytes)
 int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint64_t n_reads, uint64_t n_bases,
                      uint64_t first_id, uint8_t *out, uint64_t need) {
@@ -1871,17 +2034,35 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if ((rc = ensure(ctx, WS_STAGE_BASES, need + 64, &d_out))) return rc;
     std::vector<ntc_nx_run> nx;
     uint32_t nx_sub = 0;
+    std::vector<ntc_qual_meta> qm;
+    std::vector<uint64_t> qp;
+    const bool fastq = q_take_pending(ctx, qm, qp);  // (both pending lists leave the context here)
     if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= n_reads)
         return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
+    if (fastq) {
+        uint64_t r = 0;
+        for (const ntc_qual_meta &m : qm) {
+            if (m.n_reads > n_reads - r) return set_err(ctx, NTC_ERR_FORMAT, "quality sections for more reads than decoded");
+            r += m.n_reads;
+        }
+        if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "quality sections for fewer reads than decoded");
+    }
     if ((rc = ntc_decode_batch_device(ctx, d_recs, n_recs, (uint8_t *)d_bases, n_bases + 64, (uint64_t *)d_offs,
                                       n_reads + 2)))
         return rc;
     // exception runs go over the substitute bases before the text is formatted
     if (!nx.empty() && (rc = nx_patch(ctx, nx, nx_sub, 0, n_reads, (uint8_t *)d_bases, (const uint64_t *)d_offs)))
         return rc;
+    // and the qualities are unpacked by the decoded reads' offsets, after the patch
+    uint8_t *d_quals = nullptr;
+    if (fastq && (rc = q_unpack(ctx, qm, qp, n_reads, n_bases, (const uint64_t *)d_offs, &d_quals))) return rc;
     uint64_t *sizes = (uint64_t *)d_scan, *out_offs = sizes + (n_reads + 1), *tmp = out_offs + (n_reads + 1);
-    launch_fasta((const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status, sizes, out_offs,
-                 tmp, (uint8_t *)d_out, need, ctx->stream);
+    if (fastq)
+        launch_fastq_text((const uint8_t *)d_bases, d_quals, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status,
+                          sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
+    else
+        launch_fasta((const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status, sizes,
+                     out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, ctx->stream));
     uint64_t nr = 0, nb = 0;
@@ -1925,7 +2106,7 @@ int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
-    const uint64_t need = fasta_bytes(n_reads, n_bases, first_id);
+    const uint64_t need = text_bytes(ctx, n_reads, n_bases, first_id);
     *out_len = need;
     if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
     if (n_recs == 0) return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
@@ -2061,7 +2242,7 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
-    const uint64_t need = fasta_bytes(ctx->unp_reads, ctx->unp_bases, first_id);
+    const uint64_t need = text_bytes(ctx, ctx->unp_reads, ctx->unp_bases, first_id);
     *out_len = need;  // (a size query: out_capacity 0)
     if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
     if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
@@ -2087,6 +2268,59 @@ int ntc_decode_set_exceptions(ntc_ctx *ctx, const ntc_nx_run *runs, uint64_t n_r
         std::stable_sort(ctx->nx_pending.begin(), ctx->nx_pending.end(), less);
     ctx->nx_pending_sub = sub;
     ctx->nx_has_pending = n_runs != 0;
+    return NTC_OK;
+}
+
+int ntc_encode_qualities(ntc_ctx *ctx, ntc_qual_meta *metas, uint64_t meta_cap, uint8_t *payload, uint64_t payload_cap,
+                         uint64_t *n_blocks, uint64_t *payload_bytes) {
+    if (!ctx || !n_blocks || !payload_bytes || (meta_cap && !metas) || (payload_cap && !payload))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_blocks = ctx->q_blocks;
+    *payload_bytes = ctx->q_words * 8;
+    if (ctx->q_blocks > meta_cap || ctx->q_words * 8 > payload_cap)
+        return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the quality sections");
+    if (ctx->q_blocks == 0) return NTC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t nb = ctx->q_blocks;
+    std::vector<QBlock> blk(nb);
+    HIP_TRY(ctx, hipMemcpy(blk.data(), (const uint8_t *)ctx->ws[WS_Q_BLOCKS].p + 64 + nb * 16, nb * sizeof(QBlock),
+                           hipMemcpyDeviceToHost));
+    if (ctx->q_words)
+        HIP_TRY(ctx, hipMemcpy(payload, ctx->ws[WS_Q_PAYLOAD].p, ctx->q_words * 8, hipMemcpyDeviceToHost));
+    for (uint64_t b = 0; b < nb; b++) {
+        ntc_qual_meta &m = metas[b];
+        std::memset(&m, 0, sizeof(m));
+        m.n_reads = std::min<uint64_t>(ctx->q_block_reads, ctx->q_reads - b * ctx->q_block_reads);
+        m.n_quals = blk[b].n_quals;
+        m.payload_off = blk[b].word_off * 8;
+        m.payload_bytes = blk[b].n_words * 8;
+        m.width = (uint8_t)blk[b].w;
+        m.n_syms = (uint8_t)blk[b].n_syms;
+        std::memcpy(m.alphabet, blk[b].alphabet, blk[b].n_syms);
+    }
+    return NTC_OK;
+}
+
+int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t n_blocks, const uint8_t *payload,
+                             uint64_t payload_bytes) {
+    if (!ctx || (n_blocks && !metas) || (payload_bytes && !payload)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    ctx->qd_metas.clear();
+    ctx->qd_payload.clear();
+    ctx->qd_has_pending = false;
+    if (n_blocks == 0) return NTC_OK;
+    if (payload_bytes & 7) return set_err(ctx, NTC_ERR_FORMAT, "quality payload is not whole 64-bit words");
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        const ntc_qual_meta &m = metas[b];
+        if (!q_meta_ok(m.n_quals, m.width, m.n_syms, m.alphabet))
+            return set_err(ctx, NTC_ERR_FORMAT, "quality section " + std::to_string(b) + ": width, n_syms or alphabet");
+        if (m.n_quals >> 40 || m.payload_bytes != q_words(m.n_quals, m.width) * 8 || (m.payload_off & 7) ||
+            m.payload_off > payload_bytes || m.payload_bytes > payload_bytes - m.payload_off)
+            return set_err(ctx, NTC_ERR_FORMAT, "quality section " + std::to_string(b) + ": payload size or place");
+    }
+    ctx->qd_metas.assign(metas, metas + n_blocks);
+    ctx->qd_payload.resize(payload_bytes / 8);
+    if (payload_bytes) std::memcpy(ctx->qd_payload.data(), payload, payload_bytes);
+    ctx->qd_has_pending = true;
     return NTC_OK;
 }
 
@@ -2351,6 +2585,9 @@ struct NxHookFill {
         };
         ntc::g_nx_hooks.encode_exceptions = ntc_encode_exceptions;
         ntc::g_nx_hooks.decode_set_exceptions = ntc_decode_set_exceptions;
+        ntc::g_q_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "qualities", mode); };
+        ntc::g_q_hooks.encode_qualities = ntc_encode_qualities;
+        ntc::g_q_hooks.decode_set_qualities = ntc_decode_set_qualities;
     }
 } g_nx_hook_fill;
 }  // namespace

@@ -257,6 +257,59 @@ struct NxPatchArgs {
 };
 void launch_nx_patch(const NxPatchArgs &a, hipStream_t s);
 
+// Quality scores (quality.hip, quality_core.h).  Encode side, after launch_fastq_parse over
+// the same text: quals = the quality bytes at the reads' base offsets (room for the bases +
+// 64), pres: 4 words per block, blocks: n_blocks + 1 entries (the last holds the totals),
+// payload: q_payload_words_max(total bases, n_blocks) words.  status: a word of the
+// quality pass's own (preset here), read << 8 | NTC_ERR_FORMAT for the first bad read;
+// box[6] = that status, box[7] = payload words (the context's host mailbox).
+struct QBlock {
+    uint64_t n_quals, q_off, word_off, n_words, span_off;
+    uint64_t p0, p1;  // presence map, bits 0..127
+    uint32_t n_syms, w;
+    uint8_t alphabet[96];
+};
+struct QEncArgs {
+    const uint8_t *raw;
+    uint64_t n_raw;
+    const uint32_t *nl;
+    const uint64_t *n_nl_p;
+    const uint64_t *offs;  // [n_reads + 1]
+    uint64_t n_reads, n_blocks;
+    uint32_t block_reads, mode;
+    uint8_t *quals;
+    uint32_t *pres;
+    QBlock *blocks;
+    uint64_t *payload;
+    unsigned long long *status;
+    uint64_t *box;
+};
+uint64_t q_payload_words_max(uint64_t total, uint64_t n_blocks);
+void launch_quality_pack(const QEncArgs &a, uint64_t total, hipStream_t s);
+// Decode side: block b covers reads [r0, r1) of the decoded batch; its codes become bytes
+// at those reads' offsets in quals.  A code >= n_syms, or a block whose n_quals is not the
+// bases of its reads, sets status (the decode call's) to r0 << 8 | NTC_ERR_FORMAT.
+struct QDecBlock {
+    uint64_t r0, r1, n_quals, word_off;
+    uint32_t w, n_syms;
+    uint8_t alphabet[96];
+};
+struct QDecArgs {
+    const QDecBlock *blocks;
+    uint64_t n_blocks, tiles;  // tiles: quality_unpack_tiles(the largest n_quals)
+    const uint64_t *payload;
+    const uint64_t *offs;      // [n_reads + 1]
+    uint64_t n_reads;
+    uint8_t *quals;
+    unsigned long long *status;
+};
+uint64_t quality_unpack_tiles(uint64_t max_quals);
+void launch_quality_unpack(const QDecArgs &a, hipStream_t s);
+// launch_fasta's FASTQ twin: "@seq.{first_id + r}\n{read r}\n+\n{qualities r}\n"
+void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t n,
+                       uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,
+                       uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s);
+
 void launch_encode(const EncodeArgs &a, hipStream_t s);
 void launch_encode4(const Enc4Args &a, uint64_t total, uint32_t ms_blocks, hipStream_t s,
                     hipEvent_t ev_ms_begin, hipEvent_t ev_ms_end);

@@ -92,6 +92,7 @@ struct ntc_fastx;
 struct ntc_block_meta;
 struct ntc_ctx;
 struct ntc_nx_run;
+struct ntc_qual_meta;
 namespace ntc {
 // a plain FASTQ that ntc_fastx_open mapped: its bytes (null for any other input), and
 // moving the mapped parser to byte pos (a record start) -- pipeline.cpp's GPU-parse reader
@@ -128,6 +129,16 @@ struct NxHooks {
     int (*decode_set_exceptions)(::ntc_ctx *ctx, const ::ntc_nx_run *runs, uint64_t n_runs, uint32_t sub);
 };
 extern NxHooks g_nx_hooks;
+// The same for quality scores: with the table null, ntc_encode_file_ex / ntc_decode_file_ex
+// answer NTC_ERR_UNSUPPORTED to a quality mode other than drop or to a quality file.
+struct QHooks {
+    int (*set_mode)(::ntc_ctx *ctx, int mode);  // ctx option "qualities"
+    int (*encode_qualities)(::ntc_ctx *ctx, ::ntc_qual_meta *metas, uint64_t meta_cap, uint8_t *payload,
+                            uint64_t payload_cap, uint64_t *n_blocks, uint64_t *payload_bytes);
+    int (*decode_set_qualities)(::ntc_ctx *ctx, const ::ntc_qual_meta *metas, uint64_t n_blocks, const uint8_t *payload,
+                                uint64_t payload_bytes);
+};
+extern QHooks g_q_hooks;
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

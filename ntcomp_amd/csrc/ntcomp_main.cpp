@@ -8,9 +8,10 @@
 //                [-l LIST] [--builder auto|host|gpu] [--device N] [--index-format own|sbwt-rs] FILES...
 //   ntcomp encode -i P [--gpus N | --devices 0,0,..] [--threads T] [--blocks-per-batch B]
 //                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
-//                 [--non-acgt error|mask|keep] [--exceptions PATH] FILE > encoded.dat
+//                 [--non-acgt error|mask|keep] [--exceptions PATH]
+//                 [--qualities drop|keep|bin8] [--quality-file PATH] FILE > encoded.dat
 //   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
-//                 [--exceptions PATH] FILE > out.fasta
+//                 [--exceptions PATH] [--quality-file PATH] FILE > out.fasta (FASTQ with --quality-file)
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -69,7 +70,8 @@ bool takes_value(const std::string &o) {
     static const char *v[] = {"-o", "--output-prefix", "-k", "-p", "--prefix-precalc", "-t", "--threads", "-m",
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
-                              "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions"};
+                              "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
+                              "--qualities", "--quality-file"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -232,6 +234,13 @@ int cmd_encode(const Args &a) {
     if (policy == NTC_NX_KEEP && nx_path.empty()) bad_args("encode: --non-acgt keep requires --exceptions PATH");
     if (policy != NTC_NX_KEEP && a.flag("--exceptions"))
         bad_args("encode: --exceptions is only written under --non-acgt keep");
+    // quality scores: drop (default), keep, or bin8, with the packed sections in a side file
+    const std::string q_name = a.get("--qualities", nullptr, "drop"), q_path = a.get("--quality-file", nullptr, "");
+    const int q_mode = q_name == "drop" ? 0 : q_name == "keep" ? 1 : q_name == "bin8" ? 2 : -1;
+    if (q_mode < 0) bad_args("encode: --qualities: drop, keep or bin8");
+    if (q_mode > 0 && q_path.empty()) bad_args("encode: --qualities " + q_name + " requires --quality-file PATH");
+    if (q_mode == 0 && a.flag("--quality-file"))
+        bad_args("encode: --quality-file is only written under --qualities keep or bin8");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
@@ -255,11 +264,24 @@ int cmd_encode(const Args &a) {
     int nx_fd = -1;
     if (policy == NTC_NX_KEEP && (nx_fd = ::open(nx_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
         die("encode: cannot write " + nx_path);
+    ntc_q_stats qs{};
+    int q_fd = -1;
+    if (q_mode > 0 && (q_fd = ::open(q_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
+        die("encode: cannot write " + q_path);
+    const ntc_file_opts fo{policy, nx_fd, q_mode, q_fd, nullptr, nullptr};
     std::fflush(stdout);
-    const int rc = policy == NTC_NX_ERROR
+    const int rc = q_mode > 0 ? ntc_encode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st, &nx, &qs)
+                   : policy == NTC_NX_ERROR
                        ? ntc_encode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
                        : ntc_encode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, policy, nx_fd, &o, &st, &nx);
     if (nx_fd >= 0 && ::close(nx_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + nx_path);
+    if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
+    char qjson[256] = "";  // the quality file's figures, when one was written
+    if (q_mode > 0)
+        std::snprintf(qjson, sizeof(qjson), "\"qualities\": \"%s\", \"q_sections\": %llu, \"q_quals\": %llu, "
+                                            "\"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
+                      q_name.c_str(), (unsigned long long)qs.sections, (unsigned long long)qs.quals,
+                      (unsigned long long)qs.packed_bytes, (unsigned long long)qs.deflated_bytes);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -278,12 +300,12 @@ int cmd_encode(const Args &a) {
                      "\"threads\": %d, \"reads\": %llu, \"blocks\": %llu, \"dropped_blocks\": %llu, "
                      "\"pipeline_wall_s\": %.3f, \"deflate\": \"%s\", \"gpu_parsed_batches\": %d, \"non_acgt\": \"%s\", "
                      "\"nx_runs\": %llu, \"nx_bases\": %llu, \"nx_reads\": %llu, \"nx_runs_in_dropped_blocks\": %llu, "
-                     "\"process_s\": %.3f}\n",
+                     "%s\"process_s\": %.3f}\n",
                      t_load, t_gpu - t_load, st.parse_s, st.gpu_s, st.deflate_s, st.write_s, ctxs.size(), st.threads,
                      (unsigned long long)st.reads, (unsigned long long)st.blocks,
                      (unsigned long long)st.dropped_blocks, st.wall_s, engine.c_str(), st.gpu_parsed, nx_name.c_str(),
                      (unsigned long long)nx.runs, (unsigned long long)nx.bases, (unsigned long long)nx.reads,
-                     (unsigned long long)nx.runs_in_dropped_blocks, since(t0));
+                     (unsigned long long)nx.runs_in_dropped_blocks, qjson, since(t0));
     return 0;
 }
 
@@ -309,8 +331,11 @@ int cmd_decode(const Args &a) {
     o.blocks_per_batch = std::atoi(a.get("--blocks-per-batch", nullptr, "2").c_str());
     ntc_pipeline_stats st{};
     const std::string nx_path = a.get("--exceptions", nullptr, "");  // the side file of encode --non-acgt keep
+    const std::string q_path = a.get("--quality-file", nullptr, "");  // ... of encode --qualities keep: FASTQ out
+    const ntc_file_opts fo{0, -1, 0, -1, nx_path.empty() ? nullptr : nx_path.c_str(), q_path.c_str()};
     std::fflush(stdout);
-    const int rc = nx_path.empty()
+    const int rc = !q_path.empty() ? ntc_decode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st)
+                   : nx_path.empty()
                        ? ntc_decode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
                        : ntc_decode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), nx_path.c_str(), 1, &o, &st);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
@@ -428,13 +453,19 @@ void usage(FILE *f) {
     std::fprintf(f,
                  "Sequencing data compression with SBWT + k-bounded matching statistics; encode/decode hot path on "
                  "MI355X.\n\nusage: ntcomp build -o PREFIX [-k K] [-m MEM_GB] [--temp-dir DIR] FILES...\n"
-                 "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH] FILE > encoded.dat\n"
-                 "       ntcomp decode -i PREFIX [--exceptions PATH] FILE > out.fasta\n\n"
+                 "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH]\n"
+                 "                     [--qualities drop|keep|bin8] [--quality-file PATH] FILE > encoded.dat\n"
+                 "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] FILE > out.fasta\n\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
                  "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
                  "                     the replaced symbols to the --exceptions file (lossless)\n"
                  "  --exceptions PATH  encode --non-acgt keep: the side file to write; decode: the side file whose\n"
-                 "                     symbols are put back\n");
+                 "                     symbols are put back\n"
+                 "  --qualities MODE   encode: FASTQ quality scores: drop (default), keep (lossless), or bin8 (Phred\n"
+                 "                     scores binned to 8 levels, lossy); keep and bin8 write them, packed on the GPU,\n"
+                 "                     to the --quality-file\n"
+                 "  --quality-file PATH  encode --qualities keep|bin8: the side file to write; decode: the side file\n"
+                 "                     whose qualities are printed: the output is then FASTQ\n");
 }
 
 }  // namespace

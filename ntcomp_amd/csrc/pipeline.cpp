@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -48,6 +49,7 @@
 
 namespace ntc {
 NxHooks g_nx_hooks = {nullptr, nullptr, nullptr, nullptr};  // capi.cpp fills it at load
+QHooks g_q_hooks = {nullptr, nullptr, nullptr};
 }
 
 namespace {
@@ -207,6 +209,10 @@ struct BlockOut {  // a deflated block (its four streams' parts), or a dropped o
     int left = 0;  // parts not yet deflated
     uint64_t n_reads = 0;            // the block's reads
     std::vector<ntc_nx_run> nx;      // its exception runs (policy keep), read relative to the block
+    bool has_q = false;              // quality mode keep / bin8: its section, deflated with the streams
+    ntc_qual_meta qmeta{};
+    uint8_t *qsec = nullptr;
+    uint64_t qlen = 0;
 };
 
 struct Shared {
@@ -232,11 +238,17 @@ extern "C" {
 
 // policy / nx_fd / nx: ntc_encode_file_nx; ntc_encode_file passes policy -1 = the contexts as
 // they are, no side file
+// q_mode / q_fd / qs: ntc_encode_file_ex's quality side file (q_mode 0: none)
 static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
-                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx) {
+                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx,
+                            int q_mode = 0, int q_fd = -1, ntc_q_stats *qs = nullptr) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
+    if (q_mode < 0 || q_mode > 2 || (q_mode ? q_fd < 0 : q_fd != -1)) return NTC_ERR_INVALID_ARG;
+    const ntc::QHooks &qh = ntc::g_q_hooks;
+    if (q_mode && (!qh.set_mode || !qh.encode_qualities)) return NTC_ERR_UNSUPPORTED;
+    ntc_q_stats QS{};
     const bool keep = policy == NTC_NX_KEEP;
     ntc_nx_stats NX{};
     uint32_t nx_sub = 0;
@@ -264,6 +276,19 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 for (int i = 0; i < n; i++) ntc::g_nx_hooks.set_policy(ctxs[i], 0);
         }
     } policy_reset{ctxs, policy > 0 ? n_ctx : 0};
+    if (q_mode)
+        for (int i = 0; i < n_ctx; i++)
+            if (int r = qh.set_mode(ctxs[i], q_mode)) {
+                for (int j = 0; j < i; j++) qh.set_mode(ctxs[j], 0);
+                return r;
+            }
+    struct ModeReset {  // ... and with qualities dropped
+        ntc_ctx *const *ctxs;
+        int n;
+        ~ModeReset() {
+            for (int i = 0; i < n; i++) ntc::g_q_hooks.set_mode(ctxs[i], 0);
+        }
+    } mode_reset{ctxs, q_mode ? n_ctx : 0};
     ntc_pipeline_opts o{};
     if (opts) o = *opts;
     const int T = o.threads > 0 ? o.threads : ntc_host_threads();
@@ -319,7 +344,8 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         std::shared_ptr<uint8_t> payload;  // the GPU call's host payload (ntc_buffer_free)
         ntc_block_meta meta;
         uint64_t block;
-        int stream;
+        int stream;                        // 0..3, or 4 = the block's quality section
+        std::shared_ptr<uint8_t> qpayload = nullptr;  // the call's packed quality words
     };
     std::deque<Task> tasks;
     std::map<uint64_t, BlockOut> done;
@@ -351,6 +377,11 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     // start).  Streamed (a decoder's output): the text after the last cut, carry_n bytes at
     // carry_p in the previous batch's buffer, goes first into the next one.
     const bool streamed = !text && !o.host_parse && ntc::fastx_streamed_fastq(fx);
+    // qualities exist only where the GPU parses the text (DESIGN.md "Quality scores")
+    if (q_mode && o.host_parse)
+        sh.fail(NTC_ERR_UNSUPPORTED, "qualities: host_parse = 1 parses on the host, which drops the quality lines");
+    else if (q_mode && !text && !streamed)
+        sh.fail(NTC_ERR_UNSUPPORTED, "qualities: the input is not FASTQ (FASTA has no quality lines)");
     uint64_t text_pos = 0;
     const uint8_t *carry_p = nullptr;
     uint64_t carry_n = 0;
@@ -518,6 +549,12 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     sh.fail(NTC_ERR_IO, "FASTX input: malformed or unreadable");
                     break;
                 }
+                if (q_mode) {
+                    sh.fail(NTC_ERR_UNSUPPORTED, "qualities: a blank line, or records that are not four lines each: "
+                                                 "this batch needs the host parser, which drops the quality lines",
+                            (int64_t)next_read);
+                    break;
+                }
                 as_text = false;  // the host parser goes on from the first record not sent
                 if (streamed) {
                     ntc::fastx_stream_unread(fx, carry_p, carry_n);
@@ -645,7 +682,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 add_time(t_gpu, secs(tg, Clock::now()));
                 if (r) {
                     ntc_buffer_free(payload);
-                    if (b.is_text && r == NTC_ERR_FORMAT)  // as the host parser reports it
+                    if (b.is_text && r == NTC_ERR_FORMAT && !q_mode)  // as the host parser reports it
                         sh.fail(r, "FASTX input: malformed or unreadable");
                     else
                         sh.fail(r, std::string("encode: ") + ntc_last_error(ctxs[c]),
@@ -670,6 +707,25 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         return;
                     }
                 }
+                // ... and its quality sections (mode keep / bin8), one per block
+                std::vector<ntc_qual_meta> qmetas;
+                std::shared_ptr<uint8_t> qpl;
+                if (q_mode) {
+                    uint64_t qn = 0, qbytes = 0;
+                    int rq = qh.encode_qualities(ctxs[c], nullptr, 0, nullptr, 0, &qn, &qbytes);
+                    if (rq == NTC_ERR_CAPACITY && qn == nblk) {
+                        qmetas.resize(qn);
+                        qpl.reset((uint8_t *)std::malloc(qbytes ? qbytes : 1), std::free);
+                        rq = qpl ? qh.encode_qualities(ctxs[c], qmetas.data(), qn, qpl.get(), qbytes, &qn, &qbytes)
+                                 : NTC_ERR_CAPACITY;
+                    } else if (rq == NTC_OK || rq == NTC_ERR_CAPACITY) {
+                        rq = NTC_ERR_FORMAT;  // (never expected: a section per block)
+                    }
+                    if (rq) {
+                        sh.fail(rq, std::string("encode: qualities: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                }
                 etrace("gpu done, first block", b.first_block);
                 std::lock_guard<std::mutex> g(sh.mu);
                 S.gpu_done_s = secs(t0, Clock::now());
@@ -688,6 +744,12 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         bo.nx.back().read -= k * (uint64_t)BR;
                     }
                     bo.left = ok ? 4 : 1;
+                    if (q_mode && ok) {  // a dropped block takes its section with it
+                        bo.has_q = true;
+                        bo.qmeta = qmetas[k];
+                        bo.left++;
+                        tasks.push_back(Task{pl, metas[k], b.first_block + k, 4, qpl});
+                    }
                     int order[4] = {0, 1, 2, 3};
                     std::sort(order, order + 4, [&](int x, int y) {
                         return metas[k].stream[x].encoded_size > metas[k].stream[y].encoded_size;
@@ -717,7 +779,18 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 uint64_t len = 0;
                 const auto td = Clock::now();
                 const int status = task.meta.status;
-                if (status == NTC_OK) {
+                if (status == NTC_OK && task.stream == 4) {
+                    ntc_qual_meta qm;
+                    {
+                        std::lock_guard<std::mutex> g(sh.mu);
+                        qm = done[task.block].qmeta;
+                    }
+                    const int r = ntc_q_deflate_section(&qm, task.qpayload.get() + qm.payload_off, engine, &data, &len);
+                    if (r) {
+                        sh.fail(r, "qualities: deflate failed");
+                        return;
+                    }
+                } else if (status == NTC_OK) {
                     const int r = ntc_deflate_stream(&task.meta, task.stream, task.payload.get(), engine, &data, &len);
                     if (r) {
                         sh.fail(r, "deflate failed");
@@ -728,11 +801,17 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     return;
                 }
                 task.payload.reset();
+                task.qpayload.reset();
                 add_time(t_deflate, secs(td, Clock::now()));
                 std::lock_guard<std::mutex> g(sh.mu);
                 BlockOut &bo = done[task.block];
-                bo.part[task.stream] = data;
-                bo.len[task.stream] = len;
+                if (task.stream == 4) {
+                    bo.qsec = data;
+                    bo.qlen = len;
+                } else {
+                    bo.part[task.stream] = data;
+                    bo.len[task.stream] = len;
+                }
                 if (--bo.left == 0) sh.cv.notify_all();
             }
         });
@@ -754,6 +833,18 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     // the side file: its header now, then a section per written block that has runs, `read`
     // counted over the reads of the blocks written so far (what decode will print as seq.N - 1)
     if (keep && ntc_nx_write(nx_fd, nullptr, 0, nx_sub, 1)) sh.fail(NTC_ERR_IO, "exceptions: write failed");
+    // the quality file: its header, then the section of every block written, in file order
+    auto write_q = [&](const uint8_t *p, uint64_t n) -> bool {
+        while (n) {
+            const ssize_t w = ::write(q_fd, p, n);
+            if (w < 0 && errno == EINTR) continue;
+            if (w <= 0) return false;
+            p += w;
+            n -= (uint64_t)w;
+        }
+        return true;
+    };
+    if (q_mode && ntc_q_write_header(q_fd, q_mode)) sh.fail(NTC_ERR_IO, "qualities: write failed");
     uint64_t reads_written = 0;
     for (uint64_t blk = 0;; blk++) {
         BlockOut out;
@@ -789,11 +880,19 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 NX.runs += out.nx.size();
             }
             reads_written += out.n_reads;
+            if (out.has_q) {
+                if (!write_q(out.qsec, out.qlen)) sh.fail(NTC_ERR_IO, "qualities: write failed");
+                QS.sections++;
+                QS.quals += out.qmeta.n_quals;
+                QS.packed_bytes += out.qmeta.payload_bytes;
+                QS.deflated_bytes += out.qlen - 24 - out.qmeta.n_syms;
+            }
         } else {
             S.dropped_blocks++;
             NX.runs_in_dropped_blocks += out.nx.size();
         }
         for (int q = 0; q < 4; q++) ntc_buffer_free(out.part[q]);
+        ntc_buffer_free(out.qsec);
         add_time(t_write, secs(tw, Clock::now()));
         etrace("written block", blk);
     }
@@ -809,8 +908,10 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     for (auto &t : gpus) t.join();
     for (auto &t : pool) t.join();
     etrace("threads joined", 0);
-    for (auto &kv : done)
+    for (auto &kv : done) {
         for (int q = 0; q < 4; q++) ntc_buffer_free(kv.second.part[q]);
+        ntc_buffer_free(kv.second.qsec);
+    }
     for (auto &b : ring) {
         pinned_free(b.bases);
         pinned_free(b.offs);
@@ -832,6 +933,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     std::snprintf(S.error, sizeof(S.error), "%s", result == NTC_OK ? "" : sh.msg.c_str());
     if (stats) *stats = S;
     if (nx) *nx = NX;
+    if (qs) *qs = QS;
     return result;
 }
 
@@ -844,6 +946,13 @@ int ntc_encode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int
                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx) {
     if (policy < 0) return NTC_ERR_INVALID_ARG;
     return encode_file_impl(ctxs, n_ctx, in_path, out_fd, policy, nx_fd, opts, stats, nx);
+}
+
+int ntc_encode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts *fo,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q) {
+    if (!fo || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
+    return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
+                            fo->q_fd, q);
 }
 
 }  // extern "C"
@@ -933,8 +1042,9 @@ uint64_t digits_total(uint64_t first, uint64_t n) {  // decimal digits of first 
 extern "C" {
 
 // nx_path: ntc_decode_file_nx's side file (null: none)
+// q_path: ntc_decode_file_ex's quality file (null: none; the output is then FASTA)
 static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
-                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
+                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, const char *q_path = nullptr) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
@@ -957,6 +1067,40 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             return r;
         }
     }
+    // the quality sections, read once; section i belongs to block i of the file
+    struct QFile {
+        ntc_qual_meta *metas = nullptr;
+        uint64_t n = 0, bytes = 0;
+        uint8_t *payload = nullptr;
+        int mode = 0;
+        ~QFile() {
+            ntc_buffer_free(metas);
+            ntc_buffer_free(payload);
+        }
+    } qf;
+    if (q_path) {
+        if (!ntc::g_q_hooks.decode_set_qualities) return NTC_ERR_UNSUPPORTED;
+        if (const int r = ntc_q_read(q_path, &qf.mode, &qf.metas, &qf.n, &qf.payload, &qf.bytes)) {
+            if (stats) {
+                std::memset(stats, 0, sizeof(*stats));
+                stats->bad_read = -1;
+                std::snprintf(stats->error, sizeof(stats->error), "qualities: %s",
+                              r == NTC_ERR_IO ? "cannot read the side file" : "malformed side file");
+            }
+            return r;
+        }
+    }
+    // hands ctx the sections of blocks [first, first + n), their words from offset 0
+    auto put_quals = [&](ntc_ctx *ctx, uint64_t first, uint64_t n, std::vector<ntc_qual_meta> &tmp) -> int {
+        if (!q_path || n == 0) return NTC_OK;
+        if (first + n > qf.n) return NTC_ERR_FORMAT;
+        tmp.assign(qf.metas + first, qf.metas + first + n);
+        const uint64_t base = tmp[0].payload_off;
+        for (auto &m : tmp) m.payload_off -= base;
+        const uint64_t bytes = tmp.back().payload_off + tmp.back().payload_bytes;
+        return ntc::g_q_hooks.decode_set_qualities(ctx, tmp.data(), n, qf.payload + base, bytes);
+    };
+    const uint64_t q_per_base = q_path ? 1 : 0, q_per_read = q_path ? 3 : 0;  // FASTQ: "+\n", qualities, "\n" more
     // hands ctx the runs of reads [first, first + n) (file numbering), read relative to first
     auto put_runs = [&](ntc_ctx *ctx, uint64_t first, uint64_t n, std::vector<ntc_nx_run> &tmp) -> int {
         if (!nxf.n) return NTC_OK;
@@ -1151,6 +1295,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 }
             }
             std::vector<ntc_nx_run> nx_tmp;  // a batch's exception runs, renumbered from its first read
+            std::vector<ntc_qual_meta> q_tmp;  // ... and its quality sections
             for (uint64_t b = (uint64_t)c;; b += (uint64_t)n_ctx) {
                 DSlot *slp;
                 if (gpu_unpack) {
@@ -1190,7 +1335,8 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         sh.cv.wait(g, [&] { return sh.error != NTC_OK || sl.ready; });
                         if (sh.error != NTC_OK) return;
                     }
-                    const uint64_t need = sl.n_bases + 7 * sl.n_reads + digits_total(sl.first_id, sl.n_reads) + 64;
+                    const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
+                                          digits_total(sl.first_id, sl.n_reads) + 64;
                     const auto tf = Clock::now();
                     if (!ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
                         sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
@@ -1199,6 +1345,12 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     uint64_t len = 0;
                     if (const int rx = put_runs(ctxs[c], sl.first_id - 1, sl.n_reads, nx_tmp)) {
                         sh.fail(rx, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                    if (const int rx = put_quals(ctxs[c], sl.first_block, nb, q_tmp)) {
+                        sh.fail(rx, rx == NTC_ERR_FORMAT ? "qualities: fewer sections than blocks, or a section that "
+                                                           "does not fit its block"
+                                                         : std::string("decode: ") + ntc_last_error(ctxs[c]));
                         return;
                     }
                     const int rf = ntc_decode_fasta_unpacked(ctxs[c], sl.first_id, sl.text, sl.cap_text, &len);
@@ -1226,7 +1378,8 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 }
                 DSlot &sl = *slp;
                 const uint64_t nrec = sl.n_recs;
-                const uint64_t need = sl.n_bases + 7 * sl.n_reads + digits_total(sl.first_id, sl.n_reads) + 64;
+                const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
+                                      digits_total(sl.first_id, sl.n_reads) + 64;
                 const auto tg = Clock::now();
                 if (!ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
                     sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
@@ -1235,6 +1388,13 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 uint64_t len = 0;
                 if (const int rx = put_runs(ctxs[c], sl.first_id - 1, sl.n_reads, nx_tmp)) {
                     sh.fail(rx, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                    return;
+                }
+                if (const int rx = put_quals(ctxs[c], sl.first_block,
+                                             sl.bad_block >= 0 ? (uint64_t)sl.bad_block : sl.n_blocks, q_tmp)) {
+                    sh.fail(rx, rx == NTC_ERR_FORMAT ? "qualities: fewer sections than blocks, or a section that "
+                                                       "does not fit its block"
+                                                     : std::string("decode: ") + ntc_last_error(ctxs[c]));
                     return;
                 }
                 const int rc = ntc_decode_fasta(ctxs[c], sl.recs, nrec, sl.n_reads, sl.n_bases, sl.first_id, sl.text,
@@ -1454,6 +1614,12 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         result = NTC_ERR_FORMAT;
         sh.msg = "exceptions: a run past the last read (the side file belongs to another encoding)";
     }
+    // an input that ended cleanly used exactly all sections
+    const bool clean_end = blocks.empty() ? fsize <= 32 : blocks.back().a + blocks.back().len == fsize;
+    if (result == NTC_OK && stop_batch < 0 && clean_end && q_path && qf.n != blocks.size()) {
+        result = NTC_ERR_FORMAT;
+        sh.msg = "qualities: more sections than blocks (the side file belongs to another encoding)";
+    }
     S.dropped_blocks = blocks.size() - S.blocks;  // after a damaged block (or none)
     S.alloc_s += t_pin.load();
     S.parse_s = t_unzip.load();
@@ -1479,6 +1645,12 @@ int ntc_decode_file(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int ou
 int ntc_decode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
     return decode_file_impl(ctxs, n_ctx, in_path, nx_path, out_fd, opts, stats);
+}
+
+int ntc_decode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts *fo,
+                       const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
+    if (!fo) return NTC_ERR_INVALID_ARG;
+    return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path);
 }
 
 }  // extern "C"
