@@ -258,6 +258,73 @@ int ntc_q_write_section(int fd, const ntc_qual_meta *meta, const uint8_t *words,
 int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_blocks, uint8_t **payload,
                uint64_t *payload_bytes);
 
+/* ---- FASTQ read names ----------------------------------------------------------------------- */
+/* ntc_ctx_set_option(ctx, "names", mode) says what ntc_encode_pack_fastq does with the header
+ * lines of its text:
+ *   0  drop (default): only their '@' is looked at, as ever.
+ *   1  keep (lossless): every block of block_reads reads also yields a name section.
+ *   2  id (lossy): each name is first cut before its first space or tab, then as 1.
+ * A read's name is its header line without the '@' and without one trailing '\r'.  It may be
+ * empty and may hold any byte but '\n'; after the cut it is at most NTC_NAME_MAX bytes, else
+ * the call returns NTC_ERR_FORMAT with the lowest such read as bad_read.  The calls that take
+ * bases without header lines (ntc_encode_batch, ntc_encode_batch_device,
+ * ntc_encode_pack_batch) return NTC_ERR_UNSUPPORTED under 1 and 2.
+ *
+ * A section, the canonical front- and back-coded form of one block's names.  The chain
+ * restarts every NTC_NAME_GROUP reads of the block.  With P the name of read i - 1 and N that
+ * of read i: pre_i = suf_i = 0 when i % NTC_NAME_GROUP == 0, else pre_i = min(255, lcp(P, N))
+ * and suf_i = min(255, longest common suffix, |P| - pre_i, |N| - pre_i); mid_i = N[pre_i :
+ * |N| - suf_i].  Payload: len[n] as little-endian u16, pre[n] as u8, suf[n] as u8, the mids
+ * in read order, zero bytes up to a multiple of 8.  Decoding: N = P[:pre] + mid + P[|P| -
+ * suf:], valid iff pre + suf <= min(len_i, len_{i-1}).  The coding runs on the GPU.          */
+#define NTC_NAME_MAX 4095
+#define NTC_NAME_GROUP 64
+typedef struct ntc_name_meta {
+    uint64_t n_reads;       /* reads of the block                                          */
+    uint64_t name_bytes;    /* sum of len                                                  */
+    uint64_t mid_bytes;     /* sum of the mids                                             */
+    uint64_t payload_off;   /* byte offset of the section in the payload buffer            */
+    uint64_t payload_bytes; /* 8 * ceil((4 n_reads + mid_bytes) / 8)                       */
+} ntc_name_meta;            /* 40 bytes */
+/* The sections of the last ntc_encode_pack_fastq call on this context under mode 1 or 2, one
+ * per block (none under mode 0, or when that call failed); capacities as for
+ * ntc_encode_qualities.                                                                     */
+int ntc_encode_names(ntc_ctx *ctx, ntc_name_meta *metas, uint64_t meta_cap, uint8_t *payload, uint64_t payload_cap,
+                     uint64_t *n_blocks, uint64_t *payload_bytes);
+/* Sections (copied) for the next ntc_decode_fasta or ntc_decode_fasta_unpacked call on this
+ * context: section i covers the next metas[i].n_reads reads of that call, which then writes
+ * ">{name}\n{read}\n" (or "@{name}\n{read}\n+\n{qualities}\n" when quality sections are
+ * pending too) instead of seq.N, and returns NTC_ERR_FORMAT (no text) when the sections do
+ * not cover exactly its reads or a section breaks a rule above (a len past NTC_NAME_MAX, pre
+ * + suf past either neighbour, pre or suf on a restart read, mids or names that do not sum to
+ * the meta).  Checked here, NTC_ERR_FORMAT: payload_bytes of every section against n_reads
+ * and mid_bytes, and that it lies 8-byte aligned inside the payload.  The sections are
+ * dropped by the call that used them, whatever it returned (a call that only reports sizes
+ * keeps them); ntc_decode_batch and ntc_decode_batch_device ignore them.  n_blocks = 0 drops
+ * pending sections.                                                                         */
+int ntc_decode_set_names(ntc_ctx *ctx, const ntc_name_meta *metas, uint64_t n_blocks, const uint8_t *payload,
+                         uint64_t payload_bytes);
+
+/* ---- name side file ("NTCN", version 1) ----------------------------------------------------- */
+/* The name sections of an encoded.dat, beside it.  Everything little-endian:
+ *   header, 32 bytes: "NTCN", u32 version = 1, u8 mode (1 keep, 2 id), 23 zero bytes
+ *   sections until the end of the file, section i for block i of encoded.dat:
+ *     32 bytes: u64 n_reads, u64 name_bytes, u64 mid_bytes, u32 gz_bytes, u32 0
+ *     one gzip member of gz_bytes bytes that inflates to exactly the section's payload_bytes
+ * The functions mirror the quality file's.  ntc_n_deflate_section / ntc_n_write_section:
+ * NTC_ERR_INVALID_ARG for a meta that is not canonical (payload_bytes, mid_bytes against
+ * name_bytes, name_bytes against n_reads).  ntc_n_read validates everything: NTC_ERR_FORMAT
+ * for a bad magic, version or mode, truncation, a non-zero pad word, a member that does not
+ * inflate to exactly payload_bytes, a len past NTC_NAME_MAX, pre + suf past either
+ * neighbour, a restart read with pre or suf, mids that do not sum to mid_bytes, names that
+ * do not sum to name_bytes, non-zero padding bytes.                                         */
+int ntc_n_write_header(int fd, int mode);
+int ntc_n_deflate_section(const ntc_name_meta *meta, const uint8_t *payload, int engine, uint8_t **out,
+                          uint64_t *out_len);
+int ntc_n_write_section(int fd, const ntc_name_meta *meta, const uint8_t *payload, int engine);
+int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_blocks, uint8_t **payload,
+               uint64_t *payload_bytes);
+
 #ifdef __cplusplus
 }
 #endif

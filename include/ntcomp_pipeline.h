@@ -132,6 +132,47 @@ int ntc_encode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int
 int ntc_decode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts *fo,
                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats);
 
+/* ---- all three side files: exceptions, quality scores and read names ------------------------ */
+/* ntc_encode_file_ex2 / ntc_decode_file_ex2 are ntc_encode_file_ex / ntc_decode_file_ex with
+ * the name file beside the other two.  ntc_file_opts2 starts with its own size, so that the
+ * next side file needs no new entry point: struct_bytes must be at least
+ * sizeof(ntc_file_opts2) as declared here, else NTC_ERR_INVALID_ARG.
+ * Encode: n_mode 0 (drop): no name file, n_fd must be -1.  n_mode 1 (keep) or 2 (id,
+ * ntcomp_codec.h): every block written to encoded.dat gets its name section in the "NTCN"
+ * file at n_fd (>= 0, not closed), front-coded on the GPU and deflated by the pipeline's pool
+ * with the block's streams; a block the pipeline drops takes its section with it.
+ * encoded.dat is byte for byte that of a run without names, and the side file does not depend
+ * on the number of contexts or on whether the same text came plain or compressed.  Names
+ * exist only where the GPU parses the FASTQ text: host_parse = 1, an input that is not FASTQ,
+ * and a batch that falls back to the host parser (a blank line) are NTC_ERR_UNSUPPORTED under
+ * modes 1 and 2, with the case in stats->error.  The contexts' "names" option is set for the
+ * call and left at 0.  n (may be NULL): sections and names written, their bytes.
+ * Decode: n_path (NULL: none) = the "NTCN" file, read once (ntc_n_read); section i belongs to
+ * block i of encoded.dat and the output carries the names, ">{name}\n{read}\n" or, with
+ * q_path, "@{name}\n{read}\n+\n{qualities}\n".  An input that ended cleanly must have used
+ * exactly all sections, else NTC_ERR_FORMAT.  A "+name" third line is not kept: it comes back
+ * as a bare "+".                                                                             */
+typedef struct ntc_file_opts2 {
+    uint32_t struct_bytes; /* sizeof(ntc_file_opts2)                           */
+    int32_t nx_policy;     /* NTC_NX_*                                         */
+    int32_t nx_fd;         /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;        /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;          /* encode: quality file, -1 = none                  */
+    const char *nx_path;   /* decode: exceptions file, NULL = none             */
+    const char *q_path;    /* decode: quality file, NULL = none                */
+    int32_t n_mode;        /* 0 drop, 1 keep, 2 id                             */
+    int32_t n_fd;          /* encode: name file, -1 = none                     */
+    const char *n_path;    /* decode: name file, NULL = none                   */
+} ntc_file_opts2;
+typedef struct ntc_n_stats {
+    uint64_t sections, names, name_bytes, payload_bytes, deflated_bytes;
+} ntc_n_stats;
+int ntc_encode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts2 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n);
+int ntc_decode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts2 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ EXPORTED = [
     "ntc_decode_file_nx",
     "ntc_encode_qualities", "ntc_decode_set_qualities", "ntc_q_write_header", "ntc_q_deflate_section",
     "ntc_q_write_section", "ntc_q_read", "ntc_encode_file_ex", "ntc_decode_file_ex",
+    "ntc_encode_names", "ntc_decode_set_names", "ntc_n_write_header", "ntc_n_deflate_section",
+    "ntc_n_write_section", "ntc_n_read", "ntc_encode_file_ex2", "ntc_decode_file_ex2",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -66,6 +68,15 @@ QUALITIES = {"drop": 0, "keep": 1, "bin8": 2}
 
 def _quality_code(qualities):
     return QUALITIES[qualities] if isinstance(qualities, str) else int(qualities)
+
+
+# name modes (ctx option "names", include/ntcomp_codec.h)
+NAMES = {"drop": 0, "keep": 1, "id": 2}
+NAME_MAX, NAME_GROUP = 4095, 64
+
+
+def _names_code(names):
+    return NAMES[names] if isinstance(names, str) else int(names)
 
 
 def _policy_code(non_acgt):
@@ -101,6 +112,11 @@ class QualMeta(ctypes.Structure):
                 ("reserved", ctypes.c_uint8 * 6), ("alphabet", ctypes.c_uint8 * 96)]
 
 
+class NameMeta(ctypes.Structure):
+    """ntc_name_meta (include/ntcomp_codec.h): the name section of one block."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_reads", "name_bytes", "mid_bytes", "payload_off", "payload_bytes")]
+
+
 DEFLATE_ENGINES = {"zlib": 0, "libdeflate": 1, "adaptive": 2}  # NTC_DEFLATE_* (include/ntcomp_codec.h)
 
 
@@ -132,6 +148,19 @@ class FileOpts(ctypes.Structure):
 class QStats(ctypes.Structure):
     """ntc_q_stats (include/ntcomp_pipeline.h)."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("sections", "quals", "packed_bytes", "deflated_bytes")]
+
+
+class FileOpts2(ctypes.Structure):
+    """ntc_file_opts2 (include/ntcomp_pipeline.h): all three side files of a file-to-file call."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nx_policy", ctypes.c_int32), ("nx_fd", ctypes.c_int32),
+                ("q_mode", ctypes.c_int32), ("q_fd", ctypes.c_int32), ("nx_path", ctypes.c_char_p),
+                ("q_path", ctypes.c_char_p), ("n_mode", ctypes.c_int32), ("n_fd", ctypes.c_int32),
+                ("n_path", ctypes.c_char_p)]
+
+
+class NStats(ctypes.Structure):
+    """ntc_n_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("sections", "names", "name_bytes", "payload_bytes", "deflated_bytes")]
 
 
 class BuildOpts(ctypes.Structure):
@@ -280,6 +309,18 @@ def lib():
         "ntc_q_write_section": (I, [I, P, P, I]),
         "ntc_q_read": (I, [ctypes.c_char_p, ctypes.POINTER(I), ctypes.POINTER(P), ctypes.POINTER(u64),
                            ctypes.POINTER(P), ctypes.POINTER(u64)]),
+        "ntc_encode_names": (I, [P, P, u64, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "ntc_decode_set_names": (I, [P, P, u64, P, u64]),
+        "ntc_n_write_header": (I, [I, I]),
+        "ntc_n_deflate_section": (I, [P, P, I, ctypes.POINTER(P), ctypes.POINTER(u64)]),
+        "ntc_n_write_section": (I, [I, P, P, I]),
+        "ntc_n_read": (I, [ctypes.c_char_p, ctypes.POINTER(I), ctypes.POINTER(P), ctypes.POINTER(u64),
+                           ctypes.POINTER(P), ctypes.POINTER(u64)]),
+        "ntc_encode_file_ex2": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts2), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
+                                    ctypes.POINTER(NStats)]),
+        "ntc_decode_file_ex2": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts2), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats)]),
         "ntc_nx_write": (I, [I, P, u64, u32, I]),
         "ntc_nx_read": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "ntc_encode_file_nx": (I, [P, I, ctypes.c_char_p, I, I, I, ctypes.POINTER(PipelineOpts),
@@ -547,6 +588,32 @@ class GpuContext:
         self._check(self.L.ntc_decode_set_qualities(self.h, arr, len(metas), _p(buf), len(payload)),
                     "ntc_decode_set_qualities")
 
+    # ---- read names ------------------------------------------------------------------
+    def _nmode(self, names):
+        return GpuContext._Option(self, "names", None if names is None else _names_code(names))
+
+    def names(self):
+        """The name sections of the last encode_pack_fastq call under "keep" or "id"
+        (ntc_encode_names) -> (list of NameMeta, their payload as bytes)."""
+        nb, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.L.ntc_encode_names(self.h, None, 0, None, 0, ctypes.byref(nb), ctypes.byref(nbytes))
+        if rc not in (0, 5):
+            self._check(rc, "ntc_encode_names")
+        metas = (NameMeta * max(nb.value, 1))()
+        pay = np.zeros(max(nbytes.value, 8), dtype=np.uint8)
+        if nb.value:
+            self._check(self.L.ntc_encode_names(self.h, metas, nb.value, _p(pay), len(pay), ctypes.byref(nb),
+                                                ctypes.byref(nbytes)), "ntc_encode_names")
+        return list(metas)[:nb.value], pay[:nbytes.value].tobytes()
+
+    def set_names(self, metas, payload):
+        """Name sections (NameMeta, in read order) for the next decode_fasta /
+        decode_fasta_unpacked call, which then prints the names (ntc_decode_set_names)."""
+        arr = (NameMeta * max(len(metas), 1))(*metas)
+        buf = np.frombuffer(bytes(payload), dtype=np.uint8) if len(payload) else np.zeros(8, dtype=np.uint8)
+        self._check(self.L.ntc_decode_set_names(self.h, arr, len(metas), _p(buf), len(payload)),
+                    "ntc_decode_set_names")
+
     def exceptions(self):
         """The exception runs of the last encode / encode_pack / encode_pack_fastq call under
         policy keep (ntc_encode_exceptions), as a structured array of dtype NX_RUN in (read,
@@ -695,16 +762,17 @@ class GpuContext:
             raise e
         return bases[:nb.value].copy(), offs
 
-    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None):
+    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None, names=None):
         """encode_pack on FASTQ text parsed on the GPU (ntc_encode_pack_fastq) -> (list of
         BlockMeta, payload bytes, bases encoded).  With non_acgt (as for encode) the exception
         runs come fourth.  With qualities ("drop", "keep" or "bin8"; the call runs under that
-        mode) the quality sections come last, as qualities() returns them."""
+        mode) the quality sections come next, as qualities() returns them, and with names ("drop",
+        "keep" or "id") the name sections come last, as names() returns them."""
         t = np.frombuffer(bytes(text), dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
         nb = (n_reads + block_reads - 1) // block_reads
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
-        with self._policy(non_acgt), self._qmode(qualities):
+        with self._policy(non_acgt), self._qmode(qualities), self._nmode(names):
             rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas,
                                               ctypes.byref(out), ctypes.byref(used), ctypes.byref(nbases),
                                               ctypes.byref(bad))
@@ -722,6 +790,8 @@ class GpuContext:
             out += (self.exceptions(),)
         if qualities is not None:
             out += (self.qualities(),)
+        if names is not None:
+            out += (self.names(),)
         return out
 
     def encode_status(self):
@@ -983,7 +1053,7 @@ def concat_streams(blocks):
 
 # ---- FASTX ingest ---------------------------------------------------------------------
 def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_bases=0, deflate="zlib",
-                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1):
+                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1, names=None, n_fd=-1):
     """`ntcomp encode` file to file (ntc_encode_file, include/ntcomp_pipeline.h): FASTX ->
     GPU encode + block packer on every context -> deflate pool -> encoded.dat on out_fd.
     A plain FASTQ is parsed on the GPU unless host_parse.  Returns the per-stage stats as
@@ -992,8 +1062,20 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     symbols; "keep" writes their exception runs to nx_fd, and the stats gain an "nx" dict
     (ntc_nx_stats).  qualities ("drop", "keep", "bin8"; ntc_encode_file_ex): "keep" and "bin8"
     write the blocks' quality sections to q_fd ("NTCQ"), and the stats gain a "q" dict
-    (ntc_q_stats)."""
+    (ntc_q_stats).  names ("drop", "keep", "id"; ntc_encode_file_ex2): "keep" and "id" write the
+    blocks' name sections to n_fd ("NTCN"), and the stats gain an "n" dict (ntc_n_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
+    if names is not None:
+        fo = FileOpts2(ctypes.sizeof(FileOpts2), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
+                       None, None, _names_code(names), n_fd, None)
+        nx, q, n = NxStats(), QStats(), NStats()
+        d = _run_pipeline("ntc_encode_file_ex2", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                          tail=(ctypes.byref(nx), ctypes.byref(q), ctypes.byref(n)))
+        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
+        if qualities is not None:
+            d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
+        d["n"] = {k: int(getattr(n, k)) for k, _ in NStats._fields_}
+        return d
     if qualities is not None:
         fo = FileOpts(_policy_code(non_acgt or 0), nx_fd, _quality_code(qualities), q_fd, None, None)
         nx, q = NxStats(), QStats()
@@ -1011,7 +1093,7 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     return d
 
 
-def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None):
+def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None, n_path=None):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
@@ -1019,8 +1101,14 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
     (src/main.rs:202): stats["dropped_blocks"] > 0 and stats["error"] say so.  nx_path: the
     exception side file written by encode_file(non_acgt="keep"), whose symbols are put back
     (ntc_decode_file_nx).  q_path: the quality side file written by encode_file(qualities=
-    "keep" / "bin8"); the output is then FASTQ (ntc_decode_file_ex)."""
+    "keep" / "bin8"); the output is then FASTQ (ntc_decode_file_ex).  n_path: the name side file
+    written by encode_file(names="keep" / "id"); the reads then carry their names instead of
+    seq.N (ntc_decode_file_ex2)."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
+    if n_path is not None:
+        fo = FileOpts2(ctypes.sizeof(FileOpts2), 0, -1, 0, -1, None if nx_path is None else os.fsencode(nx_path),
+                       None if q_path is None else os.fsencode(q_path), 0, -1, os.fsencode(n_path))
+        return _run_pipeline("ntc_decode_file_ex2", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),))
     if q_path is not None:
         fo = FileOpts(0, -1, 0, -1, None if nx_path is None else os.fsencode(nx_path), os.fsencode(q_path))
         return _run_pipeline("ntc_decode_file_ex", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),))
@@ -1079,6 +1167,42 @@ def write_qualities(fd, mode, metas, payload, header=True, engine="libdeflate"):
                                        DEFLATE_ENGINES[engine])
         if rc:
             raise NtcError(rc, "ntc_q_write_section")
+
+
+def read_names(path):
+    """The name side file ("NTCN", include/ntcomp_codec.h) written beside an encoded.dat:
+    ntc_n_read -> (mode as an int, list of NameMeta, the inflated payload as bytes);
+    NtcError(NTC_ERR_FORMAT) for a malformed file."""
+    mode, pm, nb, pp, nbytes = ctypes.c_int(), ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_uint64()
+    rc = lib().ntc_n_read(os.fsencode(path), ctypes.byref(mode), ctypes.byref(pm), ctypes.byref(nb), ctypes.byref(pp),
+                          ctypes.byref(nbytes))
+    if rc:
+        raise NtcError(rc, f"ntc_n_read({path})")
+    try:
+        metas = [NameMeta.from_buffer_copy(ctypes.string_at(pm.value + i * ctypes.sizeof(NameMeta), ctypes.sizeof(NameMeta)))
+                 for i in range(nb.value)]
+        payload = ctypes.string_at(pp.value, nbytes.value) if nbytes.value else b""
+    finally:
+        lib().ntc_buffer_free(pm)
+        lib().ntc_buffer_free(pp)
+    return int(mode.value), metas, payload
+
+
+def write_names(fd, mode, metas, payload, header=True, engine="libdeflate"):
+    """The "NTCN" header (when header) and one section per NameMeta to fd (ntc_n_write_header,
+    ntc_n_write_section); payload: the bytes the metas' payload_off point into."""
+    if header:
+        rc = lib().ntc_n_write_header(fd, _names_code(mode))
+        if rc:
+            raise NtcError(rc, "ntc_n_write_header")
+    buf = np.frombuffer(bytes(payload), dtype=np.uint8) if len(payload) else np.zeros(8, dtype=np.uint8)
+    for m in metas:
+        if m.payload_off + m.payload_bytes > len(payload):
+            raise NtcError(1, "section outside the payload")
+        rc = lib().ntc_n_write_section(fd, ctypes.byref(m), ctypes.c_void_p(buf.ctypes.data + m.payload_off),
+                                       DEFLATE_ENGINES[engine])
+        if rc:
+            raise NtcError(rc, "ntc_n_write_section")
 
 
 def write_exceptions(fd, runs, sub, header=True):

@@ -188,12 +188,23 @@ def _check_q_args(args):
         _bad_args("encode: --quality-file is only written under --qualities keep or bin8")
 
 
+def _check_n_args(args):
+    """encode: --names drop|keep|id and --name-file PATH go together under keep and id."""
+    if args.names not in ("drop", "keep", "id"):
+        _bad_args("encode: --names: drop, keep or id")
+    if args.names != "drop" and not args.name_file:
+        _bad_args(f"encode: --names {args.names} requires --name-file PATH")
+    if args.names == "drop" and args.name_file is not None:
+        _bad_args("encode: --name-file is only written under --names keep or id")
+
+
 def cmd_encode(args):
     """main.rs:141-181 through the native pipeline (ntc_encode_file): plain FASTQ parsed
     on the GPU (--host-parse: on the host pool, as every other input is), GPU encode +
     block packer per context, deflate on the host pool, blocks written in file order."""
     _check_nx_args(args)
     _check_q_args(args)
+    _check_n_args(args)
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     log("Loading SBWT index...")
@@ -204,8 +215,13 @@ def cmd_encode(args):
         args.deflate = "adaptive" if nt.libdeflate_available() else "zlib"
     out = sys.stdout.buffer
     out.flush()
-    nx_file = q_file = None
+    nx_file = q_file = n_file = None
     try:
+        if args.names != "drop":
+            try:
+                n_file = open(args.name_file, "wb")
+            except OSError:
+                raise SystemExit(f"ntcomp: encode: cannot write {args.name_file}")
         if args.qualities != "drop":
             try:
                 q_file = open(args.quality_file, "wb")
@@ -220,6 +236,8 @@ def cmd_encode(args):
                                                        "nx_fd": nx_file.fileno() if nx_file else -1}
         if q_file:
             nx_args.update(qualities=args.qualities, q_fd=q_file.fileno())
+        if n_file:
+            nx_args.update(names=args.names, n_fd=n_file.fileno())
         res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, deflate=args.deflate,
                                                   host_parse=args.host_parse, **nx_args)
@@ -231,6 +249,8 @@ def cmd_encode(args):
             nx_file.close()
         if q_file:
             q_file.close()
+        if n_file:
+            n_file.close()
         for c in ctxs:
             c.close()
     if res["dropped_blocks"]:
@@ -244,7 +264,8 @@ def cmd_encode(args):
               gpu_parsed_batches=res["gpu_parsed"], non_acgt=args.non_acgt,
               **{"nx_" + k: v for k, v in res.get("nx", dict.fromkeys(("runs", "bases", "reads",
                                                                         "runs_in_dropped_blocks"), 0)).items()},
-              **({"qualities": args.qualities, **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}))
+              **({"qualities": args.qualities, **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}),
+              **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}))
 
 
 def cmd_decode(args):
@@ -261,7 +282,7 @@ def cmd_decode(args):
     try:
         res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, nx_path=args.exceptions,
-                                                  q_path=args.quality_file)
+                                                  q_path=args.quality_file, n_path=args.name_file)
     except nt.NtcError as e:
         raise SystemExit(f"ntcomp decode: {e}")
     finally:
@@ -334,6 +355,11 @@ def main(argv=None):
                    help="FASTQ quality scores: drop (default), keep (lossless) or bin8 (Phred scores binned to 8 levels, "
                         "lossy); keep and bin8 write them, packed on the GPU, to the --quality-file")
     e.add_argument("--quality-file", metavar="PATH", help="with --qualities keep or bin8: the side file to write")
+    e.add_argument("--names", default="drop", metavar="MODE",
+                   help="FASTQ read names: drop (default), keep (lossless: the header line after '@') or id (the name up "
+                        "to its first space or tab, lossy); keep and id write them, front-coded on the GPU, to the "
+                        "--name-file")
+    e.add_argument("--name-file", metavar="PATH", help="with --names keep or id: the side file to write")
     d = sub.add_parser("decode", help="Decode data written with Encode")
     d.add_argument("input_path", help="File with encoded fastX data.")
     d.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
@@ -346,6 +372,8 @@ def main(argv=None):
     d.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
     d.add_argument("--quality-file", metavar="PATH",
                    help="the side file of encode --qualities keep or bin8: the output is then FASTQ")
+    d.add_argument("--name-file", metavar="PATH",
+                   help="the side file of encode --names keep or id: the reads carry their names instead of seq.N")
     d.add_argument("--exceptions", metavar="PATH",
                    help="the side file of encode --non-acgt keep, whose symbols are put back")
     args = ap.parse_args(argv)

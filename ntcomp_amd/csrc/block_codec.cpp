@@ -50,6 +50,7 @@
 #include "codec_params.h"
 #include "nonacgt_core.h"
 #include "quality_core.h"
+#include "names_core.h"
 
 namespace {
 
@@ -1012,6 +1013,161 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
         *metas = (ntc_qual_meta *)std::malloc(all.size() * sizeof(ntc_qual_meta));
         if (!*metas) return NTC_ERR_CAPACITY;
         std::memcpy(*metas, all.data(), all.size() * sizeof(ntc_qual_meta));
+    }
+    if (!pay.empty()) {
+        *payload = (uint8_t *)std::malloc(pay.size());
+        if (!*payload) {
+            std::free(*metas);
+            *metas = nullptr;
+            return NTC_ERR_CAPACITY;
+        }
+        std::memcpy(*payload, pay.data(), pay.size());
+    }
+    *mode = buf[8];
+    *n_blocks = all.size();
+    *payload_bytes = pay.size();
+    return NTC_OK;
+}
+
+}  // extern "C"
+
+// ---- name side file "NTCN" (include/ntcomp_codec.h) -----------------------------------
+namespace {
+// the counts of a meta agree with one another (payload_off is the caller's)
+bool n_meta_ok(const ntc_name_meta &m) {
+    return !(m.n_reads >> 40) && m.mid_bytes <= m.name_bytes && m.name_bytes <= m.n_reads * ntc::kNMax &&
+           m.payload_bytes == ntc::n_payload_bytes(m.n_reads, m.mid_bytes);
+}
+// the payload of a section whose meta n_meta_ok took: every per-read rule, the sums, the padding
+bool n_section_ok(const ntc_name_meta &m, const uint8_t *p) {
+    const uint64_t n = m.n_reads;
+    uint64_t names = 0, mids = 0;
+    uint32_t plen = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t len = (uint32_t)p[2 * i] | (uint32_t)p[2 * i + 1] << 8, pre = p[2 * n + i], suf = p[3 * n + i];
+        if (!ntc::n_read_ok((uint32_t)(i % ntc::kNGroup), len, pre, suf, plen)) return false;
+        names += len;
+        mids += len - pre - suf;
+        plen = len;
+    }
+    if (names != m.name_bytes || mids != m.mid_bytes) return false;
+    for (uint64_t i = 4 * n + mids; i < m.payload_bytes; i++)
+        if (p[i]) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int ntc_n_write_header(int fd, int mode) {
+    if (fd < 0 || mode < 1 || mode > 2) return NTC_ERR_INVALID_ARG;
+    const uint8_t h[32] = {'N', 'T', 'C', 'N', 1, 0, 0, 0, (uint8_t)mode};
+    return nx_write_all(fd, h, sizeof(h)) ? NTC_OK : NTC_ERR_IO;
+}
+
+int ntc_n_deflate_section(const ntc_name_meta *meta, const uint8_t *payload, int engine, uint8_t **out, uint64_t *out_len) {
+    if (!meta || !out || !out_len || (meta->payload_bytes && !payload)) return NTC_ERR_INVALID_ARG;
+    *out = nullptr;
+    *out_len = 0;
+    if (!n_meta_ok(*meta) || !n_section_ok(*meta, payload)) return NTC_ERR_INVALID_ARG;
+    std::vector<uint8_t> buf(32);
+    if (!gzip_append(payload, meta->payload_bytes, engine, buf)) return NTC_ERR_FORMAT;
+    const uint64_t gz = buf.size() - 32;
+    if (gz >> 32) return NTC_ERR_CAPACITY;
+    std::memcpy(buf.data(), &meta->n_reads, 8);  // little-endian hosts only, as the block container
+    std::memcpy(buf.data() + 8, &meta->name_bytes, 8);
+    std::memcpy(buf.data() + 16, &meta->mid_bytes, 8);
+    const uint32_t gz32 = (uint32_t)gz;
+    std::memcpy(buf.data() + 24, &gz32, 4);
+    return hand_out(buf, out, out_len);
+}
+
+int ntc_n_write_section(int fd, const ntc_name_meta *meta, const uint8_t *payload, int engine) {
+    if (fd < 0) return NTC_ERR_INVALID_ARG;
+    uint8_t *sec = nullptr;
+    uint64_t n = 0;
+    const int rc = ntc_n_deflate_section(meta, payload, engine, &sec, &n);
+    if (rc) return rc;
+    const bool ok = nx_write_all(fd, sec, n);
+    std::free(sec);
+    return ok ? NTC_OK : NTC_ERR_IO;
+}
+
+int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_blocks, uint8_t **payload,
+               uint64_t *payload_bytes) {
+    if (!path || !mode || !metas || !n_blocks || !payload || !payload_bytes) return NTC_ERR_INVALID_ARG;
+    *mode = 0;
+    *metas = nullptr;
+    *n_blocks = 0;
+    *payload = nullptr;
+    *payload_bytes = 0;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return NTC_ERR_IO;
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+    const bool io_bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (io_bad) return NTC_ERR_IO;
+    static const uint8_t magic[8] = {'N', 'T', 'C', 'N', 1, 0, 0, 0};
+    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
+    if (buf[8] < 1 || buf[8] > 2) return NTC_ERR_FORMAT;
+    for (size_t i = 9; i < 32; i++)
+        if (buf[i]) return NTC_ERR_FORMAT;
+    // pass 1: the section headers, and where each member lies and inflates to
+    std::vector<ntc_name_meta> all;
+    std::vector<uint64_t> gz_at, gz_len;
+    uint64_t pay_bytes = 0;
+    size_t at = 32;
+    while (at < buf.size()) {
+        if (buf.size() - at < 32) return NTC_ERR_FORMAT;
+        ntc_name_meta m{};
+        const uint8_t *h = buf.data() + at;
+        std::memcpy(&m.n_reads, h, 8);
+        std::memcpy(&m.name_bytes, h + 8, 8);
+        std::memcpy(&m.mid_bytes, h + 16, 8);
+        uint32_t gz, pad;
+        std::memcpy(&gz, h + 24, 4);
+        std::memcpy(&pad, h + 28, 4);
+        at += 32;
+        m.payload_bytes = ntc::n_payload_bytes(m.n_reads & ((1ull << 40) - 1), m.mid_bytes & ((1ull << 48) - 1));
+        if (pad || !n_meta_ok(m) || buf.size() - at < gz) return NTC_ERR_FORMAT;
+        if (m.payload_bytes > (uint64_t)gz * 1100 + 4096) return NTC_ERR_FORMAT;  // past deflate's best ratio: not this member
+        m.payload_off = pay_bytes;
+        pay_bytes += m.payload_bytes;
+        gz_at.push_back(at);
+        gz_len.push_back(gz);
+        at += gz;
+        all.push_back(m);
+    }
+    // pass 2: the members inflate and are checked side by side
+    std::vector<uint8_t> pay(pay_bytes);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> bad{false};
+    const auto work = [&] {
+        std::vector<uint8_t> sec;
+        for (size_t i; (i = next.fetch_add(1)) < all.size() && !bad;) {
+            const ntc_name_meta &m = all[i];
+            if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, sec) || !n_section_ok(m, sec.data())) {
+                bad = true;
+                return;
+            }
+            if (m.payload_bytes) std::memcpy(pay.data() + m.payload_off, sec.data(), m.payload_bytes);
+        }
+    };
+    {
+        const size_t T = std::min<size_t>(all.size(), (size_t)std::max(1, std::min(16, ntc_host_threads())));
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < T; t++) pool.emplace_back(work);
+        work();
+        for (auto &t : pool) t.join();
+    }
+    if (bad) return NTC_ERR_FORMAT;
+    if (!all.empty()) {
+        *metas = (ntc_name_meta *)std::malloc(all.size() * sizeof(ntc_name_meta));
+        if (!*metas) return NTC_ERR_CAPACITY;
+        std::memcpy(*metas, all.data(), all.size() * sizeof(ntc_name_meta));
     }
     if (!pay.empty()) {
         *payload = (uint8_t *)std::malloc(pay.size());

@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "nonacgt_core.h"
 #include "quality_core.h"
+#include "names_core.h"
 #include "ntc_internal.h"
 
 using namespace ntc;
@@ -45,7 +46,8 @@ enum WsSlot {
     WS_FQ_RAW, WS_FQ_TILES, WS_FQ_NL, WS_FQ_KEPT, WS_PACK_SEGS,
     WS_UNP_PAY, WS_UNP_MARKS, WS_UNP_ST, WS_UNP_VALS, WS_UNP_RECS, WS_UNP_OUT,
     WS_NX_BITS, WS_NX_RUNS, WS_NX_PATCH,
-    WS_Q_QUALS, WS_Q_BLOCKS, WS_Q_PAYLOAD, WS_QD_IN, WS_QD_QUALS, WS_COUNT
+    WS_Q_QUALS, WS_Q_BLOCKS, WS_Q_PAYLOAD, WS_QD_IN, WS_QD_QUALS,
+    WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -75,6 +77,7 @@ struct ntc_ctx {
     unsigned long long *d_status = nullptr;
     // status mailbox in pinned host memory: {status, count a, count b}, written by k_status_box
     // at the end of a device call, so *_status() is one stream sync instead of D2H copies
+    // (16 words: 0-3 k_status_box, 4-5 non-ACGT, 6-7 qualities, 8-9 names)
     uint64_t *h_box = nullptr;
     bool box_valid = false;
     // the records of the last ntc_unpack_streams (in WS_UNP_RECS) and their read / base counts
@@ -141,6 +144,15 @@ struct ntc_ctx {
     std::vector<ntc_qual_meta> qd_metas;
     std::vector<uint64_t> qd_payload;
     bool qd_has_pending = false;
+    // read names (names.hip): the mode (0 drop, 1 keep, 2 id), the sections the last
+    // ntc_encode_pack_fastq left in WS_N_BLOCKS / WS_N_PAYLOAD, the sections waiting for the
+    // next FASTA decode call (which then writes the names instead of seq.N)
+    int n_mode = 0;
+    uint64_t n_blocks = 0, n_bytes = 0;
+    std::vector<ntc_name_meta> nd_metas;
+    std::vector<uint64_t> nd_payload;
+    uint64_t nd_name_bytes = 0;
+    bool nd_has_pending = false;
     FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
@@ -712,6 +724,134 @@ int q_unpack(ntc_ctx *ctx, const std::vector<ntc_qual_meta> &metas, const std::v
     return NTC_OK;
 }
 
+// ---- read names (names.hip) -------------------------------------------------------------
+// After a GPU FASTQ parse, beside the quality pass: measure, offsets, emit.  Asynchronous,
+// with a status word of its own; the status and the payload's size reach the host in mailbox
+// words 8 and 9 at the encode call's own status sync (n_collect).  Mode 0 returns before
+// anything is launched.
+void n_begin(ntc_ctx *ctx) {  // an encode call starts: the last call's sections are gone
+    ctx->n_blocks = ctx->n_bytes = 0;
+}
+int n_pack(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads) {
+    if (ctx->n_mode == 0 || n_reads == 0) return NTC_OK;
+    const uint64_t nb = (n_reads + block_reads - 1) / block_reads;
+    const FastqArgs &f = ctx->fq_last;
+    void *cols, *blk, *pay;
+    int rc;
+    // start, len, mid (u32), the two scans (u64), pre and suf (u8)
+    const uint64_t n1 = n_reads + 1;
+    if ((rc = ensure(ctx, WS_N_COLS, n1 * (3 * 4 + 2 * 8) + 2 * n_reads + 64, &cols))) return rc;
+    if ((rc = ensure(ctx, WS_N_BLOCKS, 64 + (nb + 1) * sizeof(NBlock), &blk))) return rc;
+    if ((rc = ensure(ctx, WS_N_PAYLOAD, names_payload_max(f.n_raw, n_reads, nb), &pay))) return rc;
+    NEncArgs a{};
+    a.raw = f.raw;
+    a.n_raw = f.n_raw;
+    a.nl = f.nl;
+    a.n_nl_p = f.tile_base + fastq_tiles(f.n_raw);
+    a.n_reads = n_reads;
+    a.n_blocks = nb;
+    a.block_reads = block_reads;
+    a.mode = (uint32_t)ctx->n_mode;
+    a.len_off = (uint64_t *)cols;
+    a.mid_off = a.len_off + n1;
+    a.start = (uint32_t *)(a.mid_off + n1);
+    a.len = a.start + n1;
+    a.mid = a.len + n1;
+    a.ps = (uint8_t *)(a.mid + n1);
+    a.tmp = f.tmp;
+    a.status = (unsigned long long *)blk;
+    a.blocks = (NBlock *)((uint8_t *)blk + 64);
+    a.payload = (uint8_t *)pay;
+    a.box = ctx->h_box;
+    ctx->h_box[8] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
+    ctx->h_box[9] = 0;
+    launch_names_pack(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+// After the encode call's sync: the names pass's verdict.  A name too long fails the call.
+int n_collect(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads, int64_t *bad_read) {
+    if (ctx->n_mode == 0 || n_reads == 0) return NTC_OK;
+    const uint64_t st = ((volatile uint64_t *)ctx->h_box)[8];
+    if (st != ~0ull) {
+        if (bad_read) *bad_read = (int64_t)(st >> 8);
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "name of read %lld: longer than %u bytes", (long long)(st >> 8), kNMax);
+        return set_err(ctx, (int)(st & 0xFF), buf);
+    }
+    ctx->n_blocks = (n_reads + block_reads - 1) / block_reads;
+    ctx->n_bytes = ((volatile uint64_t *)ctx->h_box)[9];
+    return NTC_OK;
+}
+int n_unsupported(ntc_ctx *ctx, const char *call) {
+    return set_err(ctx, NTC_ERR_UNSUPPORTED, std::string(call) + " takes bases without header lines: names keep / id "
+                                             "need ntc_encode_pack_fastq");
+}
+
+// the pending sections leave the context: the call that takes them uses them once
+bool n_take_pending(ntc_ctx *ctx, std::vector<ntc_name_meta> &metas, std::vector<uint64_t> &payload) {
+    metas.clear();
+    payload.clear();
+    if (!ctx->nd_has_pending) return false;
+    metas.swap(ctx->nd_metas);
+    payload.swap(ctx->nd_payload);
+    ctx->nd_has_pending = false;
+    ctx->nd_name_bytes = 0;
+    return true;
+}
+
+// Decode side: the sections -> the names of the decoded reads, read by read (WS_ND_NAMES) and
+// where each starts (*d_name_off, n_reads + 1 words); then the status mailbox again.
+int n_expand(ntc_ctx *ctx, const std::vector<ntc_name_meta> &metas, const std::vector<uint64_t> &payload,
+             uint64_t n_reads, uint8_t **d_names, uint64_t **d_name_off) {
+    const uint64_t nb = metas.size();
+    std::vector<NDecBlock> up(nb);
+    uint64_t r = 0, max_reads = 0, name_bytes = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+        const ntc_name_meta &m = metas[b];
+        up[b].r0 = r;
+        up[b].r1 = r += m.n_reads;
+        up[b].name_bytes = m.name_bytes;
+        up[b].mid_bytes = m.mid_bytes;
+        up[b].payload_off = m.payload_off;
+        max_reads = std::max(max_reads, m.n_reads);
+        name_bytes += m.name_bytes;
+    }
+    void *in, *cols, *names;
+    int rc;
+    const uint64_t blk_bytes = (nb * sizeof(NDecBlock) + 63) & ~63ull, n1 = n_reads + 1;
+    if ((rc = ensure(ctx, WS_ND_IN, blk_bytes + payload.size() * 8 + 64, &in))) return rc;
+    if ((rc = ensure(ctx, WS_ND_COLS, n1 * (2 * 8 + 2 * 4) + scan_tmp_words(n1) * 8 + 64, &cols))) return rc;
+    if ((rc = ensure(ctx, WS_ND_NAMES, name_bytes + 64, &names))) return rc;
+    if (nb) HIP_TRY(ctx, hipMemcpy(in, up.data(), nb * sizeof(NDecBlock), hipMemcpyHostToDevice));
+    if (!payload.empty())
+        HIP_TRY(ctx, hipMemcpy((uint8_t *)in + blk_bytes, payload.data(), payload.size() * 8, hipMemcpyHostToDevice));
+    NDecArgs a{};
+    a.blocks = (const NDecBlock *)in;
+    a.n_blocks = nb;
+    a.max_reads = max_reads;
+    a.payload = (const uint8_t *)in + blk_bytes;
+    a.payload_bytes = payload.size() * 8;
+    a.n_reads = n_reads;
+    a.name_off = (uint64_t *)cols;
+    a.mid_off = a.name_off + n1;
+    a.tmp = a.mid_off + n1;
+    a.len = (uint32_t *)(a.tmp + scan_tmp_words(n1));
+    a.mid = a.len + n1;
+    a.names = (uint8_t *)names;
+    a.names_cap = name_bytes;
+    a.status = ctx->d_status;
+    launch_names_expand(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ctx->box_valid && ctx->last == kDecode)
+        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
+                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    *d_names = (uint8_t *)names;
+    *d_name_off = a.name_off;
+    return NTC_OK;
+}
+
 // GPU packer (pack.hip) over the records of n_reads reads in HBM: block b = reads
 // [b * block_reads, ...).  Pass 1 on the device, Rice parameters and payload layout on the
 // host (glibc f64 math, codec_params.h), pass 2 on the device.  Synchronous.
@@ -872,7 +1012,7 @@ int ntc_ctx_create(int device, ntc_ctx **out) {
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void **)&ctx->d_status, 64) != hipSuccess ||
-        hipHostMalloc((void **)&ctx->h_box, 64, hipHostMallocDefault) != hipSuccess) {
+        hipHostMalloc((void **)&ctx->h_box, 128, hipHostMallocDefault) != hipSuccess) {
         delete ctx;
         return NTC_ERR_HIP;
     }
@@ -1393,6 +1533,11 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
         ctx->q_mode = (int)value;
         return NTC_OK;
     }
+    if (std::strcmp(key, "names") == 0) {  // FASTQ read names: 0 drop, 1 keep, 2 id (ntcomp_codec.h)
+        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "names must be 0 (drop), 1 (keep) or 2 (id)");
+        ctx->n_mode = (int)value;
+        return NTC_OK;
+    }
     if (std::strcmp(key, "non_acgt") == 0) {  // N and IUPAC symbols: 0 error, 1 mask, 2 keep (ntcomp_gpu.h)
         if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)");
         ctx->nx_policy = (int)value;
@@ -1444,6 +1589,7 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "spill_reruns") == 0) *value = (int64_t)ctx->spill_reruns;
     else if (std::strcmp(key, "non_acgt") == 0) *value = ctx->nx_policy;
     else if (std::strcmp(key, "qualities") == 0) *value = ctx->q_mode;
+    else if (std::strcmp(key, "names") == 0) *value = ctx->n_mode;
     else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
     else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
     else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
@@ -1474,6 +1620,7 @@ int ntc_encode_batch_device(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_batch_device");
+    if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_batch_device");
     if (ctx->nx_policy != 0)
         return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need the host-buffer encode calls "
                                                  "(the caller's device buffer is const)");
@@ -1582,6 +1729,7 @@ int ntc_encode_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_of
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_batch");
+    if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_batch");
     nx_begin(ctx);
     if (ctx->encode_variant != 4 && ctx->nx_policy != 0)
         return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need encode_variant 4");
@@ -1858,6 +2006,7 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
     if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_pack_batch");
+    if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_pack_batch");
     for (uint64_t r = 0; r < n_reads; r++)
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
@@ -1977,9 +2126,12 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     if (n_bases) *n_bases = total;
     nx_begin(ctx);
     q_begin(ctx);
+    n_begin(ctx);
     if (n_reads == 0) return NTC_OK;
     // the quality lines are packed from the text while the reads are encoded (mode 0: nothing runs)
     if ((rc = q_pack(ctx, (const uint64_t *)d_offs, n_reads, total, block_reads))) return rc;
+    // and the names are front-coded from it (mode 0: nothing runs)
+    if ((rc = n_pack(ctx, n_reads, block_reads))) return rc;
     const auto restage = [&]() -> int {  // the text is still in HBM: parse it again (it parsed clean once)
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
         ctx->fq_last.tmp = (uint64_t *)ctx->ws[WS_SCANTMP].p;  // the scan scratch may have grown (never shrinks) since
@@ -1989,17 +2141,24 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     };
     rc = encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads, meta,
                             payload, payload_bytes, bad_read, restage);
-    if (ctx->q_mode == 0) return rc;
-    // a read the quality pass refused fails the call, whatever the encode said of it
+    if (ctx->q_mode == 0 && ctx->n_mode == 0) return rc;
+    // a read the quality or the names pass refused fails the call, whatever the encode said of it
     if (rc) (void)hipStreamSynchronize(ctx->stream);  // (an encode that failed early may not have synchronised)
-    const int qrc = q_collect(ctx, n_reads, block_reads, bad_read);
-    if (rc) q_begin(ctx);  // a failed call leaves no sections
-    if (qrc && !rc) {
+    int64_t q_bad = -1, n_bad = -1;
+    const int qrc = q_collect(ctx, n_reads, block_reads, &q_bad);
+    const int nrc = n_collect(ctx, n_reads, block_reads, &n_bad);
+    const int src = qrc ? qrc : nrc;
+    if (rc || src) {  // a failed call leaves no sections
+        q_begin(ctx);
+        n_begin(ctx);
+    }
+    if (src && bad_read) *bad_read = qrc ? q_bad : n_bad;
+    if (src && !rc) {
         std::free(*payload);
         *payload = nullptr;
         *payload_bytes = 0;
     }
-    return qrc ? qrc : rc;
+    return src ? src : rc;
 }
 
 }  // extern "C"
@@ -2020,7 +2179,10 @@ uint64_t fasta_bytes(uint64_t n_reads, uint64_t n_bases, uint64_t first_id) {
 // the text a decode call writes: FASTQ when quality sections are pending ("\n+\n" and the
 // qualities more per read)
 uint64_t text_bytes(const ntc_ctx *ctx, uint64_t n_reads, uint64_t n_bases, uint64_t first_id) {
-    return fasta_bytes(n_reads, n_bases, first_id) + (ctx->qd_has_pending ? n_bases + 3 * n_reads : 0);
+    const uint64_t q = ctx->qd_has_pending ? n_bases + 3 * n_reads : 0;
+    // with names pending: ">" or "@", the name, '\n', the read, '\n' (and no seq.N)
+    if (ctx->nd_has_pending) return ctx->nd_name_bytes + n_bases + 3 * n_reads + q;
+    return fasta_bytes(n_reads, n_bases, first_id) + q;
 }
 
 // walk + FASTA text of records already in HBM (d_recs), text D2H into out (need bytes)
@@ -2036,7 +2198,10 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     uint32_t nx_sub = 0;
     std::vector<ntc_qual_meta> qm;
     std::vector<uint64_t> qp;
-    const bool fastq = q_take_pending(ctx, qm, qp);  // (both pending lists leave the context here)
+    std::vector<ntc_name_meta> nm;
+    std::vector<uint64_t> np;
+    const bool fastq = q_take_pending(ctx, qm, qp);  // (all pending lists leave the context here)
+    const bool named = n_take_pending(ctx, nm, np);
     if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= n_reads)
         return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
     if (fastq) {
@@ -2047,6 +2212,14 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
         }
         if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "quality sections for fewer reads than decoded");
     }
+    if (named) {
+        uint64_t r = 0;
+        for (const ntc_name_meta &m : nm) {
+            if (m.n_reads > n_reads - r) return set_err(ctx, NTC_ERR_FORMAT, "name sections for more reads than decoded");
+            r += m.n_reads;
+        }
+        if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "name sections for fewer reads than decoded");
+    }
     if ((rc = ntc_decode_batch_device(ctx, d_recs, n_recs, (uint8_t *)d_bases, n_bases + 64, (uint64_t *)d_offs,
                                       n_reads + 2)))
         return rc;
@@ -2056,8 +2229,15 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     // and the qualities are unpacked by the decoded reads' offsets, after the patch
     uint8_t *d_quals = nullptr;
     if (fastq && (rc = q_unpack(ctx, qm, qp, n_reads, n_bases, (const uint64_t *)d_offs, &d_quals))) return rc;
+    // and the names are expanded, each section on its own
+    uint8_t *d_names = nullptr;
+    uint64_t *d_name_off = nullptr;
+    if (named && (rc = n_expand(ctx, nm, np, n_reads, &d_names, &d_name_off))) return rc;
     uint64_t *sizes = (uint64_t *)d_scan, *out_offs = sizes + (n_reads + 1), *tmp = out_offs + (n_reads + 1);
-    if (fastq)
+    if (named)
+        launch_named_text((const uint8_t *)d_bases, d_quals, (const uint64_t *)d_offs, d_names, d_name_off, n_reads,
+                          ctx->d_status, sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
+    else if (fastq)
         launch_fastq_text((const uint8_t *)d_bases, d_quals, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status,
                           sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
     else
@@ -2321,6 +2501,50 @@ int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t 
     ctx->qd_payload.resize(payload_bytes / 8);
     if (payload_bytes) std::memcpy(ctx->qd_payload.data(), payload, payload_bytes);
     ctx->qd_has_pending = true;
+    return NTC_OK;
+}
+
+int ntc_encode_names(ntc_ctx *ctx, ntc_name_meta *metas, uint64_t meta_cap, uint8_t *payload, uint64_t payload_cap,
+                     uint64_t *n_blocks, uint64_t *payload_bytes) {
+    if (!ctx || !n_blocks || !payload_bytes || (meta_cap && !metas) || (payload_cap && !payload))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_blocks = ctx->n_blocks;
+    *payload_bytes = ctx->n_bytes;
+    if (ctx->n_blocks > meta_cap || ctx->n_bytes > payload_cap)
+        return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the name sections");
+    if (ctx->n_blocks == 0) return NTC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    static_assert(sizeof(NBlock) == sizeof(ntc_name_meta), "the device table is the public meta");
+    HIP_TRY(ctx, hipMemcpy(metas, (const uint8_t *)ctx->ws[WS_N_BLOCKS].p + 64, ctx->n_blocks * sizeof(NBlock),
+                           hipMemcpyDeviceToHost));
+    if (ctx->n_bytes) HIP_TRY(ctx, hipMemcpy(payload, ctx->ws[WS_N_PAYLOAD].p, ctx->n_bytes, hipMemcpyDeviceToHost));
+    return NTC_OK;
+}
+
+int ntc_decode_set_names(ntc_ctx *ctx, const ntc_name_meta *metas, uint64_t n_blocks, const uint8_t *payload,
+                         uint64_t payload_bytes) {
+    if (!ctx || (n_blocks && !metas) || (payload_bytes && !payload)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    ctx->nd_metas.clear();
+    ctx->nd_payload.clear();
+    ctx->nd_has_pending = false;
+    ctx->nd_name_bytes = 0;
+    if (n_blocks == 0) return NTC_OK;
+    if (payload_bytes & 7) return set_err(ctx, NTC_ERR_FORMAT, "name payload is not a multiple of 8 bytes");
+    uint64_t name_bytes = 0;
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        const ntc_name_meta &m = metas[b];
+        if (m.n_reads >> 40 || m.mid_bytes >> 48 || m.mid_bytes > m.name_bytes || m.name_bytes > m.n_reads * kNMax ||
+            m.payload_bytes != n_payload_bytes(m.n_reads, m.mid_bytes))
+            return set_err(ctx, NTC_ERR_FORMAT, "name section " + std::to_string(b) + ": counts or payload size");
+        if ((m.payload_off & 7) || m.payload_off > payload_bytes || m.payload_bytes > payload_bytes - m.payload_off)
+            return set_err(ctx, NTC_ERR_FORMAT, "name section " + std::to_string(b) + ": payload place");
+        name_bytes += m.name_bytes;
+    }
+    ctx->nd_metas.assign(metas, metas + n_blocks);
+    ctx->nd_payload.resize(payload_bytes / 8);
+    if (payload_bytes) std::memcpy(ctx->nd_payload.data(), payload, payload_bytes);
+    ctx->nd_name_bytes = name_bytes;
+    ctx->nd_has_pending = true;
     return NTC_OK;
 }
 
@@ -2588,6 +2812,9 @@ struct NxHookFill {
         ntc::g_q_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "qualities", mode); };
         ntc::g_q_hooks.encode_qualities = ntc_encode_qualities;
         ntc::g_q_hooks.decode_set_qualities = ntc_decode_set_qualities;
+        ntc::g_n_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "names", mode); };
+        ntc::g_n_hooks.encode_names = ntc_encode_names;
+        ntc::g_n_hooks.decode_set_names = ntc_decode_set_names;
     }
 } g_nx_hook_fill;
 }  // namespace

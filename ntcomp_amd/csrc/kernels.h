@@ -310,6 +310,59 @@ void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uin
                        uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,
                        uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s);
 
+// Read names (names.hip, names_core.h).  Encode side, after launch_fastq_parse over the same
+// text: start / len / mid: n_reads + 1 words each, ps: two columns of n_reads bytes (pre,
+// suf), len_off / mid_off: n_reads + 1 words (exclusive scans, tmp: scan_tmp_words(n_reads)),
+// blocks: n_blocks + 1 entries (the last holds the totals), payload: names_payload_max bytes.
+// status: a word of the names pass's own (preset here), read << 8 | NTC_ERR_FORMAT for the
+// first name past NTC_NAME_MAX; box[8] = that status, box[9] = payload bytes.
+struct NBlock {
+    uint64_t n_reads, name_bytes, mid_bytes, payload_off, payload_bytes;
+};
+struct NEncArgs {
+    const uint8_t *raw;
+    uint64_t n_raw;
+    const uint32_t *nl;
+    const uint64_t *n_nl_p;
+    uint64_t n_reads, n_blocks;
+    uint32_t block_reads, mode;
+    uint32_t *start, *len, *mid;
+    uint8_t *ps;
+    uint64_t *len_off, *mid_off, *tmp;
+    NBlock *blocks;
+    uint8_t *payload;
+    unsigned long long *status;
+    uint64_t *box;
+};
+uint64_t names_payload_max(uint64_t n_raw, uint64_t n_reads, uint64_t n_blocks);
+void launch_names_pack(const NEncArgs &a, hipStream_t s);
+// Decode side: section b covers reads [r0, r1) of the decoded batch and lies at payload +
+// payload_off (the host checked its size and place).  len / mid: n_reads + 1 words,
+// name_off / mid_off: their exclusive scans, names: names_cap bytes for the expanded names,
+// read by read.  Any per-read condition that fails, a section whose mids or names do not
+// sum to its meta, sets status (the decode call's) to r << 8 | NTC_ERR_FORMAT.
+struct NDecBlock {
+    uint64_t r0, r1, name_bytes, mid_bytes, payload_off;
+};
+struct NDecArgs {
+    const NDecBlock *blocks;
+    uint64_t n_blocks, max_reads;  // max_reads: the reads of the largest section
+    const uint8_t *payload;
+    uint64_t payload_bytes;
+    uint64_t n_reads;
+    uint32_t *len, *mid;
+    uint64_t *name_off, *mid_off, *tmp;
+    uint8_t *names;
+    uint64_t names_cap;
+    unsigned long long *status;
+};
+void launch_names_expand(const NDecArgs &a, hipStream_t s);
+// launch_fasta / launch_fastq_text with names: ">{name r}\n{read r}\n", or with d_quals
+// "@{name r}\n{read r}\n+\n{qualities r}\n"
+void launch_named_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, const uint8_t *d_names,
+                       const uint64_t *d_name_off, uint64_t n, const unsigned long long *d_status, uint64_t *sizes,
+                       uint64_t *out_offs, uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s);
+
 void launch_encode(const EncodeArgs &a, hipStream_t s);
 void launch_encode4(const Enc4Args &a, uint64_t total, uint32_t ms_blocks, hipStream_t s,
                     hipEvent_t ev_ms_begin, hipEvent_t ev_ms_end);

@@ -93,6 +93,7 @@ struct ntc_block_meta;
 struct ntc_ctx;
 struct ntc_nx_run;
 struct ntc_qual_meta;
+struct ntc_name_meta;
 namespace ntc {
 // a plain FASTQ that ntc_fastx_open mapped: its bytes (null for any other input), and
 // moving the mapped parser to byte pos (a record start) -- pipeline.cpp's GPU-parse reader
@@ -139,6 +140,16 @@ struct QHooks {
                                 uint64_t payload_bytes);
 };
 extern QHooks g_q_hooks;
+// ... and for read names: with the table null, ntc_encode_file_ex2 / ntc_decode_file_ex2
+// answer NTC_ERR_UNSUPPORTED to a name mode other than drop or to a name file.
+struct NHooks {
+    int (*set_mode)(::ntc_ctx *ctx, int mode);  // ctx option "names"
+    int (*encode_names)(::ntc_ctx *ctx, ::ntc_name_meta *metas, uint64_t meta_cap, uint8_t *payload,
+                        uint64_t payload_cap, uint64_t *n_blocks, uint64_t *payload_bytes);
+    int (*decode_set_names)(::ntc_ctx *ctx, const ::ntc_name_meta *metas, uint64_t n_blocks, const uint8_t *payload,
+                            uint64_t payload_bytes);
+};
+extern NHooks g_n_hooks;
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

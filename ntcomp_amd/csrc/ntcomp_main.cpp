@@ -9,9 +9,11 @@
 //   ntcomp encode -i P [--gpus N | --devices 0,0,..] [--threads T] [--blocks-per-batch B]
 //                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
 //                 [--non-acgt error|mask|keep] [--exceptions PATH]
-//                 [--qualities drop|keep|bin8] [--quality-file PATH] FILE > encoded.dat
+//                 [--qualities drop|keep|bin8] [--quality-file PATH]
+//                 [--names drop|keep|id] [--name-file PATH] FILE > encoded.dat
 //   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
-//                 [--exceptions PATH] [--quality-file PATH] FILE > out.fasta (FASTQ with --quality-file)
+//                 [--exceptions PATH] [--quality-file PATH] [--name-file PATH] FILE > out.fasta
+//                 (FASTQ with --quality-file, the reads' own names with --name-file)
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -71,7 +73,7 @@ bool takes_value(const std::string &o) {
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
                               "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
-                              "--qualities", "--quality-file"};
+                              "--qualities", "--quality-file", "--names", "--name-file"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -241,6 +243,12 @@ int cmd_encode(const Args &a) {
     if (q_mode > 0 && q_path.empty()) bad_args("encode: --qualities " + q_name + " requires --quality-file PATH");
     if (q_mode == 0 && a.flag("--quality-file"))
         bad_args("encode: --quality-file is only written under --qualities keep or bin8");
+    // read names: drop (default), keep, or id, with the front-coded sections in a side file
+    const std::string n_name = a.get("--names", nullptr, "drop"), n_path = a.get("--name-file", nullptr, "");
+    const int n_mode = n_name == "drop" ? 0 : n_name == "keep" ? 1 : n_name == "id" ? 2 : -1;
+    if (n_mode < 0) bad_args("encode: --names: drop, keep or id");
+    if (n_mode > 0 && n_path.empty()) bad_args("encode: --names " + n_name + " requires --name-file PATH");
+    if (n_mode == 0 && a.flag("--name-file")) bad_args("encode: --name-file is only written under --names keep or id");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
@@ -268,20 +276,34 @@ int cmd_encode(const Args &a) {
     int q_fd = -1;
     if (q_mode > 0 && (q_fd = ::open(q_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
         die("encode: cannot write " + q_path);
+    ntc_n_stats ns{};
+    int n_fd = -1;
+    if (n_mode > 0 && (n_fd = ::open(n_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
+        die("encode: cannot write " + n_path);
     const ntc_file_opts fo{policy, nx_fd, q_mode, q_fd, nullptr, nullptr};
+    const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd, nullptr};
     std::fflush(stdout);
-    const int rc = q_mode > 0 ? ntc_encode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st, &nx, &qs)
+    const int rc = n_mode > 0 ? ntc_encode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st, &nx, &qs, &ns)
+                   : q_mode > 0 ? ntc_encode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st, &nx, &qs)
                    : policy == NTC_NX_ERROR
                        ? ntc_encode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
                        : ntc_encode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, policy, nx_fd, &o, &st, &nx);
     if (nx_fd >= 0 && ::close(nx_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + nx_path);
     if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
-    char qjson[256] = "";  // the quality file's figures, when one was written
+    if (n_fd >= 0 && ::close(n_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + n_path);
+    char qjson[640] = "";  // the quality and name files' figures, when they were written
     if (q_mode > 0)
-        std::snprintf(qjson, sizeof(qjson), "\"qualities\": \"%s\", \"q_sections\": %llu, \"q_quals\": %llu, "
+        std::snprintf(qjson, 256, "\"qualities\": \"%s\", \"q_sections\": %llu, \"q_quals\": %llu, "
                                             "\"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
                       q_name.c_str(), (unsigned long long)qs.sections, (unsigned long long)qs.quals,
                       (unsigned long long)qs.packed_bytes, (unsigned long long)qs.deflated_bytes);
+    if (n_mode > 0)
+        std::snprintf(qjson + std::strlen(qjson), 320, "\"names\": \"%s\", \"n_sections\": %llu, \"n_names\": %llu, "
+                                                       "\"n_name_bytes\": %llu, \"n_payload_bytes\": %llu, "
+                                                       "\"n_deflated_bytes\": %llu, ",
+                      n_name.c_str(), (unsigned long long)ns.sections, (unsigned long long)ns.names,
+                      (unsigned long long)ns.name_bytes, (unsigned long long)ns.payload_bytes,
+                      (unsigned long long)ns.deflated_bytes);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -333,8 +355,12 @@ int cmd_decode(const Args &a) {
     const std::string nx_path = a.get("--exceptions", nullptr, "");  // the side file of encode --non-acgt keep
     const std::string q_path = a.get("--quality-file", nullptr, "");  // ... of encode --qualities keep: FASTQ out
     const ntc_file_opts fo{0, -1, 0, -1, nx_path.empty() ? nullptr : nx_path.c_str(), q_path.c_str()};
+    const std::string n_path = a.get("--name-file", nullptr, "");  // ... of encode --names keep: the reads' names
+    const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), 0, -1, 0, -1, fo.nx_path,
+                             q_path.empty() ? nullptr : q_path.c_str(), 0, -1, n_path.c_str()};
     std::fflush(stdout);
-    const int rc = !q_path.empty() ? ntc_decode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st)
+    const int rc = !n_path.empty() ? ntc_decode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st)
+                   : !q_path.empty() ? ntc_decode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st)
                    : nx_path.empty()
                        ? ntc_decode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
                        : ntc_decode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), nx_path.c_str(), 1, &o, &st);
@@ -454,8 +480,10 @@ void usage(FILE *f) {
                  "Sequencing data compression with SBWT + k-bounded matching statistics; encode/decode hot path on "
                  "MI355X.\n\nusage: ntcomp build -o PREFIX [-k K] [-m MEM_GB] [--temp-dir DIR] FILES...\n"
                  "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH]\n"
-                 "                     [--qualities drop|keep|bin8] [--quality-file PATH] FILE > encoded.dat\n"
-                 "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] FILE > out.fasta\n\n"
+                 "                     [--qualities drop|keep|bin8] [--quality-file PATH]\n"
+                 "                     [--names drop|keep|id] [--name-file PATH] FILE > encoded.dat\n"
+                 "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH] FILE\n"
+                 "                     > out.fasta\n\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
                  "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
                  "                     the replaced symbols to the --exceptions file (lossless)\n"
@@ -465,7 +493,12 @@ void usage(FILE *f) {
                  "                     scores binned to 8 levels, lossy); keep and bin8 write them, packed on the GPU,\n"
                  "                     to the --quality-file\n"
                  "  --quality-file PATH  encode --qualities keep|bin8: the side file to write; decode: the side file\n"
-                 "                     whose qualities are printed: the output is then FASTQ\n");
+                 "                     whose qualities are printed: the output is then FASTQ\n"
+                 "  --names MODE       encode: FASTQ read names: drop (default), keep (lossless: the header line\n"
+                 "                     after '@'), or id (the name up to its first space or tab, lossy); keep and id\n"
+                 "                     write them, front-coded on the GPU, to the --name-file\n"
+                 "  --name-file PATH   encode --names keep|id: the side file to write; decode: the side file whose\n"
+                 "                     names are printed instead of seq.N\n");
 }
 
 }  // namespace

@@ -50,6 +50,7 @@
 namespace ntc {
 NxHooks g_nx_hooks = {nullptr, nullptr, nullptr, nullptr};  // capi.cpp fills it at load
 QHooks g_q_hooks = {nullptr, nullptr, nullptr};
+NHooks g_n_hooks = {nullptr, nullptr, nullptr};
 }
 
 namespace {
@@ -213,6 +214,10 @@ struct BlockOut {  // a deflated block (its four streams' parts), or a dropped o
     ntc_qual_meta qmeta{};
     uint8_t *qsec = nullptr;
     uint64_t qlen = 0;
+    bool has_n = false;              // names mode keep / id: its section, likewise
+    ntc_name_meta nmeta{};
+    uint8_t *nsec = nullptr;
+    uint64_t nlen = 0;
 };
 
 struct Shared {
@@ -241,7 +246,8 @@ extern "C" {
 // q_mode / q_fd / qs: ntc_encode_file_ex's quality side file (q_mode 0: none)
 static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
                             const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx,
-                            int q_mode = 0, int q_fd = -1, ntc_q_stats *qs = nullptr) {
+                            int q_mode = 0, int q_fd = -1, ntc_q_stats *qs = nullptr, int n_mode = 0, int n_fd = -1,
+                            ntc_n_stats *ns = nullptr) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
@@ -249,6 +255,11 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     const ntc::QHooks &qh = ntc::g_q_hooks;
     if (q_mode && (!qh.set_mode || !qh.encode_qualities)) return NTC_ERR_UNSUPPORTED;
     ntc_q_stats QS{};
+    // n_mode / n_fd / ns: ntc_encode_file_ex2's name side file (n_mode 0: none)
+    if (n_mode < 0 || n_mode > 2 || (n_mode ? n_fd < 0 : n_fd != -1)) return NTC_ERR_INVALID_ARG;
+    const ntc::NHooks &nh = ntc::g_n_hooks;
+    if (n_mode && (!nh.set_mode || !nh.encode_names)) return NTC_ERR_UNSUPPORTED;
+    ntc_n_stats NS{};
     const bool keep = policy == NTC_NX_KEEP;
     ntc_nx_stats NX{};
     uint32_t nx_sub = 0;
@@ -289,6 +300,19 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             for (int i = 0; i < n; i++) ntc::g_q_hooks.set_mode(ctxs[i], 0);
         }
     } mode_reset{ctxs, q_mode ? n_ctx : 0};
+    if (n_mode)
+        for (int i = 0; i < n_ctx; i++)
+            if (int r = nh.set_mode(ctxs[i], n_mode)) {
+                for (int j = 0; j < i; j++) nh.set_mode(ctxs[j], 0);
+                return r;
+            }
+    struct NamesReset {  // ... and with names dropped
+        ntc_ctx *const *ctxs;
+        int n;
+        ~NamesReset() {
+            for (int i = 0; i < n; i++) ntc::g_n_hooks.set_mode(ctxs[i], 0);
+        }
+    } names_reset{ctxs, n_mode ? n_ctx : 0};
     ntc_pipeline_opts o{};
     if (opts) o = *opts;
     const int T = o.threads > 0 ? o.threads : ntc_host_threads();
@@ -344,8 +368,8 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         std::shared_ptr<uint8_t> payload;  // the GPU call's host payload (ntc_buffer_free)
         ntc_block_meta meta;
         uint64_t block;
-        int stream;                        // 0..3, or 4 = the block's quality section
-        std::shared_ptr<uint8_t> qpayload = nullptr;  // the call's packed quality words
+        int stream;                        // 0..3, 4 = the block's quality section, 5 = its name section
+        std::shared_ptr<uint8_t> qpayload = nullptr;  // the call's packed quality words (4), name sections (5)
     };
     std::deque<Task> tasks;
     std::map<uint64_t, BlockOut> done;
@@ -382,6 +406,11 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         sh.fail(NTC_ERR_UNSUPPORTED, "qualities: host_parse = 1 parses on the host, which drops the quality lines");
     else if (q_mode && !text && !streamed)
         sh.fail(NTC_ERR_UNSUPPORTED, "qualities: the input is not FASTQ (FASTA has no quality lines)");
+    // ... and so do names (DESIGN.md "Read names")
+    if (n_mode && o.host_parse)
+        sh.fail(NTC_ERR_UNSUPPORTED, "names: host_parse = 1 parses on the host, which drops the header lines");
+    else if (n_mode && !text && !streamed)
+        sh.fail(NTC_ERR_UNSUPPORTED, "names: the input is not FASTQ (names are kept from FASTQ text only)");
     uint64_t text_pos = 0;
     const uint8_t *carry_p = nullptr;
     uint64_t carry_n = 0;
@@ -555,6 +584,12 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                             (int64_t)next_read);
                     break;
                 }
+                if (n_mode) {
+                    sh.fail(NTC_ERR_UNSUPPORTED, "names: a blank line, or records that are not four lines each: "
+                                                 "this batch needs the host parser, which drops the header lines",
+                            (int64_t)next_read);
+                    break;
+                }
                 as_text = false;  // the host parser goes on from the first record not sent
                 if (streamed) {
                     ntc::fastx_stream_unread(fx, carry_p, carry_n);
@@ -682,7 +717,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 add_time(t_gpu, secs(tg, Clock::now()));
                 if (r) {
                     ntc_buffer_free(payload);
-                    if (b.is_text && r == NTC_ERR_FORMAT && !q_mode)  // as the host parser reports it
+                    if (b.is_text && r == NTC_ERR_FORMAT && !q_mode && !n_mode)  // as the host parser reports it
                         sh.fail(r, "FASTX input: malformed or unreadable");
                     else
                         sh.fail(r, std::string("encode: ") + ntc_last_error(ctxs[c]),
@@ -726,6 +761,25 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         return;
                     }
                 }
+                // ... and its name sections (mode keep / id), one per block
+                std::vector<ntc_name_meta> nmetas;
+                std::shared_ptr<uint8_t> npl;
+                if (n_mode) {
+                    uint64_t nn = 0, nbytes = 0;
+                    int rn = nh.encode_names(ctxs[c], nullptr, 0, nullptr, 0, &nn, &nbytes);
+                    if (rn == NTC_ERR_CAPACITY && nn == nblk) {
+                        nmetas.resize(nn);
+                        npl.reset((uint8_t *)std::malloc(nbytes ? nbytes : 1), std::free);
+                        rn = npl ? nh.encode_names(ctxs[c], nmetas.data(), nn, npl.get(), nbytes, &nn, &nbytes)
+                                 : NTC_ERR_CAPACITY;
+                    } else if (rn == NTC_OK || rn == NTC_ERR_CAPACITY) {
+                        rn = NTC_ERR_FORMAT;  // (never expected: a section per block)
+                    }
+                    if (rn) {
+                        sh.fail(rn, std::string("encode: names: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                }
                 etrace("gpu done, first block", b.first_block);
                 std::lock_guard<std::mutex> g(sh.mu);
                 S.gpu_done_s = secs(t0, Clock::now());
@@ -749,6 +803,12 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         bo.qmeta = qmetas[k];
                         bo.left++;
                         tasks.push_back(Task{pl, metas[k], b.first_block + k, 4, qpl});
+                    }
+                    if (n_mode && ok) {
+                        bo.has_n = true;
+                        bo.nmeta = nmetas[k];
+                        bo.left++;
+                        tasks.push_back(Task{pl, metas[k], b.first_block + k, 5, npl});
                     }
                     int order[4] = {0, 1, 2, 3};
                     std::sort(order, order + 4, [&](int x, int y) {
@@ -790,6 +850,17 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         sh.fail(r, "qualities: deflate failed");
                         return;
                     }
+                } else if (status == NTC_OK && task.stream == 5) {
+                    ntc_name_meta nm;
+                    {
+                        std::lock_guard<std::mutex> g(sh.mu);
+                        nm = done[task.block].nmeta;
+                    }
+                    const int r = ntc_n_deflate_section(&nm, task.qpayload.get() + nm.payload_off, engine, &data, &len);
+                    if (r) {
+                        sh.fail(r, "names: deflate failed");
+                        return;
+                    }
                 } else if (status == NTC_OK) {
                     const int r = ntc_deflate_stream(&task.meta, task.stream, task.payload.get(), engine, &data, &len);
                     if (r) {
@@ -808,6 +879,9 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 if (task.stream == 4) {
                     bo.qsec = data;
                     bo.qlen = len;
+                } else if (task.stream == 5) {
+                    bo.nsec = data;
+                    bo.nlen = len;
                 } else {
                     bo.part[task.stream] = data;
                     bo.len[task.stream] = len;
@@ -834,9 +908,9 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     // counted over the reads of the blocks written so far (what decode will print as seq.N - 1)
     if (keep && ntc_nx_write(nx_fd, nullptr, 0, nx_sub, 1)) sh.fail(NTC_ERR_IO, "exceptions: write failed");
     // the quality file: its header, then the section of every block written, in file order
-    auto write_q = [&](const uint8_t *p, uint64_t n) -> bool {
+    auto write_q = [&](const uint8_t *p, uint64_t n, int fd) -> bool {
         while (n) {
-            const ssize_t w = ::write(q_fd, p, n);
+            const ssize_t w = ::write(fd, p, n);
             if (w < 0 && errno == EINTR) continue;
             if (w <= 0) return false;
             p += w;
@@ -845,6 +919,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         return true;
     };
     if (q_mode && ntc_q_write_header(q_fd, q_mode)) sh.fail(NTC_ERR_IO, "qualities: write failed");
+    if (n_mode && ntc_n_write_header(n_fd, n_mode)) sh.fail(NTC_ERR_IO, "names: write failed");
     uint64_t reads_written = 0;
     for (uint64_t blk = 0;; blk++) {
         BlockOut out;
@@ -881,11 +956,19 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             }
             reads_written += out.n_reads;
             if (out.has_q) {
-                if (!write_q(out.qsec, out.qlen)) sh.fail(NTC_ERR_IO, "qualities: write failed");
+                if (!write_q(out.qsec, out.qlen, q_fd)) sh.fail(NTC_ERR_IO, "qualities: write failed");
                 QS.sections++;
                 QS.quals += out.qmeta.n_quals;
                 QS.packed_bytes += out.qmeta.payload_bytes;
                 QS.deflated_bytes += out.qlen - 24 - out.qmeta.n_syms;
+            }
+            if (out.has_n) {
+                if (!write_q(out.nsec, out.nlen, n_fd)) sh.fail(NTC_ERR_IO, "names: write failed");
+                NS.sections++;
+                NS.names += out.nmeta.n_reads;
+                NS.name_bytes += out.nmeta.name_bytes;
+                NS.payload_bytes += out.nmeta.payload_bytes;
+                NS.deflated_bytes += out.nlen - 32;
             }
         } else {
             S.dropped_blocks++;
@@ -893,6 +976,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         }
         for (int q = 0; q < 4; q++) ntc_buffer_free(out.part[q]);
         ntc_buffer_free(out.qsec);
+        ntc_buffer_free(out.nsec);
         add_time(t_write, secs(tw, Clock::now()));
         etrace("written block", blk);
     }
@@ -911,6 +995,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     for (auto &kv : done) {
         for (int q = 0; q < 4; q++) ntc_buffer_free(kv.second.part[q]);
         ntc_buffer_free(kv.second.qsec);
+        ntc_buffer_free(kv.second.nsec);
     }
     for (auto &b : ring) {
         pinned_free(b.bases);
@@ -934,6 +1019,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     if (stats) *stats = S;
     if (nx) *nx = NX;
     if (qs) *qs = QS;
+    if (ns) *ns = NS;
     return result;
 }
 
@@ -953,6 +1039,14 @@ int ntc_encode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int
     if (!fo || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
     return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
                             fo->q_fd, q);
+}
+
+int ntc_encode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts2 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts2) || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
+    return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
+                            fo->q_fd, q, fo->n_mode, fo->n_fd, n);
 }
 
 }  // extern "C"
@@ -1044,7 +1138,8 @@ extern "C" {
 // nx_path: ntc_decode_file_nx's side file (null: none)
 // q_path: ntc_decode_file_ex's quality file (null: none; the output is then FASTA)
 static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
-                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, const char *q_path = nullptr) {
+                            const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, const char *q_path = nullptr,
+                            const char *n_path = nullptr) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
@@ -1099,6 +1194,45 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         for (auto &m : tmp) m.payload_off -= base;
         const uint64_t bytes = tmp.back().payload_off + tmp.back().payload_bytes;
         return ntc::g_q_hooks.decode_set_qualities(ctx, tmp.data(), n, qf.payload + base, bytes);
+    };
+    // the name sections, likewise
+    struct NFile {
+        ntc_name_meta *metas = nullptr;
+        uint64_t n = 0, bytes = 0;
+        uint8_t *payload = nullptr;
+        int mode = 0;
+        ~NFile() {
+            ntc_buffer_free(metas);
+            ntc_buffer_free(payload);
+        }
+    } nf;
+    if (n_path) {
+        if (!ntc::g_n_hooks.decode_set_names) return NTC_ERR_UNSUPPORTED;
+        if (const int r = ntc_n_read(n_path, &nf.mode, &nf.metas, &nf.n, &nf.payload, &nf.bytes)) {
+            if (stats) {
+                std::memset(stats, 0, sizeof(*stats));
+                stats->bad_read = -1;
+                std::snprintf(stats->error, sizeof(stats->error), "names: %s",
+                              r == NTC_ERR_IO ? "cannot read the side file" : "malformed side file");
+            }
+            return r;
+        }
+    }
+    // hands ctx the name sections of blocks [first, first + n); *bytes = their names' bytes
+    auto put_names = [&](ntc_ctx *ctx, uint64_t first, uint64_t n, std::vector<ntc_name_meta> &tmp) -> int {
+        if (!n_path || n == 0) return NTC_OK;
+        if (first + n > nf.n) return NTC_ERR_FORMAT;
+        tmp.assign(nf.metas + first, nf.metas + first + n);
+        const uint64_t base = tmp[0].payload_off;
+        for (auto &m : tmp) m.payload_off -= base;
+        const uint64_t bytes = tmp.back().payload_off + tmp.back().payload_bytes;
+        return ntc::g_n_hooks.decode_set_names(ctx, tmp.data(), n, nf.payload + base, bytes);
+    };
+    // the names' bytes of blocks [first, first + n) (those the side file has): room in the text
+    auto name_room = [&](uint64_t first, uint64_t n) -> uint64_t {
+        uint64_t bytes = 0;
+        for (uint64_t k = first; n_path && k < first + n && k < nf.n; k++) bytes += nf.metas[k].name_bytes;
+        return bytes;
     };
     const uint64_t q_per_base = q_path ? 1 : 0, q_per_read = q_path ? 3 : 0;  // FASTQ: "+\n", qualities, "\n" more
     // hands ctx the runs of reads [first, first + n) (file numbering), read relative to first
@@ -1296,6 +1430,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             }
             std::vector<ntc_nx_run> nx_tmp;  // a batch's exception runs, renumbered from its first read
             std::vector<ntc_qual_meta> q_tmp;  // ... and its quality sections
+            std::vector<ntc_name_meta> n_tmp;  // ... and its name sections
             for (uint64_t b = (uint64_t)c;; b += (uint64_t)n_ctx) {
                 DSlot *slp;
                 if (gpu_unpack) {
@@ -1336,7 +1471,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         if (sh.error != NTC_OK) return;
                     }
                     const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
-                                          digits_total(sl.first_id, sl.n_reads) + 64;
+                                          digits_total(sl.first_id, sl.n_reads) + name_room(sl.first_block, nb) + 64;
                     const auto tf = Clock::now();
                     if (!ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
                         sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
@@ -1350,6 +1485,12 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     if (const int rx = put_quals(ctxs[c], sl.first_block, nb, q_tmp)) {
                         sh.fail(rx, rx == NTC_ERR_FORMAT ? "qualities: fewer sections than blocks, or a section that "
                                                            "does not fit its block"
+                                                         : std::string("decode: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                    if (const int rx = put_names(ctxs[c], sl.first_block, nb, n_tmp)) {
+                        sh.fail(rx, rx == NTC_ERR_FORMAT ? "names: fewer sections than blocks, or a section that does "
+                                                           "not fit its block"
                                                          : std::string("decode: ") + ntc_last_error(ctxs[c]));
                         return;
                     }
@@ -1379,7 +1520,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 DSlot &sl = *slp;
                 const uint64_t nrec = sl.n_recs;
                 const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
-                                      digits_total(sl.first_id, sl.n_reads) + 64;
+                                      digits_total(sl.first_id, sl.n_reads) + name_room(sl.first_block, sl.n_blocks) + 64;
                 const auto tg = Clock::now();
                 if (!ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
                     sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
@@ -1394,6 +1535,13 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                                              sl.bad_block >= 0 ? (uint64_t)sl.bad_block : sl.n_blocks, q_tmp)) {
                     sh.fail(rx, rx == NTC_ERR_FORMAT ? "qualities: fewer sections than blocks, or a section that "
                                                        "does not fit its block"
+                                                     : std::string("decode: ") + ntc_last_error(ctxs[c]));
+                    return;
+                }
+                if (const int rx = put_names(ctxs[c], sl.first_block,
+                                             sl.bad_block >= 0 ? (uint64_t)sl.bad_block : sl.n_blocks, n_tmp)) {
+                    sh.fail(rx, rx == NTC_ERR_FORMAT ? "names: fewer sections than blocks, or a section that does "
+                                                       "not fit its block"
                                                      : std::string("decode: ") + ntc_last_error(ctxs[c]));
                     return;
                 }
@@ -1620,6 +1768,10 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         result = NTC_ERR_FORMAT;
         sh.msg = "qualities: more sections than blocks (the side file belongs to another encoding)";
     }
+    if (result == NTC_OK && stop_batch < 0 && clean_end && n_path && nf.n != blocks.size()) {
+        result = NTC_ERR_FORMAT;
+        sh.msg = "names: more sections than blocks (the side file belongs to another encoding)";
+    }
     S.dropped_blocks = blocks.size() - S.blocks;  // after a damaged block (or none)
     S.alloc_s += t_pin.load();
     S.parse_s = t_unzip.load();
@@ -1651,6 +1803,12 @@ int ntc_decode_file_ex(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int
                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
     if (!fo) return NTC_ERR_INVALID_ARG;
     return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path);
+}
+
+int ntc_decode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts2 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts2)) return NTC_ERR_INVALID_ARG;
+    return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path, fo->n_path);
 }
 
 }  // extern "C"
