@@ -115,6 +115,9 @@ struct ntc_ctx {
     int joint_opt = -1;      // joint path runs at the next upload: -1 auto (fragmented path cover), 0 off, 1 on
     int path_link_opt = path_link_on() ? 1 : 0;  // path cover: unitigs linked across branches (default) or not
     int win_opt = -1;        // SCAN window words at the next upload: -1 auto (U >= 4), 0 off, 1 on
+    int subst_opt = subst_on() ? -1 : 0;  // substitution words at the next upload: -1 auto (the build without
+                                          // joint runs, path positions in the table, U >= 4), 0 zeroed
+    int subst_built = 0;     // the index in use carries substitution words
     int decode_only_opt = 0;  // the next upload builds only what decode needs (walk table): no path
                               // cover, suffix table or SCAN words; encode calls then fail
     bool index_decode_only = false;  // the index in use was uploaded that way
@@ -1350,6 +1353,7 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
         ctx->n_paths = 0;
         ctx->path_text_len = 0;
         ctx->index_decode_only = true;
+        ctx->subst_built = 0;
         ctx->has_index = true;
         mark("done (decode only)", false);
         ctx->upload_total_us = us_since();
@@ -1435,6 +1439,16 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
         launch_pair_words((const uint2 *)d_tab + tab_base(U), U, (uint16_t *)d_pair, ctx->stream);
         d.pair_w = (const uint16_t *)d_pair;
     }
+    // substitution words (encode_core.h subst_clean), the fourth word of each path-stream
+    // group: k_ms4 without joint runs skips the SCAN after a run break at a set bit
+    ctx->subst_built = 0;
+    if (has_paths) {
+        mark("SCAN words", true);
+        const bool on = ctx->subst_opt != 0 && !d.joint && d.tab_pos && U >= 4;
+        launch_subst_words(d, (uint4 *)d_pstream, pstream_groups(tlen, hx.k), on, ctx->stream);
+        ctx->subst_built = on ? 1 : 0;
+        mark("substitution words", true);
+    }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->n_paths = n_paths;
@@ -1479,6 +1493,11 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
     if (std::strcmp(key, "win") == 0) {  // applies to the next ntc_index_upload
         if (value < -1 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "win must be -1 (auto), 0 or 1");
         ctx->win_opt = (int)value;
+        return NTC_OK;
+    }
+    if (std::strcmp(key, "subst") == 0) {  // applies to the next ntc_index_upload
+        if (value < -1 || value > 0) return set_err(ctx, NTC_ERR_INVALID_ARG, "subst must be -1 (auto) or 0");
+        ctx->subst_opt = (int)value;
         return NTC_OK;
     }
     if (std::strcmp(key, "decode_only") == 0) {  // applies to the next ntc_index_upload
@@ -1563,6 +1582,15 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "joint") == 0) *value = ctx->has_index ? (int64_t)ctx->dix.joint : ctx->joint_opt;
     else if (std::strcmp(key, "win") == 0) *value = ctx->has_index ? (ctx->dix.win_w != nullptr) : ctx->win_opt;
     else if (std::strcmp(key, "path_link") == 0) *value = ctx->path_link_opt;
+    else if (std::strcmp(key, "subst") == 0) *value = ctx->has_index ? ctx->subst_built : ctx->subst_opt;
+    else if (std::strcmp(key, "subst_hash") == 0) {  // test hook: derived.h subst_word_hash of the device words
+        if (!ctx->has_index || !ctx->dix.has_paths) return NTC_ERR_NO_INDEX;
+        std::vector<uint4> ps(pstream_groups(ctx->path_text_len, ctx->dix.k));
+        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+            hipMemcpy(ps.data(), ctx->dix.pstream, ps.size() * 16, hipMemcpyDeviceToHost) != hipSuccess)
+            return NTC_ERR_HIP;
+        *value = (int64_t)subst_word_hash(ps.data(), ps.size());
+    }
     else if (std::strcmp(key, "filter_density_ppm") == 0) *value = ctx->filter_density_ppm;
     else if (std::strcmp(key, "n_paths") == 0) *value = (int64_t)ctx->n_paths;
     else if (std::strcmp(key, "path_text_len") == 0) *value = (int64_t)ctx->path_text_len;

@@ -156,6 +156,22 @@ void build_tab_host(const DevIndex &d, uint32_t U, std::vector<uint2> &tab, std:
     level_bits(tab, U, bits);
     fbits.clear();
     if (filter_level(U)) level_bits(tab, filter_level(U), fbits);
+    // substitution words (encode_core.h subst_clean; kernels.hip k_subst_words on the device):
+    // the fourth word of each path-stream group, from the table just built
+    if (d.has_paths && d.pstream) {
+        DevIndex dd = d;
+        dd.tab = tab.data();
+        dd.tab_bits = bits.data();
+        dd.tab_u = U;
+        const bool on = subst_on() && !d.joint;
+        uint4 *ps = const_cast<uint4 *>(d.pstream);  // the host cover's own array (host_dev_index)
+        const uint64_t groups = pstream_groups(d.path_len, d.k);
+        for (uint64_t g = 0; g < groups; g++) {
+            uint32_t w = 0;
+            for (uint32_t i = 0; on && i < 32; i++) w |= subst_clean(dd, 32 * g + i) << i;
+            ps[g].w = w;
+        }
+    }
 }
 
 namespace {
@@ -218,6 +234,11 @@ void fork_words(const HostIndex &ix, const Derived &dv, const std::vector<uint8_
         const uint32_t y = dv.C[c] + host_rank(dv, c, h);
         if (!dummy[y]) w[c] = dv.pos_of_node[y];
     }
+}
+
+bool subst_on() {
+    const char *e = std::getenv("NTC_SUBST");
+    return !(e && std::atoi(e) == 0);
 }
 
 bool path_link_on() {

@@ -36,8 +36,13 @@ void build_paths(const HostIndex &ix, Derived &dv);
 // the path cover links unitigs across branches (derived.cpp link_unitigs) unless
 // NTC_PATH_LINK=0; the upload's default for ctx option "path_link"
 bool path_link_on();
+// the substitution words (encode_core.h subst_clean) are built unless NTC_SUBST=0; the
+// upload's default for ctx option "subst"
+bool subst_on();
 // FNV-1a over the path-cover arrays (pstream, colex_at, pos_of_node, puniq) at the sizes
 // build_paths gives them: lets a test compare the device-built cover with the host one.
+// The fourth word of each path-stream group (the substitution word) is left out: it depends
+// on the suffix-table depth, not on the cover (subst_word_hash covers it).
 inline uint64_t path_cover_hash(const uint4 *pstream, const uint32_t *colex_at, const uint32_t *pos_of_node,
                                 const uint64_t *puniq, uint64_t n, uint32_t k, uint64_t tlen) {
     uint64_t h = 1469598103934665603ULL;
@@ -45,10 +50,17 @@ inline uint64_t path_cover_hash(const uint4 *pstream, const uint32_t *colex_at, 
         const uint8_t *b = (const uint8_t *)p;
         for (uint64_t i = 0; i < bytes; i++) h = (h ^ b[i]) * 1099511628211ULL;
     };
-    mix(pstream, ((tlen + k) / 32 + 8) * 16);
+    for (uint64_t g = 0; g < pstream_groups(tlen, k); g++) mix(pstream + g, 12);
     mix(colex_at, (tlen + 8) * 4);
     mix(pos_of_node, n * 4);
     mix(puniq, (tlen / 64 + 4) * 8);
+    return h;
+}
+// FNV-1a over the substitution words alone (the fourth word of each group)
+inline uint64_t subst_word_hash(const uint4 *pstream, uint64_t groups) {
+    uint64_t h = 1469598103934665603ULL;
+    for (uint64_t g = 0; g < groups; g++)
+        for (uint32_t i = 0; i < 4; i++) h = (h ^ ((pstream[g].w >> (8 * i)) & 0xFFu)) * 1099511628211ULL;
     return h;
 }
 // dummy[z] = 1 when node z's k-mer contains '$' (BFS from the root, depth < k).
@@ -56,7 +68,8 @@ std::vector<uint8_t> dummy_nodes(const HostIndex &ix, const Derived &dv);
 // Suffix-table depth U for an index of n nodes (encode_core.h "Suffix table").
 uint32_t default_tab_u(uint64_t n, uint32_t k, const uint8_t *lcs = nullptr);
 // Host build of the suffix table levels 1..U (test emulation; the GPU builds it on device).
-// (bits: presence of level U; fbits: presence of the filter level, or empty).
+// (bits: presence of level U; fbits: presence of the filter level, or empty).  Also writes
+// the substitution words into the path stream d points at (zeroes with joint runs or NTC_SUBST=0).
 void build_tab_host(const DevIndex &d, uint32_t U, std::vector<uint2> &tab, std::vector<uint32_t> &bits,
                     std::vector<uint32_t> &fbits);
 // Level of the SCAN pre-filter bitmap for depth U (0 = none).

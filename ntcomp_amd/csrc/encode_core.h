@@ -205,6 +205,16 @@ NTC_HD uint4 ld4(const uint4 *p) {
 #endif
     return *p;
 }
+// all four words of a path-stream group in one 16-byte request (a uint4 whose fourth word is
+// used apart from the others is otherwise fetched as 12 + 4 bytes: two instructions per group)
+NTC_HD uint4 ld4_whole(const uint4 *p) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const u32x4_t v = *reinterpret_cast<const u32x4_t *>(p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+#else
+    return *p;
+#endif
+}
 // a load with no reuse (suffix-table entries: 2.9 GB, random): streaming hint, so that it
 // does not push the L2-resident filter bitmap out
 NTC_HD uint2 load2_stream(const uint2 *p) {
@@ -581,6 +591,49 @@ NTC_HD uint2 tab_make(const DevIndex &ix, uint32_t u, uint64_t key, const uint2 
     const uint2 suf = prev[key >> 2];
     return tab_long(suf) ? mk2(suf.x, kTabShort | (u - 1)) : suf;
 }
+
+// Substitution word: the fourth word of each path-stream group, bit i for text position
+// t = 32 g + i, built at upload (kernels.hip k_subst_words; derived.cpp build_tab_host).
+// clean(t) = 1 says: a read that equals the path text on the U - 1 characters before t,
+// carries any of the three other bases at t and equals the text again on t + 1 .. t + U + 1
+// has, at the U positions from the break on, a short break position, no two consecutive long
+// positions and a short last one, and the U-mer text[t+1 .. t+U] is one node whose top-level
+// table entry carries its path position.  The SCAN after such a run break can only find the
+// pair (t + U, t + U + 1) and enter the path again at the node whose k-mer ends at t + U, so
+// MsLaneT<false>::step enters there without any SCAN load.  The U-mers that hold the replaced
+// character depend on the text and on the base alone: all three bases are tested here.
+//  * one path's text covers the window: a node's k-mer ends at every t' in [t-1, t+U+1];
+//  * per base a != text[t], P_a(i) = presence of the U-mer ending at t + i of the text with
+//    a at t (i = 0 .. U-1): P_a(0) = 0, P_a(U-1) = 0, no P_a(i) = P_a(i+1) = 1;
+//  * the entry of text[t+1 .. t+U] is kTabPos | (t + U + 1 - k), the node ending at t + U;
+//  * the table carries path positions (tab_pos) and U >= 4.
+NTC_HD uint32_t subst_clean(const DevIndex &ix, uint64_t t) {
+    const uint32_t U = ix.tab_u, k = ix.k;
+    if (!ix.tab_pos || U < 4 || t < k || t + U + 2 > ix.path_len) return 0u;
+    uint64_t win, ec;
+    uint32_t ends, e2;
+    path_text32(ix.pstream, t - 1, ec, ends);
+    const uint32_t need = (1u << (U + 3)) - 1u;  // k-mer ends at t - 1 .. t + U + 1
+    if ((ends & need) != need) return 0u;
+    path_text32(ix.pstream, t + 1 - U, win, e2);  // text[t-U+1 .. t+U] in the low 4 U bits (U <= 15)
+    const uint64_t mask = (1ULL << (2 * U)) - 1;
+    const uint2 e = ix.tab[tab_base(U) + ((win >> (2 * U)) & mask)];
+    if (!tab_long(e) || !(e.y & kTabPos) || (e.y & ~kTabPos) != (uint32_t)(t + U + 1 - k)) return 0u;
+    const uint32_t own = (uint32_t)(win >> (2 * (U - 1))) & 3u;
+    for (uint32_t a = 0; a < 4; a++) {
+        if (a == own) continue;
+        const uint64_t s = (win & ~(3ULL << (2 * (U - 1)))) | ((uint64_t)a << (2 * (U - 1)));
+        uint32_t P = 0;
+        for (uint32_t i = 0; i < U; i++) {
+            const uint64_t key = (s >> (2 * i)) & mask;
+            P |= ((ix.tab_bits[key >> 5] >> (key & 31)) & 1u) << i;
+        }
+        if ((P & 1u) || ((P >> (U - 1)) & 1u) || (P & (P >> 1))) return 0u;
+    }
+    return 1u;
+}
+// groups of the path stream (sizes as derived.cpp build_paths)
+NTC_HD uint64_t pstream_groups(uint64_t tlen, uint32_t k) { return (tlen + k) / 32 + 8; }
 
 // ======================================================================================
 // shared by the flattened encoders
@@ -1358,7 +1411,11 @@ struct MsLaneT {
             // position of the last node it covered on each side, vfy >> 8 = 4 + the read's
             // character c at p (see the stop below)
             uint32_t hopc = kJoint ? vfy >> 8 : 0u;
-            bool nohop = false;
+            // (non-joint build) this run verifies an UNCONFIRMED guess, entered at a run break
+            // from the substitution word alone: bit 8, and the d the lane had at the break above
+            // it (see the shortcut below); gj / ge still hold that break
+            const uint32_t unc = kJoint ? 0u : vfy >> 8;
+            bool nohop = false, sub = false;
             vfy = 0;
             for (;;) {
                 // 64 path characters after node j's k-mer (from pre characters before its end
@@ -1369,8 +1426,14 @@ struct MsLaneT {
                 NTC_TOUCH(kTrPst, ix.pstream + (T >> 5) + 2);
                 NTC_TOUCH(kTrQ, Q + ((qo + p + m - pre) >> 5));
                 NTC_TOUCH(kTrQ, Q + ((qo + p + m - pre) >> 5) + 2);
-                const uint4 g0 = ld4<4>(ix.pstream + (T >> 5)), g1 = ld4<4>(ix.pstream + (T >> 5) + 1),
-                            g2 = ld4<4>(ix.pstream + (T >> 5) + 2);
+                // (non-joint build) the substitution words come with the text: whole 16-byte groups.
+                // Left to the compiler the fourth word is a load of its own per group, which costs
+                // the build 3 % with the words zeroed; re-reading the break's word after the loop
+                // instead measured the same with the words on and 1 % slower with them zeroed.
+                constexpr bool kCarry = !kJoint;
+                const uint4 g0 = kCarry ? ld4_whole(ix.pstream + (T >> 5)) : ld4<4>(ix.pstream + (T >> 5)),
+                            g1 = kCarry ? ld4_whole(ix.pstream + (T >> 5) + 1) : ld4<4>(ix.pstream + (T >> 5) + 1),
+                            g2 = kCarry ? ld4_whole(ix.pstream + (T >> 5) + 2) : ld4<4>(ix.pstream + (T >> 5) + 2);
                 // a hop loads the fork block entry of c with the path text: one round trip
                 uint4 ex = make_uint4(0, 0, 0, 0);
                 if (kJoint && (hopc & 8u)) {
@@ -1441,6 +1504,14 @@ struct MsLaneT {
                 const uint32_t ib = ~vb ? (uint32_t)__builtin_ctz(~vb) : 32u;
                 if (ib < lb) lb = ib;
                 uint32_t lim = la == 32 ? 32 + lb : la;
+                if constexpr (kCarry) {
+                    // the substitution bit (subst_clean) of the text position the run stops at: the
+                    // groups' fourth words, shifted as the k-mer end bits are.  A set bit has its
+                    // end bit set, so the stop is a character mismatch (or the read's end, below)
+                    const uint32_t sa = sh ? ((g0.w >> sh) | (g1.w << (32 - sh))) : g0.w;
+                    const uint32_t sb = sh ? ((g1.w >> sh) | (g2.w << (32 - sh))) : g1.w;
+                    sub = lim < 64 && ((lim < 32 ? sa >> lim : sb >> (lim - 32)) & 1u);
+                }
                 const uint32_t lx = lim;
                 const bool xend = la < 32 ? la == ia : lb < 32 && lb == ib;  // x's stop (at lx) is a path end
                 uint32_t ny = nx, ly = 64;
@@ -1569,6 +1640,18 @@ struct MsLaneT {
                 m = 0;  // on into the EXT block below, in this same call
                 nohop = false;
             }
+            if (!kJoint && unc && m == 0) {
+                // The unconfirmed guess failed (its U characters, or the character after them):
+                // the pair it assumed was never established, so neither the table entry of its
+                // node (kModeEnter) nor the "long p" break check applies.  Back to the break at
+                // ge with the lane as the run left it, and on with the ordinary SCAN there.
+                NTC_STAT(14);
+                j = gj;
+                p = ge;
+                d = (unc >> 1) & 0xFFu;
+                window(b, p + 1 - U);
+                mode = kModeBrk;
+            }
             if (m > 0 || nohop) {
                 if (m > 0) {
                     put_entry(b, p, j + 1, m, (d + 1 < k ? d + 1 : k) | kRunTag);
@@ -1586,6 +1669,29 @@ struct MsLaneT {
                     NTC_STAT(((ix.rank[(uint64_t)c * ix.rwords + (v >> 5)].y >> (v & 31)) & 1u) ? 11 : 12);
                 }
 #endif
+                if constexpr (!kJoint) {
+                    // Substitution shortcut (subst_clean): the run stopped on a mismatch at a clean
+                    // text position with the read equal to the path on the U - 1 characters before
+                    // it (d >= U - 1).  If the read also equals the path on the U + 1 characters
+                    // after it, its U-mers at p .. p + U - 1 are the ones the bit was computed from:
+                    // the SCAN would find p short, no pair before p + U, the pair (p + U, p + U + 1)
+                    // and the single node at path position gj + U + 1.  So enter that state now, as
+                    // the guess below does for x = ge + U, but UNCONFIRMED: the run verifies the U
+                    // characters and must go on by at least one (the pair's second position), else
+                    // the lane returns to this break (above).  No window or pair word is loaded.
+                    if (sub && d + 1 >= U && p + U + 1 < len) {
+                        NTC_STAT(13);
+                        vfy = U | (1u << 8) | (d << 9);
+                        j = gj + U + 1;
+                        jy() = 0xFFFFFFFFu;
+                        p = ge + U + 1;
+                        d = U;
+                        hi = kScanW;
+                        try_run = true;
+                        mode = kModeBrk;
+                        return 0;
+                    }
+                }
                 // the run broke at p (mostly a sequencing error): table first
                 window(b, p + 1 - U);
                 mode = kModeBrk;

@@ -985,6 +985,20 @@ void launch_win_words(const uint32_t *bits, uint32_t U, uint32_t *out, hipStream
     hipLaunchKernelGGL(k_win_words, grid_for(win_words_count(U) * 8), dim3(256), 0, s, bits, U, out);
 }
 
+// substitution words (encode_core.h subst_clean): one lane per path text position, one lane
+// per 32 positions stores the ballot as the fourth word of its group (on = 0: zeroes).  Other
+// lanes read the first three words of the same groups meanwhile, never the fourth.
+__global__ __launch_bounds__(256) void k_subst_words(DevIndex ix, uint4 *pstream, uint64_t groups, uint32_t on) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t c = on && t < 32 * groups ? subst_clean(ix, t) : 0u;
+    const uint64_t m = __ballot(c != 0);
+    if ((threadIdx.x & 31) == 0 && (t >> 5) < groups) pstream[t >> 5].w = (uint32_t)(m >> (threadIdx.x & 32));
+}
+
+void launch_subst_words(const DevIndex &ix, uint4 *pstream, uint64_t groups, bool on, hipStream_t s) {
+    hipLaunchKernelGGL(k_subst_words, grid_for(32 * groups), dim3(256), 0, s, ix, pstream, groups, on ? 1u : 0u);
+}
+
 void launch_tab_build(const DevIndex &ix, uint32_t U, uint2 *tab, uint32_t *bits, uint32_t F, uint32_t *fbits,
                       hipStream_t s) {
     for (uint32_t u = 1; u <= U; u++) {

@@ -72,6 +72,9 @@ def main():
     if args.order == "minimizer":
         reads = reads.reshape(args.reads, args.read_len)[minimizer_order(reads, args.reads, args.read_len)].ravel()
     os.environ["NTC_TRACE_GROUP"] = str(args.group)
+    # the k_ms4 build the upload's auto picks: joint runs for a collection of strains (a
+    # fragmented path cover), none for one genome -- the build the substitution words feed
+    os.environ.setdefault("NTC_EMU_JOINT", "1" if args.strains else "0")
     offs = np.arange(0, args.reads * args.read_len + 1, args.read_len, dtype=np.uint64)
     recs, _ = emu_lib.emu_encode(ix.n, args.k, ix.rows, ix.C, ix.lcs, reads, offs, tab_u=args.tab_u)
     K = len(KINDS)
