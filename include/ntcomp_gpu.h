@@ -122,6 +122,11 @@ int ntc_ctx_synchronize(ntc_ctx *ctx);
  * "path_hash" (test hook: FNV-1a of the cover arrays, derived.h path_cover_hash; the path
  * stream's substitution words are left out of it), "subst_hash" (test hook: FNV-1a of those
  * words alone, derived.h subst_word_hash),
+ * "dev_walk", "dev_rank2", "dev_tab", "dev_tab_bits", "dev_filt_bits", "dev_pair_w",
+ * "dev_win_w" (test hooks: the device address of that derived array of the uploaded index,
+ * or 0 where the upload did not build it -- "dev_filt_bits" is the allocated bitmap also
+ * when the auto rule switched the filter off; NTC_ERR_NO_INDEX without an index; tests copy
+ * the arrays with ntc_memcpy_d2h at the sizes encode_core.h gives them),
  * "tab_u" (after an upload: the depth in use), "tab_u_fallback" (1: the default depth 15
  * did not fit in free HBM, 14 was used), "pack_us" (last GPU block packer call, both
  * kernels), "upload_host_us" / "upload_total_us"

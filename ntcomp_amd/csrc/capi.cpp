@@ -1608,6 +1608,22 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
             return NTC_ERR_HIP;
         *value = (int64_t)path_cover_hash(ps.data(), ca.data(), pn.data(), pu.data(), n, (uint32_t)k, tlen);
     }
+    else if (std::strncmp(key, "dev_", 4) == 0) {  // test hooks: device address of a derived array, 0 = not built
+        const DevIndex &d = ctx->dix;
+        const void *p;
+        if (std::strcmp(key, "dev_walk") == 0) p = d.walk;
+        else if (std::strcmp(key, "dev_rank2") == 0) p = d.rank2;
+        else if (std::strcmp(key, "dev_tab") == 0) p = d.tab;
+        else if (std::strcmp(key, "dev_tab_bits") == 0) p = d.tab_bits;
+        else if (std::strcmp(key, "dev_filt_bits") == 0) p = d.filt_bits;  // allocated also when filt_f = 0
+        else if (std::strcmp(key, "dev_pair_w") == 0) p = d.pair_w;
+        else if (std::strcmp(key, "dev_win_w") == 0) p = d.win_w;
+        else return NTC_ERR_INVALID_ARG;
+        if (!ctx->has_index) return NTC_ERR_NO_INDEX;
+        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return NTC_ERR_HIP;
+        *value = (int64_t)(uintptr_t)p;
+    }
     else if (std::strcmp(key, "upload_host_us") == 0) *value = ctx->upload_host_us;
     else if (std::strcmp(key, "max_pass_bases") == 0) *value = (int64_t)ctx->max_pass_bases;
     else if (std::strcmp(key, "upload_total_us") == 0) *value = ctx->upload_total_us;
