@@ -206,14 +206,38 @@ int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t 
  * the block, ascending (n_syms of them, 1..94); width = 0, 1, 2, 4 or 8 bits for n_syms = 1,
  * 2, 3-4, 5-16, more; quality i of the block (read by read) has the rank of its byte in the
  * alphabet as its code, in bits [i width, i width + width) of a little-endian bit stream of
- * ceil(n_quals width / 64) 64-bit words, unused high bits zero.  The packing runs on the GPU. */
+ * ceil(n_quals width / 64) 64-bit words, unused high bits zero.  The packing runs on the GPU.
+ *
+ * ntc_ctx_set_option(ctx, "quality_coder", c) chooses the sections' coder: 0 pack (default, the
+ * form above), 1 rans.  The option holds until it is changed, can be read with
+ * ntc_ctx_get_option, and is ignored under qualities = 0.  Under 1 a section is coded on the
+ * GPU by a static order-1 rANS coder; its meta has reserved[0] = 1, width still follows from
+ * n_syms, payload_off is 8-aligned, payload_bytes is exact, and the body there is canonical
+ * (one input, one byte string):
+ *   symbols   a quality's symbol is its rank in the alphabet; the block's qualities are cut into
+ *             spans of 2048, whatever the reads, the last one may be shorter
+ *   context   the symbol before it in the same span; n_syms at a span's start: n_syms + 1 rows
+ *   table     (n_syms + 1) * n_syms u16, row-major: counts over the whole block per (context,
+ *             symbol), each row normalised to sum 4096: f = 0 where the count is 0, else
+ *             max(1, floor(c * 4096 / T)); the difference to 4096 goes to the symbol with the
+ *             largest count (lowest index on ties); a row never seen is all zeros
+ *   sizes     ceil(n_quals / 2048) u32: the bytes of each span's stream
+ *   streams   back to back.  Byte-wise rANS, 32-bit state, L = 2^23: the encoder starts at L
+ *             and takes the span's symbols last to first; for start c (the frequencies below
+ *             the symbol in its row) and frequency f: while x >= 2^19 f emit x & 0xFF and shift
+ *             x >>= 8, then x = ((x / f) << 12) + x % f + c.  The stream is the final state as
+ *             u32, then the emitted bytes in reverse order.  The decoder reads forward: x = the
+ *             first 4 bytes; per symbol slot = x & 4095, s the symbol with c_s <= slot < c_s +
+ *             f_s, x = f_s (x >> 12) + slot - c_s, and while x < L: x = x << 8 | next byte.  At
+ *             the end x = L and the span's bytes are used up.
+ * A section with n_syms <= 1 has an empty body. */
 typedef struct ntc_qual_meta {
     uint64_t n_reads;       /* reads of the block                                          */
     uint64_t n_quals;       /* their quality bytes (= their bases)                         */
     uint64_t payload_off;   /* byte offset of the section's words in the payload buffer    */
-    uint64_t payload_bytes; /* 8 * ceil(n_quals * width / 64)                              */
+    uint64_t payload_bytes; /* 8 * ceil(n_quals * width / 64); coder 1: the body's bytes   */
     uint8_t width, n_syms;
-    uint8_t reserved[6];    /* 0                                                           */
+    uint8_t reserved[6];    /* [0]: the coder, 0 pack, 1 rans; the rest 0                  */
     uint8_t alphabet[96];   /* n_syms bytes ascending, then zeros                          */
 } ntc_qual_meta;            /* 136 bytes */
 /* The sections of the last ntc_encode_pack_fastq call on this context under mode 1 or 2, one
@@ -231,11 +255,17 @@ int ntc_encode_qualities(ntc_ctx *ctx, ntc_qual_meta *metas, uint64_t meta_cap, 
  * payload_bytes of every section, and that it lies 8-byte aligned inside the payload.  The
  * sections are dropped by the call that used them, whatever it returned (a call that only
  * reports sizes keeps them); ntc_decode_batch and ntc_decode_batch_device ignore them.
- * n_blocks = 0 drops pending sections.                                                      */
+ * n_blocks = 0 drops pending sections.
+ * Sections of coder 1 (all of them, or none) are decoded on the GPU.  Checked here for them,
+ * NTC_ERR_FORMAT: every row of the table sums to 4096 or is all zero, the start row is not zero
+ * when n_quals > 0, the span sizes number ceil(n_quals / 2048), each is >= 4 and they sum to the
+ * rest of the body, and the body is empty exactly when n_syms <= 1.  The decode call returns
+ * NTC_ERR_FORMAT (no text) also for a slot that falls in no symbol of its row, a byte needed
+ * past a span's end, a final state other than L and bytes of a span left over.               */
 int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t n_blocks, const uint8_t *payload,
                              uint64_t payload_bytes);
 
-/* ---- quality side file ("NTCQ", version 1) -------------------------------------------------- */
+/* ---- quality side file ("NTCQ", versions 1 and 2) ------------------------------------------- */
 /* The quality sections of an encoded.dat, beside it.  Everything little-endian:
  *   header, 32 bytes: "NTCQ", u32 version = 1, u8 mode (1 keep, 2 bin8), 23 zero bytes
  *   sections until the end of the file, section i for block i of encoded.dat:
@@ -250,8 +280,20 @@ int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t 
  * both freed with ntc_buffer_free, null when empty), *mode.  NTC_ERR_IO if it cannot be read;
  * NTC_ERR_FORMAT for a bad magic, version or mode, a truncated header, alphabet or member, a
  * width that does not follow from n_syms, an alphabet that is not ascending or leaves
- * '!'..'~', a member that does not inflate to exactly payload_bytes, non-zero padding bits.  */
+ * '!'..'~', a member that does not inflate to exactly payload_bytes, non-zero padding bits.
+ *
+ * Version 2 holds sections of coder 1 (rans); files of coder 0 are always version 1:
+ *   header, 32 bytes: "NTCQ", u32 version = 2, u8 mode, u8 coder = 1, 22 zero bytes
+ *   sections as above, the last header field being the body's bytes; after the alphabet comes
+ *   the body as it is, no gzip member
+ * ntc_q_write_header2 writes the header of a coder (0: the version-1 header).  For a meta with
+ * reserved[0] = 1, ntc_q_deflate_section and ntc_q_write_section emit a version-2 section
+ * (engine is ignored; NTC_ERR_INVALID_ARG for a body ntc_decode_set_qualities would refuse).
+ * ntc_q_read reads both versions; for version 2 every body starts 8-aligned in *payload, and
+ * NTC_ERR_FORMAT is also a coder byte other than 1 and everything ntc_decode_set_qualities
+ * checks of a body.                                                                          */
 int ntc_q_write_header(int fd, int mode);
+int ntc_q_write_header2(int fd, int mode, int coder);
 int ntc_q_deflate_section(const ntc_qual_meta *meta, const uint8_t *words, int engine, uint8_t **out,
                           uint64_t *out_len);
 int ntc_q_write_section(int fd, const ntc_qual_meta *meta, const uint8_t *words, int engine);

@@ -110,6 +110,12 @@ int ntc_decode_file_nx(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, con
  * the host parser (a blank line) are NTC_ERR_UNSUPPORTED under modes 1 and 2, with the case
  * in stats->error.  The contexts' "qualities" option is set for the call and left at 0.
  * q (may be NULL): sections and qualities written, their packed and deflated bytes.
+ * The sections' coder is the contexts' "quality_coder" option (ntcomp_codec.h: 0 pack, 1 rans),
+ * which the call leaves as it is; contexts that disagree are NTC_ERR_INVALID_ARG.  Under 1 the
+ * file is version 2, the pool copies each section's body as it came off the device instead of
+ * deflating it, and every property above holds as well; q->packed_bytes is then the bodies'
+ * bytes and q->deflated_bytes the sections' bytes as written.  Decode needs no option: the
+ * file's header names the coder.
  * Decode: nx_path as for ntc_decode_file_nx; q_path (NULL: none) = the "NTCQ" file, read once
  * (ntc_q_read); section i belongs to block i of encoded.dat, each batch gets its blocks'
  * sections and the output is FASTQ, "@seq.N\n{read}\n+\n{qualities}\n".  An input that ended

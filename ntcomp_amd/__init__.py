@@ -49,7 +49,7 @@ EXPORTED = [
     "ntc_index_prefix_table", "ntc_index_share", "ntc_index_prepare", "ntc_index_upload_prepared", "ntc_index_prep_free",
     "ntc_encode_exceptions", "ntc_decode_set_exceptions", "ntc_nx_write", "ntc_nx_read", "ntc_encode_file_nx",
     "ntc_decode_file_nx",
-    "ntc_encode_qualities", "ntc_decode_set_qualities", "ntc_q_write_header", "ntc_q_deflate_section",
+    "ntc_encode_qualities", "ntc_decode_set_qualities", "ntc_q_write_header", "ntc_q_write_header2", "ntc_q_deflate_section",
     "ntc_q_write_section", "ntc_q_read", "ntc_encode_file_ex", "ntc_decode_file_ex",
     "ntc_encode_names", "ntc_decode_set_names", "ntc_n_write_header", "ntc_n_deflate_section",
     "ntc_n_write_section", "ntc_n_read", "ntc_encode_file_ex2", "ntc_decode_file_ex2",
@@ -64,10 +64,16 @@ NX_RUN = np.dtype([("read", "<u8"), ("pos", "<u4"), ("len", "<u4"), ("sym", "<u4
 
 # quality modes (ctx option "qualities", include/ntcomp_codec.h)
 QUALITIES = {"drop": 0, "keep": 1, "bin8": 2}
+# the quality sections' coder (ctx option "quality_coder"): packed codes, or order-1 rANS on the GPU
+QUALITY_CODERS = {"pack": 0, "rans": 1}
 
 
 def _quality_code(qualities):
     return QUALITIES[qualities] if isinstance(qualities, str) else int(qualities)
+
+
+def _coder_code(coder):
+    return QUALITY_CODERS[coder] if isinstance(coder, str) else int(coder)
 
 
 # name modes (ctx option "names", include/ntcomp_codec.h)
@@ -110,6 +116,15 @@ class QualMeta(ctypes.Structure):
     _fields_ = [("n_reads", ctypes.c_uint64), ("n_quals", ctypes.c_uint64), ("payload_off", ctypes.c_uint64),
                 ("payload_bytes", ctypes.c_uint64), ("width", ctypes.c_uint8), ("n_syms", ctypes.c_uint8),
                 ("reserved", ctypes.c_uint8 * 6), ("alphabet", ctypes.c_uint8 * 96)]
+
+    @property
+    def coder(self):
+        """0 pack, 1 rans: the first reserved byte"""
+        return int(self.reserved[0])
+
+    @coder.setter
+    def coder(self, value):
+        self.reserved[0] = int(value)
 
 
 class NameMeta(ctypes.Structure):
@@ -305,6 +320,7 @@ def lib():
         "ntc_encode_qualities": (I, [P, P, u64, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "ntc_decode_set_qualities": (I, [P, P, u64, P, u64]),
         "ntc_q_write_header": (I, [I, I]),
+        "ntc_q_write_header2": (I, [I, I, I]),
         "ntc_q_deflate_section": (I, [P, P, I, ctypes.POINTER(P), ctypes.POINTER(u64)]),
         "ntc_q_write_section": (I, [I, P, P, I]),
         "ntc_q_read": (I, [ctypes.c_char_p, ctypes.POINTER(I), ctypes.POINTER(P), ctypes.POINTER(u64),
@@ -566,6 +582,18 @@ class GpuContext:
     def _qmode(self, qualities):
         return GpuContext._Option(self, "qualities", None if qualities is None else _quality_code(qualities))
 
+    def _qcoder(self, coder):
+        return GpuContext._Option(self, "quality_coder", None if coder is None else _coder_code(coder))
+
+    @property
+    def quality_coder(self):
+        """The coder of the quality sections encode_pack_fastq makes ("quality_coder"): 0 pack, 1 rans."""
+        return self.get_option("quality_coder")
+
+    @quality_coder.setter
+    def quality_coder(self, coder):
+        self.set_option("quality_coder", _coder_code(coder))
+
     def qualities(self):
         """The quality sections of the last encode_pack_fastq call under "keep" or "bin8"
         (ntc_encode_qualities) -> (list of QualMeta, their packed words as bytes)."""
@@ -762,17 +790,19 @@ class GpuContext:
             raise e
         return bases[:nb.value].copy(), offs
 
-    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None, names=None):
+    def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None, names=None,
+                          quality_coder=None):
         """encode_pack on FASTQ text parsed on the GPU (ntc_encode_pack_fastq) -> (list of
         BlockMeta, payload bytes, bases encoded).  With non_acgt (as for encode) the exception
         runs come fourth.  With qualities ("drop", "keep" or "bin8"; the call runs under that
         mode) the quality sections come next, as qualities() returns them, and with names ("drop",
-        "keep" or "id") the name sections come last, as names() returns them."""
+        "keep" or "id") the name sections come last, as names() returns them.  quality_coder ("pack" or
+        "rans"; the call runs under it): the coder of the quality sections."""
         t = np.frombuffer(bytes(text), dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
         nb = (n_reads + block_reads - 1) // block_reads
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
-        with self._policy(non_acgt), self._qmode(qualities), self._nmode(names):
+        with self._policy(non_acgt), self._qmode(qualities), self._nmode(names), self._qcoder(quality_coder):
             rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas,
                                               ctypes.byref(out), ctypes.byref(used), ctypes.byref(nbases),
                                               ctypes.byref(bad))
@@ -1152,13 +1182,14 @@ def read_qualities(path):
     return int(mode.value), metas, payload
 
 
-def write_qualities(fd, mode, metas, payload, header=True, engine="libdeflate"):
-    """The "NTCQ" header (when header) and one section per QualMeta to fd (ntc_q_write_header,
-    ntc_q_write_section); payload: the words the metas' payload_off point into."""
+def write_qualities(fd, mode, metas, payload, header=True, engine="libdeflate", coder="pack"):
+    """The "NTCQ" header (when header) and one section per QualMeta to fd (ntc_q_write_header2,
+    ntc_q_write_section); payload: the words the metas' payload_off point into.  coder "rans":
+    the version-2 header, for sections whose metas say coder 1."""
     if header:
-        rc = lib().ntc_q_write_header(fd, _quality_code(mode))
+        rc = lib().ntc_q_write_header2(fd, _quality_code(mode), _coder_code(coder))
         if rc:
-            raise NtcError(rc, "ntc_q_write_header")
+            raise NtcError(rc, "ntc_q_write_header2")
     buf = np.frombuffer(bytes(payload), dtype=np.uint8) if len(payload) else np.zeros(8, dtype=np.uint8)
     for m in metas:
         if m.payload_off + m.payload_bytes > len(payload):

@@ -186,6 +186,10 @@ def _check_q_args(args):
         _bad_args(f"encode: --qualities {args.qualities} requires --quality-file PATH")
     if args.qualities == "drop" and args.quality_file is not None:
         _bad_args("encode: --quality-file is only written under --qualities keep or bin8")
+    if args.quality_coder is not None and args.quality_coder not in ("pack", "rans"):
+        _bad_args("encode: --quality-coder: pack or rans")
+    if args.quality_coder is not None and args.qualities == "drop":
+        _bad_args("encode: --quality-coder needs --qualities keep or bin8")
 
 
 def _check_n_args(args):
@@ -236,6 +240,8 @@ def cmd_encode(args):
                                                        "nx_fd": nx_file.fileno() if nx_file else -1}
         if q_file:
             nx_args.update(qualities=args.qualities, q_fd=q_file.fileno())
+            for c in ctxs:  # the pipeline takes the coder from its contexts
+                c.quality_coder = args.quality_coder or "pack"
         if n_file:
             nx_args.update(names=args.names, n_fd=n_file.fileno())
         res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
@@ -264,7 +270,8 @@ def cmd_encode(args):
               gpu_parsed_batches=res["gpu_parsed"], non_acgt=args.non_acgt,
               **{"nx_" + k: v for k, v in res.get("nx", dict.fromkeys(("runs", "bases", "reads",
                                                                         "runs_in_dropped_blocks"), 0)).items()},
-              **({"qualities": args.qualities, **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}),
+              **({"qualities": args.qualities, "quality_coder": args.quality_coder or "pack",
+                  **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}),
               **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}))
 
 
@@ -355,6 +362,9 @@ def main(argv=None):
                    help="FASTQ quality scores: drop (default), keep (lossless) or bin8 (Phred scores binned to 8 levels, "
                         "lossy); keep and bin8 write them, packed on the GPU, to the --quality-file")
     e.add_argument("--quality-file", metavar="PATH", help="with --qualities keep or bin8: the side file to write")
+    e.add_argument("--quality-coder", default=None, metavar="CODER",
+                   help="with --qualities keep or bin8: pack (default; packed codes, deflated on the host) or rans "
+                        "(order-1 rANS coded on the GPU, no host deflate)")
     e.add_argument("--names", default="drop", metavar="MODE",
                    help="FASTQ read names: drop (default), keep (lossless: the header line after '@') or id (the name up "
                         "to its first space or tab, lossy); keep and id write them, front-coded on the GPU, to the "

@@ -49,6 +49,7 @@
 #include "ntc_internal.h"
 #include "codec_params.h"
 #include "nonacgt_core.h"
+#include "qrans_core.h"
 #include "quality_core.h"
 #include "names_core.h"
 
@@ -889,10 +890,33 @@ int ntc_q_write_header(int fd, int mode) {
     return nx_write_all(fd, h, sizeof(h)) ? NTC_OK : NTC_ERR_IO;
 }
 
+int ntc_q_write_header2(int fd, int mode, int coder) {
+    if (coder == 0) return ntc_q_write_header(fd, mode);
+    if (fd < 0 || mode < 1 || mode > 2 || coder != 1) return NTC_ERR_INVALID_ARG;
+    const uint8_t h[32] = {'N', 'T', 'C', 'Q', 2, 0, 0, 0, (uint8_t)mode, (uint8_t)coder};
+    return nx_write_all(fd, h, sizeof(h)) ? NTC_OK : NTC_ERR_IO;
+}
+
 int ntc_q_deflate_section(const ntc_qual_meta *meta, const uint8_t *words, int engine, uint8_t **out, uint64_t *out_len) {
     if (!meta || !out || !out_len || (meta->payload_bytes && !words)) return NTC_ERR_INVALID_ARG;
     *out = nullptr;
     *out_len = 0;
+    if (meta->reserved[0] == 1) {  // coder 1: the body as it came off the device, no gzip member
+        if (!ntc::q_meta_ok(meta->n_quals, meta->width, meta->n_syms, meta->alphabet) || meta->payload_bytes >> 32 ||
+            !ntc::qr_body_ok(meta->n_quals, meta->n_syms, words, meta->payload_bytes))
+            return NTC_ERR_INVALID_ARG;
+        std::vector<uint8_t> sec(24);
+        sec.insert(sec.end(), meta->alphabet, meta->alphabet + meta->n_syms);
+        if (meta->payload_bytes) sec.insert(sec.end(), words, words + meta->payload_bytes);
+        std::memcpy(sec.data(), &meta->n_reads, 8);
+        std::memcpy(sec.data() + 8, &meta->n_quals, 8);
+        sec[16] = meta->width;
+        sec[17] = meta->n_syms;
+        const uint32_t body32 = (uint32_t)meta->payload_bytes;
+        std::memcpy(sec.data() + 20, &body32, 4);
+        return hand_out(sec, out, out_len);
+    }
+    if (meta->reserved[0]) return NTC_ERR_INVALID_ARG;
     if (!ntc::q_meta_ok(meta->n_quals, meta->width, meta->n_syms, meta->alphabet) ||
         meta->payload_bytes != ntc::q_words(meta->n_quals, meta->width) * 8)
         return NTC_ERR_INVALID_ARG;
@@ -939,9 +963,11 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
     std::fclose(f);
     if (io_bad) return NTC_ERR_IO;
     static const uint8_t magic[8] = {'N', 'T', 'C', 'Q', 1, 0, 0, 0};
-    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
-    if (buf[8] < 1 || buf[8] > 2) return NTC_ERR_FORMAT;
-    for (size_t i = 9; i < 32; i++)
+    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 4) != 0) return NTC_ERR_FORMAT;
+    const bool v2 = buf[4] == 2;  // version 2: coder 1, the bodies as they are
+    if (std::memcmp(buf.data() + 5, magic + 5, 3) != 0 || (!v2 && buf[4] != 1)) return NTC_ERR_FORMAT;
+    if (buf[8] < 1 || buf[8] > 2 || buf[9] != (v2 ? 1 : 0)) return NTC_ERR_FORMAT;
+    for (size_t i = 10; i < 32; i++)
         if (buf[i]) return NTC_ERR_FORMAT;
     // pass 1: the headers and alphabets, and where each member lies and inflates to
     std::vector<ntc_qual_meta> all;
@@ -966,6 +992,18 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
         if (!ntc::q_meta_ok(m.n_quals, m.width, m.n_syms, m.alphabet) || m.n_quals > m.n_reads * (1ull << 32))
             return NTC_ERR_FORMAT;
         if (buf.size() - at < gz || (gz == 0) != (m.width == 0)) return NTC_ERR_FORMAT;
+        if (v2) {  // gz = the body's bytes; every body starts 8-aligned in the payload
+            if (!ntc::qr_body_ok(m.n_quals, m.n_syms, buf.data() + at, gz)) return NTC_ERR_FORMAT;
+            m.reserved[0] = 1;
+            m.payload_off = pay_bytes;
+            m.payload_bytes = gz;
+            pay_bytes += ((uint64_t)gz + 7) & ~7ull;
+            gz_at.push_back(at);
+            gz_len.push_back(gz);
+            at += gz;
+            all.push_back(m);
+            continue;
+        }
         const uint64_t nw = ntc::q_words(m.n_quals, m.width);
         if (nw * 8 > (uint64_t)gz * 1100 + 4096) return NTC_ERR_FORMAT;  // past deflate's best ratio: not this member
         m.payload_off = pay_bytes;
@@ -985,6 +1023,10 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
         for (size_t i; (i = next.fetch_add(1)) < all.size() && !bad;) {
             const ntc_qual_meta &m = all[i];
             if (!m.width) continue;
+            if (v2) {
+                std::memcpy(pay.data() + m.payload_off, buf.data() + gz_at[i], m.payload_bytes);
+                continue;
+            }
             if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, words)) {
                 bad = true;
                 return;

@@ -20,6 +20,7 @@
 #include "derived.h"
 #include "kernels.h"
 #include "nonacgt_core.h"
+#include "qrans_core.h"
 #include "quality_core.h"
 #include "names_core.h"
 #include "ntc_internal.h"
@@ -47,6 +48,7 @@ enum WsSlot {
     WS_UNP_PAY, WS_UNP_MARKS, WS_UNP_ST, WS_UNP_VALS, WS_UNP_RECS, WS_UNP_OUT,
     WS_NX_BITS, WS_NX_RUNS, WS_NX_PATCH,
     WS_Q_QUALS, WS_Q_BLOCKS, WS_Q_PAYLOAD, WS_QD_IN, WS_QD_QUALS,
+    WS_QR_COUNTS, WS_QR_CUM, WS_QR_SCRATCH, WS_QR_SCAN,
     WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES, WS_COUNT
 };
 
@@ -142,6 +144,8 @@ struct ntc_ctx {
     // ntc_encode_pack_fastq left in WS_Q_BLOCKS / WS_Q_PAYLOAD, the sections waiting for the
     // next FASTA decode call (which then writes FASTQ)
     int q_mode = 0;
+    int q_coder = 0;       // option "quality_coder": 0 pack, 1 rans (qrans.hip); q_coder_last: of those sections
+    int q_coder_last = 0;
     uint64_t q_blocks = 0, q_words = 0, q_reads = 0;
     uint32_t q_block_reads = 0;
     std::vector<ntc_qual_meta> qd_metas;
@@ -621,7 +625,9 @@ int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t tota
     if ((rc = ensure(ctx, WS_Q_QUALS, total + 64, &quals))) return rc;
     // the status word, the presence maps (16 B per block), the blocks and their totals
     if ((rc = ensure(ctx, WS_Q_BLOCKS, 64 + nb * 16 + (nb + 1) * sizeof(QBlock), &blk))) return rc;
-    if ((rc = ensure(ctx, WS_Q_PAYLOAD, q_payload_words_max(total, nb) * 8, &pay))) return rc;
+    const bool rans = ctx->q_coder == 1;
+    if ((rc = ensure(ctx, WS_Q_PAYLOAD, rans ? qr_payload_bytes_max(total, nb) : q_payload_words_max(total, nb) * 8, &pay)))
+        return rc;
     const FastqArgs &f = ctx->fq_last;
     QEncArgs a{};
     a.raw = f.raw;
@@ -641,7 +647,30 @@ int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t tota
     a.box = ctx->h_box;
     ctx->h_box[6] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
     ctx->h_box[7] = 0;
-    launch_quality_pack(a, total, ctx->stream);
+    ctx->q_coder_last = ctx->q_coder;
+    if (!rans) {
+        launch_quality_pack(a, total, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+        return NTC_OK;
+    }
+    // coder 1: counts, cumulative rows, a scratch slot per span, the span sizes and their scan
+    const uint64_t S = qr_spans_max(total, nb);
+    void *cnt, *cum, *scr, *scan;
+    if ((rc = ensure(ctx, WS_QR_COUNTS, nb * kQRCountStride * 4, &cnt))) return rc;
+    if ((rc = ensure(ctx, WS_QR_CUM, nb * kQRCumStride * 2, &cum))) return rc;
+    if ((rc = ensure(ctx, WS_QR_SCRATCH, S * kQRSlot + 64, &scr))) return rc;
+    if ((rc = ensure(ctx, WS_QR_SCAN, (2 * (S + 1) + scan_tmp_words(S)) * 8, &scan))) return rc;
+    QREncArgs ra{};
+    ra.q = a;
+    ra.counts = (uint32_t *)cnt;
+    ra.cum = (uint16_t *)cum;
+    ra.scratch = (uint8_t *)scr;
+    ra.sizes = (uint64_t *)scan;
+    ra.offs = ra.sizes + (S + 1);
+    ra.tmp = ra.offs + (S + 1);
+    ra.spans_max = S;
+    launch_quality_gather(a, ctx->stream);
+    launch_quality_rans(ra, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     return NTC_OK;
 }
@@ -678,10 +707,75 @@ bool q_take_pending(ntc_ctx *ctx, std::vector<ntc_qual_meta> &metas, std::vector
     return true;
 }
 
+// Decode side, coder 1 (ntc_decode_set_qualities checked every body with qr_body_ok): the
+// blocks, where every span's stream starts and ends, and the payload go up; then as q_unpack.
+int q_rans_decode(ntc_ctx *ctx, const std::vector<ntc_qual_meta> &metas, const std::vector<uint64_t> &payload,
+                  uint64_t n_reads, uint64_t n_bases, const uint64_t *d_offs, uint8_t **d_quals) {
+    const uint64_t nb = metas.size();
+    std::vector<QRDecBlock> blk(nb + 1);
+    std::vector<uint64_t> span_at;
+    const uint8_t *pay = (const uint8_t *)payload.data();
+    uint64_t r = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+        const ntc_qual_meta &m = metas[b];
+        QRDecBlock &k = blk[b];
+        std::memset(&k, 0, sizeof(k));
+        k.r0 = r;
+        k.r1 = r += m.n_reads;
+        k.n_quals = m.n_quals;
+        k.body_off = m.payload_off;
+        k.span_off = span_at.size() / 2;
+        k.n_syms = m.n_syms;
+        std::memcpy(k.alphabet, m.alphabet, 96);
+        if (r > n_reads) break;
+        if (m.n_syms <= 1) continue;
+        const uint64_t ns = qr_spans(m.n_quals), tb = qr_table_bytes(m.n_syms);
+        uint64_t at = m.payload_off + tb + 4 * ns;
+        for (uint64_t j = 0; j < ns; j++) {
+            uint32_t size;
+            std::memcpy(&size, pay + m.payload_off + tb + 4 * j, 4);
+            span_at.push_back(at);
+            span_at.push_back(at += size);
+        }
+    }
+    if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "the quality sections do not cover exactly the reads decoded");
+    std::memset(&blk[nb], 0, sizeof(QRDecBlock));
+    blk[nb].span_off = span_at.size() / 2;
+    void *in, *quals;
+    int rc;
+    const uint64_t blk_bytes = (blk.size() * sizeof(QRDecBlock) + 63) & ~63ull, at_bytes = (span_at.size() * 8 + 63) & ~63ull;
+    if ((rc = ensure(ctx, WS_QD_IN, blk_bytes + at_bytes + payload.size() * 8 + 64, &in))) return rc;
+    if ((rc = ensure(ctx, WS_QD_QUALS, n_bases + 64, &quals))) return rc;
+    HIP_TRY(ctx, hipMemcpy(in, blk.data(), blk.size() * sizeof(QRDecBlock), hipMemcpyHostToDevice));
+    if (!span_at.empty())
+        HIP_TRY(ctx, hipMemcpy((uint8_t *)in + blk_bytes, span_at.data(), span_at.size() * 8, hipMemcpyHostToDevice));
+    if (!payload.empty())
+        HIP_TRY(ctx, hipMemcpy((uint8_t *)in + blk_bytes + at_bytes, payload.data(), payload.size() * 8, hipMemcpyHostToDevice));
+    QRDecArgs a{};
+    a.blocks = (const QRDecBlock *)in;
+    a.n_blocks = nb;
+    a.n_spans = span_at.size() / 2;
+    a.span_at = (const uint64_t *)((uint8_t *)in + blk_bytes);
+    a.payload = (const uint8_t *)in + blk_bytes + at_bytes;
+    a.offs = d_offs;
+    a.n_reads = n_reads;
+    a.quals = (uint8_t *)quals;
+    a.status = ctx->d_status;
+    launch_quality_rans_decode(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ctx->box_valid && ctx->last == kDecode)
+        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
+                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    *d_quals = (uint8_t *)quals;
+    return NTC_OK;
+}
+
 // Decode side: the sections over the decoded reads' offsets -> quality bytes (WS_QD_QUALS);
 // then the status mailbox again, as the unpack may have set the status.
 int q_unpack(ntc_ctx *ctx, const std::vector<ntc_qual_meta> &metas, const std::vector<uint64_t> &payload,
              uint64_t n_reads, uint64_t n_bases, const uint64_t *d_offs, uint8_t **d_quals) {
+    if (!metas.empty() && metas[0].reserved[0] == 1) return q_rans_decode(ctx, metas, payload, n_reads, n_bases, d_offs, d_quals);
     const uint64_t nb = metas.size();
     std::vector<uint8_t> up(nb * sizeof(QDecBlock));
     uint64_t r = 0, max_q = 0;
@@ -1552,6 +1646,11 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
         ctx->q_mode = (int)value;
         return NTC_OK;
     }
+    if (std::strcmp(key, "quality_coder") == 0) {  // the quality sections' coder: 0 pack, 1 rans (ntcomp_codec.h)
+        if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "quality_coder must be 0 (pack) or 1 (rans)");
+        ctx->q_coder = (int)value;
+        return NTC_OK;
+    }
     if (std::strcmp(key, "names") == 0) {  // FASTQ read names: 0 drop, 1 keep, 2 id (ntcomp_codec.h)
         if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "names must be 0 (drop), 1 (keep) or 2 (id)");
         ctx->n_mode = (int)value;
@@ -1633,6 +1732,7 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "spill_reruns") == 0) *value = (int64_t)ctx->spill_reruns;
     else if (std::strcmp(key, "non_acgt") == 0) *value = ctx->nx_policy;
     else if (std::strcmp(key, "qualities") == 0) *value = ctx->q_mode;
+    else if (std::strcmp(key, "quality_coder") == 0) *value = ctx->q_coder;
     else if (std::strcmp(key, "names") == 0) *value = ctx->n_mode;
     else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
     else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
@@ -2517,7 +2617,8 @@ int ntc_encode_qualities(ntc_ctx *ctx, ntc_qual_meta *metas, uint64_t meta_cap, 
         m.n_reads = std::min<uint64_t>(ctx->q_block_reads, ctx->q_reads - b * ctx->q_block_reads);
         m.n_quals = blk[b].n_quals;
         m.payload_off = blk[b].word_off * 8;
-        m.payload_bytes = blk[b].n_words * 8;
+        m.payload_bytes = ctx->q_coder_last == 1 ? blk[b].body_bytes : blk[b].n_words * 8;
+        m.reserved[0] = (uint8_t)ctx->q_coder_last;
         m.width = (uint8_t)blk[b].w;
         m.n_syms = (uint8_t)blk[b].n_syms;
         std::memcpy(m.alphabet, blk[b].alphabet, blk[b].n_syms);
@@ -2532,17 +2633,27 @@ int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t 
     ctx->qd_payload.clear();
     ctx->qd_has_pending = false;
     if (n_blocks == 0) return NTC_OK;
-    if (payload_bytes & 7) return set_err(ctx, NTC_ERR_FORMAT, "quality payload is not whole 64-bit words");
+    const uint32_t coder = metas[0].reserved[0];  // 0 pack, 1 rans: one coder for all sections
+    if (coder > 1) return set_err(ctx, NTC_ERR_FORMAT, "quality sections of an unknown coder");
+    if (coder == 0 && (payload_bytes & 7)) return set_err(ctx, NTC_ERR_FORMAT, "quality payload is not whole 64-bit words");
     for (uint64_t b = 0; b < n_blocks; b++) {
         const ntc_qual_meta &m = metas[b];
         if (!q_meta_ok(m.n_quals, m.width, m.n_syms, m.alphabet))
             return set_err(ctx, NTC_ERR_FORMAT, "quality section " + std::to_string(b) + ": width, n_syms or alphabet");
+        if (m.reserved[0] != coder) return set_err(ctx, NTC_ERR_FORMAT, "quality sections of more than one coder");
+        if (coder == 1) {
+            if (m.n_quals >> 40 || (m.payload_off & 7) || m.payload_off > payload_bytes ||
+                m.payload_bytes > payload_bytes - m.payload_off ||
+                !qr_body_ok(m.n_quals, m.n_syms, payload + m.payload_off, m.payload_bytes))
+                return set_err(ctx, NTC_ERR_FORMAT, "quality section " + std::to_string(b) + ": table, span sizes or place");
+            continue;
+        }
         if (m.n_quals >> 40 || m.payload_bytes != q_words(m.n_quals, m.width) * 8 || (m.payload_off & 7) ||
             m.payload_off > payload_bytes || m.payload_bytes > payload_bytes - m.payload_off)
             return set_err(ctx, NTC_ERR_FORMAT, "quality section " + std::to_string(b) + ": payload size or place");
     }
     ctx->qd_metas.assign(metas, metas + n_blocks);
-    ctx->qd_payload.resize(payload_bytes / 8);
+    ctx->qd_payload.assign((payload_bytes + 7) / 8, 0);
     if (payload_bytes) std::memcpy(ctx->qd_payload.data(), payload, payload_bytes);
     ctx->qd_has_pending = true;
     return NTC_OK;
@@ -2855,6 +2966,10 @@ struct NxHookFill {
         ntc::g_nx_hooks.decode_set_exceptions = ntc_decode_set_exceptions;
         ntc::g_q_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "qualities", mode); };
         ntc::g_q_hooks.encode_qualities = ntc_encode_qualities;
+        ntc::g_q_hooks.get_coder = [](ntc_ctx *ctx) {
+            int64_t v = 0;
+            return ntc_ctx_get_option(ctx, "quality_coder", &v) == NTC_OK ? (int)v : -1;
+        };
         ntc::g_q_hooks.decode_set_qualities = ntc_decode_set_qualities;
         ntc::g_n_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "names", mode); };
         ntc::g_n_hooks.encode_names = ntc_encode_names;

@@ -268,6 +268,7 @@ struct QBlock {
     uint64_t p0, p1;  // presence map, bits 0..127
     uint32_t n_syms, w;
     uint8_t alphabet[96];
+    uint64_t body_bytes;  // coder 1 (qrans.hip): the section body's bytes, at byte 8 word_off of the payload
 };
 struct QEncArgs {
     const uint8_t *raw;
@@ -286,6 +287,27 @@ struct QEncArgs {
 };
 uint64_t q_payload_words_max(uint64_t total, uint64_t n_blocks);
 void launch_quality_pack(const QEncArgs &a, uint64_t total, hipStream_t s);
+// the first two steps alone (k_q_gather, k_q_alpha): what both coders start from
+void launch_quality_gather(const QEncArgs &a, hipStream_t s);
+// Coder 1, the order-1 rANS coder (qrans.hip, qrans_core.h), in place of k_q_pack after
+// launch_quality_gather.  With S = qr_spans_max(total, n_blocks): counts: n_blocks *
+// kQRCountStride words (zeroed here), cum: n_blocks * kQRCumStride u16, scratch: S *
+// kQRSlot + 64 bytes, sizes / offs: S + 1 words each, tmp: scan_tmp_words(S) words, payload
+// (q.payload): qr_payload_bytes_max(total, n_blocks) bytes.  Every body starts 8-aligned, the
+// bytes up to the next body are zero; box[7] = the payload's 64-bit words, blocks[b].word_off
+// and body_bytes say where each body lies.
+constexpr uint64_t kQRCountStride = 95 * 94, kQRCumStride = 95 * 96, kQRSlot = 3080;
+struct QREncArgs {
+    QEncArgs q;
+    uint32_t *counts;
+    uint16_t *cum;
+    uint8_t *scratch;
+    uint64_t *sizes, *offs, *tmp;
+    uint64_t spans_max;
+};
+uint64_t qr_spans_max(uint64_t total, uint64_t n_blocks);
+uint64_t qr_payload_bytes_max(uint64_t total, uint64_t n_blocks);
+void launch_quality_rans(const QREncArgs &a, hipStream_t s);
 // Decode side: block b covers reads [r0, r1) of the decoded batch; its codes become bytes
 // at those reads' offsets in quals.  A code >= n_syms, or a block whose n_quals is not the
 // bases of its reads, sets status (the decode call's) to r0 << 8 | NTC_ERR_FORMAT.
@@ -305,6 +327,26 @@ struct QDecArgs {
 };
 uint64_t quality_unpack_tiles(uint64_t max_quals);
 void launch_quality_unpack(const QDecArgs &a, hipStream_t s);
+// Coder 1: block b's body (validated by the host, qr_body_ok) lies at byte body_off (8-aligned)
+// of payload, its spans are span_off .. of span_at, which holds two words per span: where its
+// stream starts and ends in payload.  Status as above, also for a slot in no symbol, a byte
+// needed past the span's end, a final state other than L and unconsumed bytes.
+struct QRDecBlock {
+    uint64_t r0, r1, n_quals, body_off, span_off;
+    uint32_t n_syms, pad;
+    uint8_t alphabet[96];
+};
+struct QRDecArgs {
+    const QRDecBlock *blocks;  // [n_blocks + 1]: the last one's span_off = n_spans
+    uint64_t n_blocks, n_spans;
+    const uint8_t *payload;
+    const uint64_t *span_at;
+    const uint64_t *offs;      // [n_reads + 1]
+    uint64_t n_reads;
+    uint8_t *quals;
+    unsigned long long *status;
+};
+void launch_quality_rans_decode(const QRDecArgs &a, hipStream_t s);
 // launch_fasta's FASTQ twin: "@seq.{first_id + r}\n{read r}\n+\n{qualities r}\n"
 void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t n,
                        uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,

@@ -138,6 +138,7 @@ struct QHooks {
                             uint64_t payload_cap, uint64_t *n_blocks, uint64_t *payload_bytes);
     int (*decode_set_qualities)(::ntc_ctx *ctx, const ::ntc_qual_meta *metas, uint64_t n_blocks, const uint8_t *payload,
                                 uint64_t payload_bytes);
+    int (*get_coder)(::ntc_ctx *ctx);  // ctx option "quality_coder" (0 pack, 1 rans), < 0: cannot be read
 };
 extern QHooks g_q_hooks;
 // ... and for read names: with the table null, ntc_encode_file_ex2 / ntc_decode_file_ex2

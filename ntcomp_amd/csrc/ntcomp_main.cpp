@@ -9,7 +9,7 @@
 //   ntcomp encode -i P [--gpus N | --devices 0,0,..] [--threads T] [--blocks-per-batch B]
 //                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
 //                 [--non-acgt error|mask|keep] [--exceptions PATH]
-//                 [--qualities drop|keep|bin8] [--quality-file PATH]
+//                 [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]
 //                 [--names drop|keep|id] [--name-file PATH] FILE > encoded.dat
 //   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
 //                 [--exceptions PATH] [--quality-file PATH] [--name-file PATH] FILE > out.fasta
@@ -73,7 +73,7 @@ bool takes_value(const std::string &o) {
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
                               "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
-                              "--qualities", "--quality-file", "--names", "--name-file"};
+                              "--qualities", "--quality-file", "--quality-coder", "--names", "--name-file"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -243,6 +243,11 @@ int cmd_encode(const Args &a) {
     if (q_mode > 0 && q_path.empty()) bad_args("encode: --qualities " + q_name + " requires --quality-file PATH");
     if (q_mode == 0 && a.flag("--quality-file"))
         bad_args("encode: --quality-file is only written under --qualities keep or bin8");
+    // ... and their coder: pack (default; deflated on the host) or rans (coded on the GPU)
+    const std::string qc_name = a.get("--quality-coder", nullptr, "pack");
+    const int q_coder = qc_name == "pack" ? 0 : qc_name == "rans" ? 1 : -1;
+    if (q_coder < 0) bad_args("encode: --quality-coder: pack or rans");
+    if (q_mode == 0 && a.flag("--quality-coder")) bad_args("encode: --quality-coder needs --qualities keep or bin8");
     // read names: drop (default), keep, or id, with the front-coded sections in a side file
     const std::string n_name = a.get("--names", nullptr, "drop"), n_path = a.get("--name-file", nullptr, "");
     const int n_mode = n_name == "drop" ? 0 : n_name == "keep" ? 1 : n_name == "id" ? 2 : -1;
@@ -280,6 +285,9 @@ int cmd_encode(const Args &a) {
     int n_fd = -1;
     if (n_mode > 0 && (n_fd = ::open(n_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
         die("encode: cannot write " + n_path);
+    if (q_mode > 0)  // the pipeline takes the coder from its contexts
+        for (ntc_ctx *c : ctxs)
+            if (ntc_ctx_set_option(c, "quality_coder", q_coder)) die("encode: --quality-coder: the option was refused");
     const ntc_file_opts fo{policy, nx_fd, q_mode, q_fd, nullptr, nullptr};
     const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd, nullptr};
     std::fflush(stdout);
@@ -291,11 +299,11 @@ int cmd_encode(const Args &a) {
     if (nx_fd >= 0 && ::close(nx_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + nx_path);
     if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
     if (n_fd >= 0 && ::close(n_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + n_path);
-    char qjson[640] = "";  // the quality and name files' figures, when they were written
+    char qjson[704] = "";  // the quality and name files' figures, when they were written
     if (q_mode > 0)
-        std::snprintf(qjson, 256, "\"qualities\": \"%s\", \"q_sections\": %llu, \"q_quals\": %llu, "
-                                            "\"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
-                      q_name.c_str(), (unsigned long long)qs.sections, (unsigned long long)qs.quals,
+        std::snprintf(qjson, 320, "\"qualities\": \"%s\", \"quality_coder\": \"%s\", \"q_sections\": %llu, "
+                                  "\"q_quals\": %llu, \"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
+                      q_name.c_str(), qc_name.c_str(), (unsigned long long)qs.sections, (unsigned long long)qs.quals,
                       (unsigned long long)qs.packed_bytes, (unsigned long long)qs.deflated_bytes);
     if (n_mode > 0)
         std::snprintf(qjson + std::strlen(qjson), 320, "\"names\": \"%s\", \"n_sections\": %llu, \"n_names\": %llu, "
@@ -480,7 +488,7 @@ void usage(FILE *f) {
                  "Sequencing data compression with SBWT + k-bounded matching statistics; encode/decode hot path on "
                  "MI355X.\n\nusage: ntcomp build -o PREFIX [-k K] [-m MEM_GB] [--temp-dir DIR] FILES...\n"
                  "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH]\n"
-                 "                     [--qualities drop|keep|bin8] [--quality-file PATH]\n"
+                 "                     [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]\n"
                  "                     [--names drop|keep|id] [--name-file PATH] FILE > encoded.dat\n"
                  "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH] FILE\n"
                  "                     > out.fasta\n\n"
@@ -494,6 +502,8 @@ void usage(FILE *f) {
                  "                     to the --quality-file\n"
                  "  --quality-file PATH  encode --qualities keep|bin8: the side file to write; decode: the side file\n"
                  "                     whose qualities are printed: the output is then FASTQ\n"
+                 "  --quality-coder CODER  encode --qualities keep|bin8: pack (default; packed codes, deflated on the\n"
+                 "                     host) or rans (order-1 rANS coded on the GPU, no host deflate)\n"
                  "  --names MODE       encode: FASTQ read names: drop (default), keep (lossless: the header line\n"
                  "                     after '@'), or id (the name up to its first space or tab, lossy); keep and id\n"
                  "                     write them, front-coded on the GPU, to the --name-file\n"

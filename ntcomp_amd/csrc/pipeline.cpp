@@ -49,7 +49,7 @@
 
 namespace ntc {
 NxHooks g_nx_hooks = {nullptr, nullptr, nullptr, nullptr};  // capi.cpp fills it at load
-QHooks g_q_hooks = {nullptr, nullptr, nullptr};
+QHooks g_q_hooks = {nullptr, nullptr, nullptr, nullptr};
 NHooks g_n_hooks = {nullptr, nullptr, nullptr};
 }
 
@@ -254,6 +254,13 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     if (q_mode < 0 || q_mode > 2 || (q_mode ? q_fd < 0 : q_fd != -1)) return NTC_ERR_INVALID_ARG;
     const ntc::QHooks &qh = ntc::g_q_hooks;
     if (q_mode && (!qh.set_mode || !qh.encode_qualities)) return NTC_ERR_UNSUPPORTED;
+    // the sections' coder is the contexts' "quality_coder" option, which must be the same in all
+    int q_coder = 0;
+    if (q_mode && qh.get_coder) {
+        q_coder = qh.get_coder(ctxs[0]);
+        for (int i = 0; i < n_ctx; i++)
+            if (q_coder < 0 || qh.get_coder(ctxs[i]) != q_coder) return NTC_ERR_INVALID_ARG;
+    }
     ntc_q_stats QS{};
     // n_mode / n_fd / ns: ntc_encode_file_ex2's name side file (n_mode 0: none)
     if (n_mode < 0 || n_mode > 2 || (n_mode ? n_fd < 0 : n_fd != -1)) return NTC_ERR_INVALID_ARG;
@@ -918,7 +925,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         }
         return true;
     };
-    if (q_mode && ntc_q_write_header(q_fd, q_mode)) sh.fail(NTC_ERR_IO, "qualities: write failed");
+    if (q_mode && ntc_q_write_header2(q_fd, q_mode, q_coder)) sh.fail(NTC_ERR_IO, "qualities: write failed");
     if (n_mode && ntc_n_write_header(n_fd, n_mode)) sh.fail(NTC_ERR_IO, "names: write failed");
     uint64_t reads_written = 0;
     for (uint64_t blk = 0;; blk++) {
@@ -960,7 +967,8 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 QS.sections++;
                 QS.quals += out.qmeta.n_quals;
                 QS.packed_bytes += out.qmeta.payload_bytes;
-                QS.deflated_bytes += out.qlen - 24 - out.qmeta.n_syms;
+                // coder 1 (no gzip member): the section as written
+                QS.deflated_bytes += out.qmeta.reserved[0] == 1 ? out.qlen : out.qlen - 24 - out.qmeta.n_syms;
             }
             if (out.has_n) {
                 if (!write_q(out.nsec, out.nlen, n_fd)) sh.fail(NTC_ERR_IO, "names: write failed");

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "qrans_core.h"
 #include "quality_core.h"
 
 namespace ntc {
@@ -25,6 +26,7 @@ namespace {
 constexpr uint32_t kQChunk = 64;   // records per workgroup of k_q_gather (16 per wave)
 constexpr uint32_t kQSpan = 2048;  // qualities per wave of k_q_pack (4 loads of 8 B per lane)
 constexpr uint32_t kQTile = 1024;  // qualities per workgroup of k_q_unpack
+static_assert(kQSpan == kQRSpan, "k_q_alpha counts the spans of both coders");
 
 __device__ __forceinline__ uint64_t umin(uint64_t x, uint64_t y) { return x < y ? x : y; }
 
@@ -217,13 +219,18 @@ __global__ __launch_bounds__(256) void k_fastq(const uint8_t *bases, const uint8
 
 uint64_t q_payload_words_max(uint64_t total, uint64_t n_blocks) { return total / 8 + n_blocks + 1; }
 
-void launch_quality_pack(const QEncArgs &a, uint64_t total, hipStream_t s) {
+void launch_quality_gather(const QEncArgs &a, hipStream_t s) {
     if (a.n_blocks == 0) return;
     (void)hipMemsetAsync(a.pres, 0, a.n_blocks * 16, s);  // a failure shows in the caller's hipGetLastError
     (void)hipMemsetAsync(a.status, 0xFF, 8, s);
     const uint64_t cpb = (a.block_reads + kQChunk - 1) / kQChunk;
     hipLaunchKernelGGL(k_q_gather, dim3((uint32_t)(a.n_blocks * cpb)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_q_alpha, dim3(1), dim3(256), 0, s, a);
+}
+
+void launch_quality_pack(const QEncArgs &a, uint64_t total, hipStream_t s) {
+    if (a.n_blocks == 0) return;
+    launch_quality_gather(a, s);
     const uint64_t spans = total / kQSpan + a.n_blocks;  // at most: a block's last span may be short
     hipLaunchKernelGGL(k_q_pack, dim3((uint32_t)((spans + 3) / 4)), dim3(256), 0, s, a);
 }
