@@ -130,7 +130,14 @@ int ntc_ctx_synchronize(ntc_ctx *ctx);
  * "tab_u" (after an upload: the depth in use), "tab_u_fallback" (1: the default depth 15
  * did not fit in free HBM, 14 was used), "pack_us" (last GPU block packer call, both
  * kernels), "upload_host_us" / "upload_total_us"
- * (last upload: host-side derivation / whole call).  Env NTC_ENCODE_VARIANT sets the
+ * (last upload: host-side derivation / whole call),
+ * "unpack_rice_not_simple", "unpack_rice_serial", "unpack_rice_through" (the paths the last
+ * ntc_unpack_streams call took through its Rice streams, s2 and s3 of every block: the
+ * streams in which some segment's chain did not meet the next segment's, so the true chain
+ * was walked; those among them in which a chain met none within 8 segments, which one lane
+ * decoded; and the segments the walked chains of the others ran through without a code
+ * start -- all 0 after a call with no Rice tile; they come back with the call's block
+ * statuses, at no launch or synchronisation of their own).  Env NTC_ENCODE_VARIANT sets the
  * default variant at ntc_ctx_create.                                                 */
 int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value);
 int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value);

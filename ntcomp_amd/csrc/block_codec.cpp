@@ -673,10 +673,12 @@ int zip_parts(const std::vector<uint64_t> (&parts)[4], std::vector<uint64_t> *ve
             const uint32_t l = flag >> 2;
             if (j + l > T) return NTC_ERR_FORMAT;
             // bases j .. j + l - 1 of the concatenation: from chunk j / 31 (and the next)
+            // (past 32 bases the reference's as_2bit panics; here base t lands on bit 2 t mod 64,
+            // as in unpack.hip, so the two decoders agree on such a block too)
             w = 0;
             for (uint32_t t = 0; t < l; t++) {
                 const uint64_t q = j + t;
-                w |= ((bn[q / 31] >> (2 * (q % 31))) & 3ULL) << (2 * t);
+                w |= ((bn[q / 31] >> (2 * (q % 31))) & 3ULL) << ((2 * t) & 63);
             }
             w &= 0x00FFFFFFFFFFFFFFULL;
             j += l;

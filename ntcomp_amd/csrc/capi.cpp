@@ -85,6 +85,7 @@ struct ntc_ctx {
     // the records of the last ntc_unpack_streams (in WS_UNP_RECS) and their read / base counts
     uint64_t *unp_d_recs = nullptr;
     uint64_t unp_recs = 0, unp_reads = 0, unp_bases = 0;
+    uint64_t unp_path[3] = {0, 0, 0};  // its Rice streams flagged not-simple, serial; segments run through
     // last call
     CallKind last = kNone;
     uint64_t last_n = 0;           // reads (encode) / records (decode)
@@ -1737,6 +1738,9 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
     else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
     else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
+    else if (std::strcmp(key, "unpack_rice_not_simple") == 0) *value = (int64_t)ctx->unp_path[0];
+    else if (std::strcmp(key, "unpack_rice_serial") == 0) *value = (int64_t)ctx->unp_path[1];
+    else if (std::strcmp(key, "unpack_rice_through") == 0) *value = (int64_t)ctx->unp_path[2];
     else if (std::strcmp(key, "pool_entries") == 0) *value = (int64_t)ctx->last4.pcap;  // last call's pools
     else if (std::strcmp(key, "pool_records") == 0) *value = (int64_t)ctx->last4.rcap;
     else if (std::strcmp(key, "workspace_bytes") == 0) {  // device workspace held now (all slots)
@@ -2450,6 +2454,7 @@ int ntc_unpack_streams(ntc_ctx *ctx, const uint8_t *payload, uint64_t payload_by
     if (n_bases) *n_bases = 0;
     ctx->unp_recs = 0;
     ctx->unp_reads = ctx->unp_bases = 0;
+    ctx->unp_path[0] = ctx->unp_path[1] = ctx->unp_path[2] = 0;
     if (n_blocks == 0) return NTC_OK;
     // stream descriptors: word offsets into the payload, value offsets, record offsets
     std::vector<UnpackStream> st(4 * n_blocks);
@@ -2502,9 +2507,9 @@ int ntc_unpack_streams(ntc_ctx *ctx, const uint8_t *payload, uint64_t payload_by
     uint64_t max_recs = 0;
     for (uint64_t b = 0; b < n_blocks; b++) max_recs = std::max<uint64_t>(max_recs, metas[b].stream[2].num_u64);
     const uint64_t segw = unpack_seg_words(n_blocks, max_recs);
-    if ((rc = ensure(ctx, WS_UNP_OUT, n_blocks * 3 * 8 + segw * 8 + 4 * n_blocks * 4 + 8, &d_out))) return rc;
+    if ((rc = ensure(ctx, WS_UNP_OUT, (n_blocks * 3 + 3) * 8 + segw * 8 + 4 * n_blocks * 4 + 8, &d_out))) return rc;
     uint64_t *d_roff = (uint64_t *)((uint8_t *)d_st + st.size() * sizeof(UnpackStream));
-    uint64_t *d_out3 = (uint64_t *)d_out, *d_segc = d_out3 + 3 * n_blocks;
+    uint64_t *d_out3 = (uint64_t *)d_out, *d_segc = d_out3 + 3 * n_blocks + 3;  // (the path words between)
     int32_t *d_sst = (int32_t *)(d_segc + segw);
     HIP_TRY(ctx, hipMemcpyAsync(d_pay, payload, payload_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_st, up.data(), up.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -2531,9 +2536,10 @@ int ntc_unpack_streams(ntc_ctx *ctx, const uint8_t *payload, uint64_t payload_by
     dv.out3 = d_out3;
     launch_unpack(dv, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    std::vector<uint64_t> o3(3 * n_blocks);
-    HIP_TRY(ctx, hipMemcpyAsync(o3.data(), d_out3, 3 * n_blocks * 8, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint64_t> o3(3 * n_blocks + 3);  // out3 and the path words after it, in one copy
+    HIP_TRY(ctx, hipMemcpyAsync(o3.data(), d_out3, (3 * n_blocks + 3) * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 3; i++) ctx->unp_path[i] = o3[3 * n_blocks + i];
     // the blocks before the first damaged one (decode_block's Err ends the reference's loop,
     // main.rs:202); a block the host already found damaged (meta status) ends it as well
     uint64_t ok = 0, rd = 0, bs = 0;

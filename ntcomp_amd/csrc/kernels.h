@@ -178,8 +178,9 @@ struct UnpackPlan {
 void unpack_plan(const UnpackStream *st, uint64_t n_blocks, UnpackPlan &plan);
 uint64_t unpack_ws_bytes(const UnpackPlan &plan);  // the tiles' tables (ws)
 // streams -> values (status[4 b + i]), zip -> records of block b at recs[rec_off[b] ...];
-// out3[3 b .. 3 b + 2] = reads, bases, status.  marks: as many words as the payload; segc:
-// unpack_seg_words(n_blocks, the largest block's records) words
+// out3[3 b .. 3 b + 2] = reads, bases, status, and after the blocks' three words about the
+// Rice paths taken (streams flagged not-simple, serial; segments run through).  marks: as
+// many words as the payload; segc: unpack_seg_words(n_blocks, the largest block's records) words
 struct UnpackDev {
     const uint64_t *payload;
     const UnpackStream *st;

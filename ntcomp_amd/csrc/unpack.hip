@@ -438,8 +438,13 @@ __global__ __launch_bounds__(64) void k_rice_walk(const uint64_t *payload, const
     }
 }
 
+// path[0 .. 2] (the three words after out3, zeroed with it): the call's Rice streams flagged
+// kNotSimple, those flagged kSerial (k_rice_scan), and the active segments a not-simple
+// stream's true chain runs through (k_rice_count) -- what ntc_ctx_get_option reports as
+// "unpack_rice_not_simple" / "unpack_rice_serial" / "unpack_rice_through"
 __global__ __launch_bounds__(kRiceTileSegs) void k_rice_count(const UnpackStream *st, const UnpTile *tiles,
-                                                             const uint64_t *marks, RiceWs w) {
+                                                             const uint64_t *marks, RiceWs w,
+                                                             unsigned long long *path) {
     const RiceSeg x = rice_seg(st, tiles);
     const uint32_t fl = w.flags[x.r];
     if (fl & (kSerial | kBadParam)) return;
@@ -452,14 +457,23 @@ __global__ __launch_bounds__(kRiceTileSegs) void k_rice_count(const UnpackStream
         w.E[x.g] = on ? y : kNoEntry;
     }
     const uint64_t tot = wave_sum(cnt);
-    if (threadIdx.x == 0) w.TSUM[blockIdx.x] = tot;
+    const uint64_t thr = (uint64_t)__popcll(__ballot(x.active && !on));
+    if (threadIdx.x == 0) {
+        w.TSUM[blockIdx.x] = tot;
+        if (thr) atomicAdd(&path[2], (unsigned long long)thr);
+    }
 }
 
 __global__ __launch_bounds__(64) void k_rice_scan(const UnpackStream *st, const UnpStreamRef *rs, int32_t *status,
-                                                 RiceWs w) {
+                                                 RiceWs w, unsigned long long *path) {
     const UnpStreamRef ref = rs[blockIdx.x];
     const UnpackStream s = st[ref.si];
-    if (s.n == 0 || ref.n_tiles == 0 || (w.flags[blockIdx.x] & (kSerial | kBadParam))) return;
+    const uint32_t fl = w.flags[blockIdx.x];
+    if (threadIdx.x == 0) {
+        if (fl & kNotSimple) atomicAdd(&path[0], 1ull);
+        if (fl & kSerial) atomicAdd(&path[1], 1ull);
+    }
+    if (s.n == 0 || ref.n_tiles == 0 || (fl & (kSerial | kBadParam))) return;
     const int lane = threadIdx.x;
     uint64_t base = 0;
     for (uint32_t k0 = 0; k0 < ref.n_tiles; k0 += 64) {
@@ -695,7 +709,9 @@ __global__ __launch_bounds__(kMbTileSegs) void k_mb_decode(const uint64_t *paylo
 }
 
 // The zip runs in segments of kZipSeg records, one workgroup each, so a call's few blocks
-// fill the GPU.  k_zip_count: per segment, its long records and short bases.
+// fill the GPU.  k_zip_count: per segment, its long records and, in one word, the bases every
+// flag's bits 2..7 ask for (low half: they make T) and those of its short records alone (high
+// half: only a short record moves the base cursor, decode.rs:137-139).  Both < 2^18.
 constexpr uint64_t kZipSeg = 4096;
 __global__ __launch_bounds__(kZipThreads) void k_zip_count(const UnpackStream *st, const uint64_t *vals, uint32_t nseg,
                                                           uint64_t *segc) {
@@ -705,9 +721,9 @@ __global__ __launch_bounds__(kZipThreads) void k_zip_count(const UnpackStream *s
     const uint64_t r0 = (uint64_t)g * kZipSeg, r1 = r0 + kZipSeg < s3.n ? r0 + kZipSeg : s3.n;
     uint64_t nl = 0, ns = 0;
     for (uint64_t r = r0 + threadIdx.x; r < r1; r += kZipThreads) {
-        const uint64_t f = fl[r];
+        const uint64_t f = fl[r], len = (f & 0xFC) >> 2;
         nl += !(f & 2);
-        ns += (f & 0xFC) >> 2;  // T counts every flag's bits 2..7 (decode.rs:114)
+        ns += len | ((f & 2) ? len << 32 : 0);  // T counts every flag's bits 2..7 (decode.rs:112)
     }
     nl = wave_sum(nl);
     ns = wave_sum(ns);
@@ -755,9 +771,9 @@ __global__ __launch_bounds__(kZipThreads) void k_zip_write(const UnpackStream *s
             const uint64_t l = segc[2 * ((uint64_t)b * nseg + q)], x = segc[2 * ((uint64_t)b * nseg + q) + 1];
             if (q < g) {
                 li += l;
-                sj += x;
+                sj += x >> 32;
             }
-            T += x;
+            T += x & 0xFFFFFFFFull;
         }
         if (!err && T && s4.n != (T + 30) / 31) err = NTC_ERR_FORMAT;  // short-base chunks
         s_err = err;
@@ -874,6 +890,9 @@ void launch_unpack(const UnpackDev &d, hipStream_t s) {
     // Rice streams
     const RiceWs rw = rice_ws((uint8_t *)d.ws + mb_ws_bytes(d.n_mb_tiles), d.n_rice_tiles, d.n_rice_streams);
     (void)hipMemsetAsync(rw.flags, 0, (uint64_t)d.n_rice_streams * 4, s);
+    // out3 and the three path words after it (k_rice_count and k_rice_scan add into those)
+    unsigned long long *path = (unsigned long long *)d.out3 + 3 * d.n_blocks;
+    (void)hipMemsetAsync(d.out3, 0, (d.n_blocks * 3 + 3) * 8, s);
     if (d.n_rice_tiles) {
         hipLaunchKernelGGL(k_rice_a, dim3(d.n_rice_tiles), dim3(kRiceTileSegs), 0, s, d.payload, d.st, d.rice_tiles,
                            d.marks, rw);
@@ -884,8 +903,8 @@ void launch_unpack(const UnpackDev &d, hipStream_t s) {
                        d.status, rw);
     if (d.n_rice_tiles)
         hipLaunchKernelGGL(k_rice_count, dim3(d.n_rice_tiles), dim3(kRiceTileSegs), 0, s, d.st, d.rice_tiles,
-                           (const uint64_t *)d.marks, rw);
-    hipLaunchKernelGGL(k_rice_scan, dim3(d.n_rice_streams), dim3(64), 0, s, d.st, d.rice_streams, d.status, rw);
+                           (const uint64_t *)d.marks, rw, path);
+    hipLaunchKernelGGL(k_rice_scan, dim3(d.n_rice_streams), dim3(64), 0, s, d.st, d.rice_streams, d.status, rw, path);
     if (d.n_rice_tiles)
         hipLaunchKernelGGL(k_rice_decode, dim3(d.n_rice_tiles), dim3(kRiceTileSegs), 0, s, d.payload, d.st,
                            d.rice_tiles, d.vals, d.status, rw);
@@ -904,7 +923,6 @@ void launch_unpack(const UnpackDev &d, hipStream_t s) {
     if (nt)
         hipLaunchKernelGGL(k_mb_decode, dim3(d.n_mb_tiles), dim3(kMbTileSegs), 0, s, d.payload, d.st, d.mb_tiles, X, C,
                            TE, TP, d.vals, d.status);
-    (void)hipMemsetAsync(d.out3, 0, d.n_blocks * 3 * 8, s);
     hipLaunchKernelGGL(k_zip_count, dim3((uint32_t)(d.n_blocks * nseg)), dim3(kZipThreads), 0, s, d.st, d.vals, nseg,
                        d.segc);
     hipLaunchKernelGGL(k_zip_write, dim3((uint32_t)(d.n_blocks * nseg)), dim3(kZipThreads), 0, s, d.st, d.vals,
