@@ -367,6 +367,84 @@ int ntc_n_write_section(int fd, const ntc_name_meta *meta, const uint8_t *payloa
 int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_blocks, uint8_t **payload,
                uint64_t *payload_bytes);
 
+/* ---- per-block content digests -------------------------------------------------------------- */
+/* ntc_ctx_set_option(ctx, "digests", 1) (default 0: nothing is launched) makes
+ * ntc_encode_pack_fastq and ntc_encode_pack_batch also digest, on the GPU, what each block of
+ * block_reads reads holds, so that a decode can check that it gave the same bytes back.  All
+ * arithmetic is modulo 2^64:
+ *   mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;
+ *            x ^= x >> 31
+ *   K0 = 0xD6E8FEB86659FD93, K1 = 0x9E3779B97F4A7C15
+ *   h(s), s a string of n bytes:  w_j = the little-endian u64 of s[8j .. 8j + 8), zero-padded
+ *            past n;  h(s) = mix((n + 1) K0 + sum_j mix(w_j + (j + 1) K1))
+ *   D(s_0 .. s_{m-1}) = sum_i mix(h(s_i) + (i + 1) K1),  i = the read's index inside the block
+ * It guards against accident (another index, a damaged or truncated file, an unmatched side
+ * file), not against an adversary.  A block has one D per component; s_i is
+ *   NTC_DIGEST_SEQ   the read's bases as the records hold them: after the non-ACGT pass has put
+ *                    in the substitute base.  Always present.
+ *   NTC_DIGEST_SYM   the read's symbols before that pass.  Present under non_acgt 2 (keep).
+ *   NTC_DIGEST_QUAL  the quality bytes as a decode prints them (after bin8's mapping).  Present
+ *                    under qualities 1 and 2 (ntc_encode_pack_fastq only).
+ *   NTC_DIGEST_NAME  the name as a decode prints it (after id's cut).  Present under names 1 and
+ *                    2 (ntc_encode_pack_fastq only).                                          */
+#define NTC_DIGEST_SEQ 1u
+#define NTC_DIGEST_SYM 2u
+#define NTC_DIGEST_QUAL 4u
+#define NTC_DIGEST_NAME 8u
+typedef struct ntc_digest_meta {
+    uint64_t n_reads;    /* reads of the block                                             */
+    uint64_t n_bases;    /* their bases                                                    */
+    uint64_t d_seq;      /* the component digests; 0 for a component that is not present   */
+    uint64_t d_sym;
+    uint64_t d_qual;
+    uint64_t d_name;
+    uint32_t components; /* NTC_DIGEST_* bits: present (encode, expected) / checked (decode) */
+    uint32_t reserved;   /* 0                                                              */
+} ntc_digest_meta;       /* 56 bytes */
+/* The digests of the last ntc_encode_pack_fastq or ntc_encode_pack_batch call on this context
+ * with "digests" 1, one entry per block (none with "digests" 0, or when that call failed).
+ * *n_blocks = their number; NTC_ERR_CAPACITY (nothing copied) when cap is smaller.          */
+int ntc_encode_digests(ntc_ctx *ctx, ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks);
+/* Expected digests (copied) for the next ntc_decode_fasta or ntc_decode_fasta_unpacked call on
+ * this context: entry i covers the next metas[i].n_reads reads of that call, which digests on
+ * the GPU what it decoded -- seq right after the walk, sym after the exception runs went in
+ * (only when runs were pending), qual and name after their sections were expanded (only when
+ * those were pending) -- and compares there every component it could compute whose bit the
+ * entry has.  A block whose bases count or digest differs makes the call return
+ * NTC_ERR_DIGEST and write no text; ntc_last_error names the block, the component and both
+ * values.  NTC_ERR_FORMAT when the entries do not cover exactly the call's reads.  Checked
+ * here, NTC_ERR_INVALID_ARG: a bit outside NTC_DIGEST_*, a missing NTC_DIGEST_SEQ, a non-zero
+ * digest of an absent component, reserved != 0.  The entries are dropped by the call that
+ * used them, whatever it returned (a call that only reports sizes keeps them);
+ * ntc_decode_batch and ntc_decode_batch_device ignore them.  n_blocks = 0 drops them.      */
+int ntc_decode_set_digests(ntc_ctx *ctx, const ntc_digest_meta *metas, uint64_t n_blocks);
+/* What the last ntc_decode_fasta / ntc_decode_fasta_unpacked call that was given expected
+ * digests computed, also after NTC_ERR_DIGEST: entry i has that block's reads, bases and the
+ * digests of the components it could check (components says which; the others are 0).
+ * Capacity protocol as above.
+ * A verification pass needs no text: with ntc_ctx_set_option(ctx, "discard_text", 1) (default
+ * 0) ntc_decode_fasta and ntc_decode_fasta_unpacked run as ever, the formatter included, but do
+ * not copy the text to the host; out may then be NULL and out_capacity 0, and *out_len is
+ * still the text's size.                                                                    */
+int ntc_decode_digests(ntc_ctx *ctx, ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks);
+
+/* ---- digest side file ("NTCD", version 1) --------------------------------------------------- */
+/* The digests of an encoded.dat, beside it.  Everything little-endian, nothing deflated:
+ *   header, 32 bytes: "NTCD", u32 version = 1, u8 components (the union over the file), 3 zero
+ *     bytes, u32 k and u64 n_nodes of the index it was written against (ntc_index_info), 8 zero
+ *     bytes
+ *   one 56-byte ntc_digest_meta per block of encoded.dat, until the end of the file
+ * ntc_d_read refuses with NTC_ERR_FORMAT: a bad magic or version, non-zero padding, a length
+ * that is not 32 + 56 m, a component bit outside the header's (or a header without
+ * NTC_DIGEST_SEQ, or a section without it), a non-zero digest of an absent component.
+ * ntc_d_write_header / ntc_d_write_section refuse the same with NTC_ERR_INVALID_ARG (a
+ * section is checked against NTC_DIGEST_* alone; its reader checks it against the header).
+ * *metas is malloc'ed (free() it; NULL when there is no section).                           */
+int ntc_d_write_header(int fd, uint32_t components, uint32_t k, uint64_t n_nodes);
+int ntc_d_write_section(int fd, const ntc_digest_meta *meta);
+int ntc_d_read(const char *path, uint32_t *components, uint32_t *k, uint64_t *n_nodes, ntc_digest_meta **metas,
+               uint64_t *n_blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,7 +54,8 @@ typedef enum ntc_status {
     NTC_ERR_FORMAT = 8,
     NTC_ERR_IO = 9,
     NTC_ERR_UNSUPPORTED = 10,
-    NTC_ERR_REFERENCE_PANIC = 11
+    NTC_ERR_REFERENCE_PANIC = 11,
+    NTC_ERR_DIGEST = 12 /* decode: a block's content digest differs (ntcomp_codec.h) */
 } ntc_status;
 
 typedef struct ntc_ctx ntc_ctx;

@@ -179,6 +179,62 @@ int ntc_encode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
 int ntc_decode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts2 *fo,
                         const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats);
 
+/* ---- the digest file: a decode that checks itself ------------------------------------------- */
+/* ntc_encode_file_ex3 / ntc_decode_file_ex3 are ntc_encode_file_ex2 / ntc_decode_file_ex2 with
+ * the per-block content digests of ntcomp_codec.h beside the three side files.  ntc_file_opts3
+ * holds ntc_file_opts2's fields in the same order, then its own; struct_bytes must be at least
+ * sizeof(ntc_file_opts3) as declared here, else NTC_ERR_INVALID_ARG.
+ * Encode: d_mode 0: no digest file, d_fd must be -1.  d_mode 1: every block written to
+ * encoded.dat gets its 56-byte section in the "NTCD" file at d_fd (>= 0, not closed), in file
+ * order, digested on the GPU from the bytes the call has there anyway; a block the pipeline
+ * drops takes its section with it.  The header names the uploaded index (k, n_nodes) and the
+ * components the call's modes yield: seq always, sym under NTC_NX_KEEP, qual under q_mode 1 / 2,
+ * name under n_mode 1 / 2.  It works with every policy, mode and input kind; encoded.dat and the
+ * other side files are byte for byte those of a run without it, and the file does not depend on
+ * the number of contexts or on whether the same text came plain or compressed.  The contexts'
+ * "digests" option is set for the call and left at 0.  d (may be NULL): sections written, and
+ * how many of them hold each component.
+ * Decode: d_path (NULL: none) = the "NTCD" file, read once (ntc_d_read).  A file whose k or
+ * n_nodes are not the uploaded index's fails before the first batch with NTC_ERR_DIGEST and
+ * "written against another index" in stats->error.  Section i belongs to block i of
+ * encoded.dat; each batch is checked on the GPU before its text is formatted.  A block that
+ * differs ends the call with NTC_ERR_DIGEST: stats->bad_read = the block's first read (from 0,
+ * as decode numbers them), stats->error names the block, the component and both values, and the
+ * output is a prefix of the true text (the batches before that block's).  Under a digest file
+ * the lenient endings of ntc_decode_file are errors: a damaged block or a truncated input is
+ * NTC_ERR_FORMAT, not NTC_OK with dropped_blocks > 0, and so are sections left over after a
+ * clean end.  A component whose side file is not given (sym: nx_path, qual: q_path, name:
+ * n_path) cannot be checked; d->not_checkable collects those bits.  d (may be NULL): sections
+ * used, and how many blocks were checked for each component.
+ * out_fd = -1 (here only): everything runs, the formatter included, but the text is neither
+ * copied off the device nor written -- a verification pass.                                     */
+typedef struct ntc_file_opts3 {
+    uint32_t struct_bytes; /* sizeof(ntc_file_opts3)                           */
+    int32_t nx_policy;     /* NTC_NX_*                                         */
+    int32_t nx_fd;         /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;        /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;          /* encode: quality file, -1 = none                  */
+    const char *nx_path;   /* decode: exceptions file, NULL = none             */
+    const char *q_path;    /* decode: quality file, NULL = none                */
+    int32_t n_mode;        /* 0 drop, 1 keep, 2 id                             */
+    int32_t n_fd;          /* encode: name file, -1 = none                     */
+    const char *n_path;    /* decode: name file, NULL = none                   */
+    int32_t d_mode;        /* 0 none, 1 write digests                          */
+    int32_t d_fd;          /* encode: digest file, -1 = none                   */
+    const char *d_path;    /* decode: digest file, NULL = none                 */
+} ntc_file_opts3;
+typedef struct ntc_d_stats {
+    uint64_t sections;                                      /* written (encode) / checked (decode)  */
+    uint64_t blocks_seq, blocks_sym, blocks_qual, blocks_name; /* of them, with / checked for each  */
+    uint32_t not_checkable;                                 /* decode: NTC_DIGEST_* present, not checked */
+    uint32_t reserved;
+} ntc_d_stats;
+int ntc_encode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts3 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n, ntc_d_stats *d);
+int ntc_decode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts3 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d);
+
 #ifdef __cplusplus
 }
 #endif

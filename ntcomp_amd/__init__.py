@@ -29,6 +29,7 @@ STATUS = {
     0: "NTC_OK", 1: "NTC_ERR_INVALID_ARG", 2: "NTC_ERR_INVALID_BASE", 3: "NTC_ERR_EMPTY_READ",
     4: "NTC_ERR_LENGTH", 5: "NTC_ERR_CAPACITY", 6: "NTC_ERR_HIP", 7: "NTC_ERR_NO_INDEX",
     8: "NTC_ERR_FORMAT", 9: "NTC_ERR_IO", 10: "NTC_ERR_UNSUPPORTED", 11: "NTC_ERR_REFERENCE_PANIC",
+    12: "NTC_ERR_DIGEST",
 }
 
 # every symbol include/ntcomp_gpu.h and include/ntcomp_host.h declare
@@ -53,6 +54,8 @@ EXPORTED = [
     "ntc_q_write_section", "ntc_q_read", "ntc_encode_file_ex", "ntc_decode_file_ex",
     "ntc_encode_names", "ntc_decode_set_names", "ntc_n_write_header", "ntc_n_deflate_section",
     "ntc_n_write_section", "ntc_n_read", "ntc_encode_file_ex2", "ntc_decode_file_ex2",
+    "ntc_encode_digests", "ntc_decode_set_digests", "ntc_decode_digests", "ntc_d_write_header",
+    "ntc_d_write_section", "ntc_d_read", "ntc_encode_file_ex3", "ntc_decode_file_ex3",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -132,6 +135,20 @@ class NameMeta(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("n_reads", "name_bytes", "mid_bytes", "payload_off", "payload_bytes")]
 
 
+# digest components (ntc_digest_meta.components, include/ntcomp_codec.h)
+DIGEST_SEQ, DIGEST_SYM, DIGEST_QUAL, DIGEST_NAME = 1, 2, 4, 8
+DIGEST_COMPONENTS = ("seq", "sym", "qual", "name")
+
+
+class DigestMeta(ctypes.Structure):
+    """ntc_digest_meta (include/ntcomp_codec.h): the content digests of one block."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_reads", "n_bases", "d_seq", "d_sym", "d_qual", "d_name")] + \
+               [("components", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 DEFLATE_ENGINES = {"zlib": 0, "libdeflate": 1, "adaptive": 2}  # NTC_DEFLATE_* (include/ntcomp_codec.h)
 
 
@@ -171,6 +188,20 @@ class FileOpts2(ctypes.Structure):
                 ("q_mode", ctypes.c_int32), ("q_fd", ctypes.c_int32), ("nx_path", ctypes.c_char_p),
                 ("q_path", ctypes.c_char_p), ("n_mode", ctypes.c_int32), ("n_fd", ctypes.c_int32),
                 ("n_path", ctypes.c_char_p)]
+
+
+class FileOpts3(ctypes.Structure):
+    """ntc_file_opts3 (include/ntcomp_pipeline.h): the three side files and the digest file."""
+    _fields_ = FileOpts2._fields_ + [("d_mode", ctypes.c_int32), ("d_fd", ctypes.c_int32), ("d_path", ctypes.c_char_p)]
+
+
+class DStats(ctypes.Structure):
+    """ntc_d_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("sections", "blocks_seq", "blocks_sym", "blocks_qual", "blocks_name")] + \
+               [("not_checkable", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class NStats(ctypes.Structure):
@@ -332,11 +363,23 @@ def lib():
         "ntc_n_write_section": (I, [I, P, P, I]),
         "ntc_n_read": (I, [ctypes.c_char_p, ctypes.POINTER(I), ctypes.POINTER(P), ctypes.POINTER(u64),
                            ctypes.POINTER(P), ctypes.POINTER(u64)]),
+        "ntc_encode_digests": (I, [P, P, u64, ctypes.POINTER(u64)]),
+        "ntc_decode_set_digests": (I, [P, P, u64]),
+        "ntc_decode_digests": (I, [P, P, u64, ctypes.POINTER(u64)]),
+        "ntc_d_write_header": (I, [I, u32, u32, u64]),
+        "ntc_d_write_section": (I, [I, P]),
+        "ntc_d_read": (I, [ctypes.c_char_p, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64),
+                           ctypes.POINTER(P), ctypes.POINTER(u64)]),
         "ntc_encode_file_ex2": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts2), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
                                     ctypes.POINTER(NStats)]),
         "ntc_decode_file_ex2": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts2), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats)]),
+        "ntc_encode_file_ex3": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts3), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
+                                    ctypes.POINTER(NStats), ctypes.POINTER(DStats)]),
+        "ntc_decode_file_ex3": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts3), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats)]),
         "ntc_nx_write": (I, [I, P, u64, u32, I]),
         "ntc_nx_read": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "ntc_encode_file_nx": (I, [P, I, ctypes.c_char_p, I, I, I, ctypes.POINTER(PipelineOpts),
@@ -642,6 +685,45 @@ class GpuContext:
         self._check(self.L.ntc_decode_set_names(self.h, arr, len(metas), _p(buf), len(payload)),
                     "ntc_decode_set_names")
 
+    # ---- content digests ---------------------------------------------------------------
+    @property
+    def digests(self):
+        """Option "digests": 1 makes encode_pack and encode_pack_fastq digest every block on the GPU."""
+        return self.get_option("digests")
+
+    @digests.setter
+    def digests(self, on):
+        self.set_option("digests", 1 if on else 0)
+
+    def _digests(self, digests):
+        return GpuContext._Option(self, "digests", None if digests is None else (1 if digests else 0))
+
+    def _digest_table(self, fn, what):
+        nb = ctypes.c_uint64()
+        rc = fn(self.h, None, 0, ctypes.byref(nb))
+        if rc not in (0, 5):
+            self._check(rc, what)
+        metas = (DigestMeta * max(nb.value, 1))()
+        if nb.value:
+            self._check(fn(self.h, metas, nb.value, ctypes.byref(nb)), what)
+        return list(metas)[:nb.value]
+
+    def encode_digests(self):
+        """The digests of the last encode_pack / encode_pack_fastq call with digests on
+        (ntc_encode_digests) -> list of DigestMeta, one per block."""
+        return self._digest_table(self.L.ntc_encode_digests, "ntc_encode_digests")
+
+    def decode_set_digests(self, metas):
+        """Expected digests (DigestMeta, in read order) for the next decode_fasta_unpacked call, which
+        then checks what it decoded against them on the GPU (ntc_decode_set_digests)."""
+        arr = (DigestMeta * max(len(metas), 1))(*metas)
+        self._check(self.L.ntc_decode_set_digests(self.h, arr, len(metas)), "ntc_decode_set_digests")
+
+    def decode_digests(self):
+        """What the last decode call that was given expected digests computed, also after
+        NTC_ERR_DIGEST (ntc_decode_digests); components says which were checked."""
+        return self._digest_table(self.L.ntc_decode_digests, "ntc_decode_digests")
+
     def exceptions(self):
         """The exception runs of the last encode / encode_pack / encode_pack_fastq call under
         policy keep (ntc_encode_exceptions), as a structured array of dtype NX_RUN in (read,
@@ -748,11 +830,12 @@ class GpuContext:
                                                   ctypes.byref(used)), "ntc_pack_blocks_device")
         return list(metas)[:nb], int(used.value)
 
-    def encode_pack(self, bases, offsets, block_reads=65536, non_acgt=None):
+    def encode_pack(self, bases, offsets, block_reads=65536, non_acgt=None, digests=None):
         """Reads -> packed blocks (ntc_encode_pack_batch): the records stay in HBM and the
         GPU packer writes each block's four streams; returns (list of BlockMeta, payload
         bytes) ready for deflate_block.  With non_acgt (as for encode) the exception runs
-        come third."""
+        come third.  With digests (True / False; the call runs under it) the blocks' DigestMeta
+        come last, as encode_digests() returns them."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nreads = len(offsets) - 1
@@ -760,7 +843,7 @@ class GpuContext:
         metas = (BlockMeta * max(nb, 1))()
         out, used, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_int64(-1)
         b = bases if len(bases) else np.zeros(1, dtype=np.uint8)
-        with self._policy(non_acgt):
+        with self._policy(non_acgt), self._digests(digests):
             rc = self.L.ntc_encode_pack_batch(self.h, _p(b), _p(offsets), nreads, block_reads, metas,
                                               ctypes.byref(out), ctypes.byref(used), ctypes.byref(bad))
         if rc:
@@ -771,9 +854,12 @@ class GpuContext:
             payload = ctypes.string_at(out.value, used.value) if used.value else b""
         finally:
             self.L.ntc_buffer_free(out)
+        out = (list(metas)[:nb], payload)
         if non_acgt is not None:
-            return list(metas)[:nb], payload, self.exceptions()
-        return list(metas)[:nb], payload
+            out += (self.exceptions(),)
+        if digests is not None:
+            out += (self.encode_digests(),)
+        return out
 
     def parse_fastq(self, text, n_reads):
         """Plain FASTQ text of exactly n_reads 4-line records -> (bases, offsets), parsed on
@@ -791,18 +877,21 @@ class GpuContext:
         return bases[:nb.value].copy(), offs
 
     def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None, names=None,
-                          quality_coder=None):
+                          quality_coder=None, digests=None):
         """encode_pack on FASTQ text parsed on the GPU (ntc_encode_pack_fastq) -> (list of
         BlockMeta, payload bytes, bases encoded).  With non_acgt (as for encode) the exception
         runs come fourth.  With qualities ("drop", "keep" or "bin8"; the call runs under that
         mode) the quality sections come next, as qualities() returns them, and with names ("drop",
         "keep" or "id") the name sections come last, as names() returns them.  quality_coder ("pack" or
-        "rans"; the call runs under it): the coder of the quality sections."""
+        "rans"; the call runs under it): the coder of the quality sections.  With digests (True / False;
+        the call runs under it) the blocks' DigestMeta come after all of those, as encode_digests()
+        returns them."""
         t = np.frombuffer(bytes(text), dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
         nb = (n_reads + block_reads - 1) // block_reads
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
-        with self._policy(non_acgt), self._qmode(qualities), self._nmode(names), self._qcoder(quality_coder):
+        with self._policy(non_acgt), self._qmode(qualities), self._nmode(names), self._qcoder(quality_coder), \
+                self._digests(digests):
             rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas,
                                               ctypes.byref(out), ctypes.byref(used), ctypes.byref(nbases),
                                               ctypes.byref(bad))
@@ -822,6 +911,8 @@ class GpuContext:
             out += (self.qualities(),)
         if names is not None:
             out += (self.names(),)
+        if digests is not None:
+            out += (self.encode_digests(),)
         return out
 
     def encode_status(self):
@@ -1083,7 +1174,7 @@ def concat_streams(blocks):
 
 # ---- FASTX ingest ---------------------------------------------------------------------
 def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_bases=0, deflate="zlib",
-                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1, names=None, n_fd=-1):
+                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1, names=None, n_fd=-1, d_fd=None):
     """`ntcomp encode` file to file (ntc_encode_file, include/ntcomp_pipeline.h): FASTX ->
     GPU encode + block packer on every context -> deflate pool -> encoded.dat on out_fd.
     A plain FASTQ is parsed on the GPU unless host_parse.  Returns the per-stage stats as
@@ -1093,8 +1184,23 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     (ntc_nx_stats).  qualities ("drop", "keep", "bin8"; ntc_encode_file_ex): "keep" and "bin8"
     write the blocks' quality sections to q_fd ("NTCQ"), and the stats gain a "q" dict
     (ntc_q_stats).  names ("drop", "keep", "id"; ntc_encode_file_ex2): "keep" and "id" write the
-    blocks' name sections to n_fd ("NTCN"), and the stats gain an "n" dict (ntc_n_stats)."""
+    blocks' name sections to n_fd ("NTCN"), and the stats gain an "n" dict (ntc_n_stats).  d_fd (None:
+    no digests; ntc_encode_file_ex3): the blocks' content digests, computed on the GPU, go to that
+    descriptor ("NTCD"), and the stats gain a "d" dict (ntc_d_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
+    if d_fd is not None:
+        fo = FileOpts3(ctypes.sizeof(FileOpts3), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
+                       None, None, _names_code(names or 0), n_fd, None, 1, d_fd, None)
+        nx, q, n, ds = NxStats(), QStats(), NStats(), DStats()
+        d = _run_pipeline("ntc_encode_file_ex3", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                          tail=(ctypes.byref(nx), ctypes.byref(q), ctypes.byref(n), ctypes.byref(ds)))
+        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
+        if qualities is not None:
+            d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
+        if names is not None:
+            d["n"] = {k: int(getattr(n, k)) for k, _ in NStats._fields_}
+        d["d"] = ds.as_dict()
+        return d
     if names is not None:
         fo = FileOpts2(ctypes.sizeof(FileOpts2), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
                        None, None, _names_code(names), n_fd, None)
@@ -1123,7 +1229,8 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     return d
 
 
-def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None, n_path=None):
+def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None, n_path=None,
+                d_path=None):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
@@ -1133,8 +1240,25 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
     (ntc_decode_file_nx).  q_path: the quality side file written by encode_file(qualities=
     "keep" / "bin8"); the output is then FASTQ (ntc_decode_file_ex).  n_path: the name side file
     written by encode_file(names="keep" / "id"); the reads then carry their names instead of
-    seq.N (ntc_decode_file_ex2)."""
+    seq.N (ntc_decode_file_ex2).  d_path: the digest file written by encode_file(d_fd=...): every
+    block is checked on the GPU against it (ntc_decode_file_ex3); NtcError(NTC_ERR_DIGEST) with
+    .bad_read = the first read of the block that differs, or for a file written against another
+    index; a damaged or truncated input is then NTC_ERR_FORMAT; the stats gain a "d" dict
+    (ntc_d_stats).  With d_path, out_fd -1 checks without copying or writing the text."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
+    if d_path is not None:
+        enc = lambda p: None if p is None else os.fsencode(p)
+        fo = FileOpts3(ctypes.sizeof(FileOpts3), 0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1,
+                       enc(d_path))
+        ds = DStats()
+        try:
+            d = _run_pipeline("ntc_decode_file_ex3", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                              tail=(ctypes.byref(ds),))
+        except NtcError as e:
+            e.stats["d"] = ds.as_dict()
+            raise
+        d["d"] = ds.as_dict()
+        return d
     if n_path is not None:
         fo = FileOpts2(ctypes.sizeof(FileOpts2), 0, -1, 0, -1, None if nx_path is None else os.fsencode(nx_path),
                        None if q_path is None else os.fsencode(q_path), 0, -1, os.fsencode(n_path))
@@ -1234,6 +1358,36 @@ def write_names(fd, mode, metas, payload, header=True, engine="libdeflate"):
                                        DEFLATE_ENGINES[engine])
         if rc:
             raise NtcError(rc, "ntc_n_write_section")
+
+
+def read_digests(path):
+    """The digest side file ("NTCD", include/ntcomp_codec.h) written beside an encoded.dat:
+    ntc_d_read -> (components, k, n_nodes, list of DigestMeta); NtcError(NTC_ERR_FORMAT) for a
+    malformed file."""
+    comp, k, n, pm, nb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_uint64()
+    rc = lib().ntc_d_read(os.fsencode(path), ctypes.byref(comp), ctypes.byref(k), ctypes.byref(n), ctypes.byref(pm),
+                          ctypes.byref(nb))
+    if rc:
+        raise NtcError(rc, f"ntc_d_read({path})")
+    try:
+        size = ctypes.sizeof(DigestMeta)
+        metas = [DigestMeta.from_buffer_copy(ctypes.string_at(pm.value + i * size, size)) for i in range(nb.value)]
+    finally:
+        lib().ntc_buffer_free(pm)
+    return int(comp.value), int(k.value), int(n.value), metas
+
+
+def write_digests(fd, components, k, n_nodes, metas, header=True):
+    """The "NTCD" header (when header) and one section per DigestMeta to fd (ntc_d_write_header,
+    ntc_d_write_section)."""
+    if header:
+        rc = lib().ntc_d_write_header(fd, components, k, n_nodes)
+        if rc:
+            raise NtcError(rc, "ntc_d_write_header")
+    for m in metas:
+        rc = lib().ntc_d_write_section(fd, ctypes.byref(m))
+        if rc:
+            raise NtcError(rc, "ntc_d_write_section")
 
 
 def write_exceptions(fd, runs, sub, header=True):

@@ -202,6 +202,23 @@ def _check_n_args(args):
         _bad_args("encode: --name-file is only written under --names keep or id")
 
 
+def _check_d_args(args, command, others):
+    """--digest-file PATH: not empty, and no file the same call reads or writes."""
+    d = args.digest_file
+    if d is None:
+        if command == "verify":
+            _bad_args("verify: --digest-file PATH is required")
+        return
+    if d == "":
+        _bad_args(f"{command}: --digest-file needs a path")
+    if any(o is not None and o == d for o in others):
+        _bad_args(f"{command}: --digest-file names a file this call uses already: {d}")
+
+
+def _component_names(mask):
+    return ",".join(n for c, n in enumerate(("seq", "sym", "qual", "name")) if mask >> c & 1) or "-"
+
+
 def cmd_encode(args):
     """main.rs:141-181 through the native pipeline (ntc_encode_file): plain FASTQ parsed
     on the GPU (--host-parse: on the host pool, as every other input is), GPU encode +
@@ -209,6 +226,7 @@ def cmd_encode(args):
     _check_nx_args(args)
     _check_q_args(args)
     _check_n_args(args)
+    _check_d_args(args, "encode", (args.exceptions, args.quality_file, args.name_file, args.query_file))
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     log("Loading SBWT index...")
@@ -219,8 +237,13 @@ def cmd_encode(args):
         args.deflate = "adaptive" if nt.libdeflate_available() else "zlib"
     out = sys.stdout.buffer
     out.flush()
-    nx_file = q_file = n_file = None
+    nx_file = q_file = n_file = d_file = None
     try:
+        if args.digest_file is not None:
+            try:
+                d_file = open(args.digest_file, "wb")
+            except OSError:
+                raise SystemExit(f"ntcomp: encode: cannot write {args.digest_file}")
         if args.names != "drop":
             try:
                 n_file = open(args.name_file, "wb")
@@ -244,6 +267,8 @@ def cmd_encode(args):
                 c.quality_coder = args.quality_coder or "pack"
         if n_file:
             nx_args.update(names=args.names, n_fd=n_file.fileno())
+        if d_file:
+            nx_args.update(d_fd=d_file.fileno())
         res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, deflate=args.deflate,
                                                   host_parse=args.host_parse, **nx_args)
@@ -257,6 +282,8 @@ def cmd_encode(args):
             q_file.close()
         if n_file:
             n_file.close()
+        if d_file:
+            d_file.close()
         for c in ctxs:
             c.close()
     if res["dropped_blocks"]:
@@ -272,26 +299,33 @@ def cmd_encode(args):
                                                                         "runs_in_dropped_blocks"), 0)).items()},
               **({"qualities": args.qualities, "quality_coder": args.quality_coder or "pack",
                   **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}),
-              **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}))
+              **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}),
+              **({"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"} if "d" in res else {}))
 
 
-def cmd_decode(args):
+def cmd_decode(args, verify=False):
     """main.rs:183-211 through the native pipeline (ntc_decode_file): blocks inflated and
     stream-decoded on the host pool, inverse-SBWT walk + FASTA formatting per context on the
-    GPU, ">seq.N" text written in file order."""
+    GPU, ">seq.N" text written in file order.  verify: the same with every block checked against
+    the --digest-file and no text copied off the device or written; one line on stdout."""
+    command = "verify" if verify else "decode"
+    _check_d_args(args, command, (args.exceptions, args.quality_file, args.name_file, args.input_path))
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     index = st.wrap("index_load", nt.Index.load)(args.index_prefix)
     ctxs = _open_gpus(index, _devices(args), st, args.contexts_per_gpu, decode_only=True)
-    log("Decoding encoded data...")
+    log("Verifying encoded data..." if verify else "Decoding encoded data...")
     out = sys.stdout.buffer
     out.flush()
     try:
-        res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, out.fileno(), threads=args.threads,
-                                                  blocks_per_batch=args.blocks_per_batch, nx_path=args.exceptions,
-                                                  q_path=args.quality_file, n_path=args.name_file)
+        res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, -1 if verify else out.fileno(),
+                                                  threads=args.threads, blocks_per_batch=args.blocks_per_batch,
+                                                  nx_path=args.exceptions, q_path=args.quality_file,
+                                                  n_path=args.name_file, d_path=args.digest_file)
     except nt.NtcError as e:
-        raise SystemExit(f"ntcomp decode: {e}")
+        bad = getattr(e, "bad_read", -1)
+        raise SystemExit(f"ntcomp {command}: {e}" + (f" (read {bad + 1})" if e.code == 12 and bad is not None and bad >= 0
+                                                     else ""))
     finally:
         for c in ctxs:
             c.close()
@@ -301,8 +335,15 @@ def cmd_decode(args):
     if st.on:
         for k, name in (("parse_s", "unzip"), ("gpu_s", "gpu"), ("write_s", "write")):
             st.acc[name] = res[k]
-    st.report(command="decode", gpus=len(ctxs), threads=res["threads"], reads=res["reads"], blocks=res["blocks"],
-              pipeline_wall_s=round(res["wall_s"], 3))
+    if verify:
+        d = res["d"]
+        checked = sum(1 << c for c, k in enumerate(("blocks_seq", "blocks_sym", "blocks_qual", "blocks_name")) if d[k])
+        print(f"verify: OK: {d['sections']} blocks, {res['reads']} reads, checked {_component_names(checked)}, "
+              f"not checkable {_component_names(d['not_checkable'])}", flush=True)
+    st.report(command=command, gpus=len(ctxs), threads=res["threads"], reads=res["reads"], blocks=res["blocks"],
+              pipeline_wall_s=round(res["wall_s"], 3),
+              **({**{"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"},
+                  "d_not_checkable": _component_names(res["d"]["not_checkable"])} if "d" in res else {}))
 
 
 def main(argv=None):
@@ -370,6 +411,8 @@ def main(argv=None):
                         "to its first space or tab, lossy); keep and id write them, front-coded on the GPU, to the "
                         "--name-file")
     e.add_argument("--name-file", metavar="PATH", help="with --names keep or id: the side file to write")
+    e.add_argument("--digest-file", metavar="PATH",
+                   help="also write per-block content digests, computed on the GPU, for decode / verify --digest-file")
     d = sub.add_parser("decode", help="Decode data written with Encode")
     d.add_argument("input_path", help="File with encoded fastX data.")
     d.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
@@ -386,6 +429,24 @@ def main(argv=None):
                    help="the side file of encode --names keep or id: the reads carry their names instead of seq.N")
     d.add_argument("--exceptions", metavar="PATH",
                    help="the side file of encode --non-acgt keep, whose symbols are put back")
+    d.add_argument("--digest-file", metavar="PATH",
+                   help="the digest file of encode --digest-file: every block is checked against it on the GPU; another "
+                        "index, a damaged or truncated file or a side file of another run is an error that names the "
+                        "block and the component")
+    v = sub.add_parser("verify", help="Check encoded data against its digest file without writing the text")
+    v.add_argument("input_path", help="File with encoded fastX data.")
+    v.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
+    v.add_argument("--gpus", type=int, default=1, help="GPUs to decode on (batches dealt round-robin).")
+    v.add_argument("--devices", help="comma-separated device list, one context each; overrides --gpus")
+    v.add_argument("--threads", type=int, default=0, help="block unzip threads (0: CPUs available)")
+    v.add_argument("--contexts-per-gpu", type=int, default=DECODE_CONTEXTS_PER_GPU,
+                   help="contexts per device sharing one index copy; calls alternate over them")
+    v.add_argument("--blocks-per-batch", type=int, default=2, help="blocks per GPU call")
+    v.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
+    v.add_argument("--digest-file", metavar="PATH", help="the digest file of encode --digest-file (required)")
+    v.add_argument("--quality-file", metavar="PATH", help="the side file of encode --qualities keep or bin8")
+    v.add_argument("--name-file", metavar="PATH", help="the side file of encode --names keep or id")
+    v.add_argument("--exceptions", metavar="PATH", help="the side file of encode --non-acgt keep")
     args = ap.parse_args(argv)
     if getattr(args, "threads", None) == 0:
         import ntcomp_amd as nt
@@ -396,6 +457,8 @@ def main(argv=None):
         cmd_encode(args)
     elif args.command == "decode":
         cmd_decode(args)
+    elif args.command == "verify":
+        cmd_decode(args, verify=True)
     else:
         ap.print_help()
     return 0

@@ -52,6 +52,7 @@
 #include "qrans_core.h"
 #include "quality_core.h"
 #include "names_core.h"
+#include "digest_core.h"
 
 namespace {
 
@@ -1225,6 +1226,78 @@ int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_b
     *mode = buf[8];
     *n_blocks = all.size();
     *payload_bytes = pay.size();
+    return NTC_OK;
+}
+
+}  // extern "C"
+
+// ---- digest side file "NTCD" (include/ntcomp_codec.h) ---------------------------------
+namespace {
+static_assert(sizeof(ntc_digest_meta) == 56, "a section is the meta as it stands");
+// a meta on its own: known bits, seq among them, nothing set for an absent component
+bool d_meta_ok(const ntc_digest_meta &m) {
+    if ((m.components & ~ntc::kDgAll) || !(m.components & ntc::kDgSeq) || m.reserved) return false;
+    const uint64_t d[4] = {m.d_seq, m.d_sym, m.d_qual, m.d_name};
+    for (uint32_t c = 0; c < 4; c++)
+        if (!(m.components >> c & 1) && d[c]) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int ntc_d_write_header(int fd, uint32_t components, uint32_t k, uint64_t n_nodes) {
+    if (fd < 0 || (components & ~ntc::kDgAll) || !(components & ntc::kDgSeq)) return NTC_ERR_INVALID_ARG;
+    uint8_t h[32] = {'N', 'T', 'C', 'D', 1, 0, 0, 0, (uint8_t)components};
+    std::memcpy(h + 12, &k, 4);  // little-endian hosts only, as the block container
+    std::memcpy(h + 16, &n_nodes, 8);
+    return nx_write_all(fd, h, sizeof(h)) ? NTC_OK : NTC_ERR_IO;
+}
+
+int ntc_d_write_section(int fd, const ntc_digest_meta *meta) {
+    if (fd < 0 || !meta || !d_meta_ok(*meta)) return NTC_ERR_INVALID_ARG;
+    return nx_write_all(fd, (const uint8_t *)meta, sizeof(*meta)) ? NTC_OK : NTC_ERR_IO;
+}
+
+int ntc_d_read(const char *path, uint32_t *components, uint32_t *k, uint64_t *n_nodes, ntc_digest_meta **metas,
+               uint64_t *n_blocks) {
+    if (!path || !components || !k || !n_nodes || !metas || !n_blocks) return NTC_ERR_INVALID_ARG;
+    *components = *k = 0;
+    *n_nodes = 0;
+    *metas = nullptr;
+    *n_blocks = 0;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return NTC_ERR_IO;
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+    const bool io_bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (io_bad) return NTC_ERR_IO;
+    static const uint8_t magic[8] = {'N', 'T', 'C', 'D', 1, 0, 0, 0};
+    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
+    const uint32_t comp = buf[8];
+    if ((comp & ~ntc::kDgAll) || !(comp & ntc::kDgSeq)) return NTC_ERR_FORMAT;
+    for (size_t i = 9; i < 12; i++)
+        if (buf[i]) return NTC_ERR_FORMAT;
+    for (size_t i = 24; i < 32; i++)
+        if (buf[i]) return NTC_ERR_FORMAT;
+    if ((buf.size() - 32) % sizeof(ntc_digest_meta)) return NTC_ERR_FORMAT;
+    const uint64_t n = (buf.size() - 32) / sizeof(ntc_digest_meta);
+    std::vector<ntc_digest_meta> all(n);
+    if (n) std::memcpy(all.data(), buf.data() + 32, n * sizeof(ntc_digest_meta));
+    for (const ntc_digest_meta &m : all)
+        if (!d_meta_ok(m) || (m.components & ~comp)) return NTC_ERR_FORMAT;
+    if (n) {
+        *metas = (ntc_digest_meta *)std::malloc(n * sizeof(ntc_digest_meta));
+        if (!*metas) return NTC_ERR_CAPACITY;
+        std::memcpy(*metas, all.data(), n * sizeof(ntc_digest_meta));
+    }
+    std::memcpy(k, buf.data() + 12, 4);
+    std::memcpy(n_nodes, buf.data() + 16, 8);
+    *components = comp;
+    *n_blocks = n;
     return NTC_OK;
 }
 

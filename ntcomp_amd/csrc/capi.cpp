@@ -23,6 +23,7 @@
 #include "qrans_core.h"
 #include "quality_core.h"
 #include "names_core.h"
+#include "digest_core.h"
 #include "ntc_internal.h"
 
 using namespace ntc;
@@ -49,7 +50,8 @@ enum WsSlot {
     WS_NX_BITS, WS_NX_RUNS, WS_NX_PATCH,
     WS_Q_QUALS, WS_Q_BLOCKS, WS_Q_PAYLOAD, WS_QD_IN, WS_QD_QUALS,
     WS_QR_COUNTS, WS_QR_CUM, WS_QR_SCRATCH, WS_QR_SCAN,
-    WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES, WS_COUNT
+    WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES,
+    WS_DG_TABLE, WS_DGD_IN, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -161,6 +163,17 @@ struct ntc_ctx {
     std::vector<uint64_t> nd_payload;
     uint64_t nd_name_bytes = 0;
     bool nd_has_pending = false;
+    // content digests (digest.hip): the option (0 off, 1 on), the table the last
+    // ntc_encode_pack_* call left in WS_DG_TABLE, the expected digests waiting for the next
+    // FASTA decode call, and what the last such call computed (WS_DGD_IN holds both on the device)
+    int dg_opt = 0;
+    uint64_t dg_blocks = 0;
+    const uint32_t *n_d_start = nullptr, *n_d_len = nullptr;  // the name spans of the names pass in flight
+    std::vector<ntc_digest_meta> dd_metas;
+    bool dd_has_pending = false;
+    std::vector<ntc_digest_meta> dd_expected, dd_computed;
+    int discard_text = 0;  // option "discard_text": a FASTA decode call formats its text and leaves it on the device
+    uint32_t dd_checkable = 0;  // the components that call could compute
     FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
@@ -225,6 +238,7 @@ const char *status_name(int code) {
     case NTC_ERR_CAPACITY: return "output capacity exceeded";
     case NTC_ERR_FORMAT: return "malformed input";
     case NTC_ERR_REFERENCE_PANIC: return "short record longer than k (the reference panics, encode.rs:151-152)";
+    case NTC_ERR_DIGEST: return "content digest of the block differs; its first read";
     default: return "error";
     }
 }
@@ -863,6 +877,8 @@ int n_pack(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads) {
     a.box = ctx->h_box;
     ctx->h_box[8] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
     ctx->h_box[9] = 0;
+    ctx->n_d_start = a.start;
+    ctx->n_d_len = a.len;
     launch_names_pack(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     return NTC_OK;
@@ -948,6 +964,164 @@ int n_expand(ntc_ctx *ctx, const std::vector<ntc_name_meta> &metas, const std::v
     *d_names = (uint8_t *)names;
     *d_name_off = a.name_off;
     return NTC_OK;
+}
+
+// ---- content digests (digest.hip) ---------------------------------------------------------
+// Encode side, option "digests" 1: a table entry per block (WS_DG_TABLE, the public
+// ntc_digest_meta), each component added to it by one pass over bytes the call has in HBM
+// anyway.  Asynchronous, on the call's stream; option 0 launches nothing.
+static_assert(sizeof(DigestMetaDev) == sizeof(ntc_digest_meta) && sizeof(ntc_digest_meta) == 56,
+              "the device table is the public meta");
+void dg_begin(ntc_ctx *ctx) {  // an encode call starts: the last call's digests are gone
+    ctx->dg_blocks = 0;
+}
+// the components a call under the context's options yields (0: digests are off)
+uint32_t dg_components(const ntc_ctx *ctx, bool fastq) {
+    if (!ctx->dg_opt) return 0;
+    return kDgSeq | (ctx->nx_policy == 2 ? kDgSym : 0) | (fastq && ctx->q_mode ? kDgQual : 0) |
+           (fastq && ctx->n_mode ? kDgName : 0);
+}
+// the table of the call: reads and bases per block, the digests zeroed but those in keep
+int dg_init(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint32_t block_reads, uint32_t components,
+            uint32_t keep) {
+    const uint64_t nb = (n_reads + block_reads - 1) / block_reads;
+    void *t;
+    int rc;
+    if ((rc = ensure(ctx, WS_DG_TABLE, nb * sizeof(DigestMetaDev), &t))) return rc;
+    launch_digest_init((DigestMetaDev *)t, nb, n_reads, block_reads, d_offs, components, keep, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+// component c (0 seq .. 3 name) of the call's blocks: strings by offs, or by start / len
+int dg_add(ntc_ctx *ctx, uint32_t c, const void *buf, uint64_t buf_bytes, const uint64_t *offs, const uint32_t *start,
+           const uint32_t *len, uint64_t n_reads, uint32_t block_reads) {
+    DigestArgs a{};
+    a.buf = (const uint8_t *)buf;
+    a.buf_bytes = buf_bytes;
+    a.offs = offs;
+    a.start = start;
+    a.len = len;
+    a.n_reads = n_reads;
+    a.block_reads = block_reads;
+    a.out = ((DigestMetaDev *)ctx->ws[WS_DG_TABLE].p)->d + c;
+    a.out_stride = sizeof(DigestMetaDev) / 8;
+    launch_digest(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+
+// Decode side: the expected digests leave the context with the call that takes them
+bool dg_take_pending(ntc_ctx *ctx, std::vector<ntc_digest_meta> &metas) {
+    metas.clear();
+    if (!ctx->dd_has_pending) return false;
+    metas.swap(ctx->dd_metas);
+    ctx->dd_has_pending = false;
+    return true;
+}
+// The decode call in flight: expected and computed tables and the blocks' first reads on the
+// device (WS_DGD_IN); the runs of sections of one size, each of which is one launch_digest
+struct DgDecode {
+    DigestMetaDev *expected = nullptr, *computed = nullptr;
+    uint64_t *r0 = nullptr;
+    std::vector<uint64_t> first;               // first read of each block, and the total
+    std::vector<std::pair<uint64_t, uint64_t>> groups;  // [first block, one past the last)
+    uint32_t checkable = kDgSeq;
+};
+int dgd_begin(ntc_ctx *ctx, const std::vector<ntc_digest_meta> &exp, DgDecode &d) {
+    const uint64_t nb = exp.size();
+    d.first.assign(nb + 1, 0);
+    for (uint64_t b = 0; b < nb; b++) d.first[b + 1] = d.first[b] + exp[b].n_reads;
+    for (uint64_t b = 0; b < nb;) {  // sections of exp[b].n_reads reads, closed by the first shorter one
+        uint64_t e = b + 1;
+        while (e < nb && exp[e - 1].n_reads == exp[b].n_reads && exp[e].n_reads <= exp[b].n_reads) e++;
+        d.groups.emplace_back(b, e);
+        b = e;
+    }
+    ctx->dd_expected = exp;
+    ctx->dd_checkable = 0;
+    ctx->dd_computed.assign(nb, ntc_digest_meta{});
+    for (uint64_t b = 0; b < nb; b++) ctx->dd_computed[b].n_reads = exp[b].n_reads;
+    void *in;
+    int rc;
+    const uint64_t tb = nb * sizeof(DigestMetaDev);
+    if ((rc = ensure(ctx, WS_DGD_IN, 2 * tb + (nb + 1) * 8, &in))) return rc;
+    d.expected = (DigestMetaDev *)in;
+    d.computed = d.expected + nb;
+    d.r0 = (uint64_t *)(d.computed + nb);
+    HIP_TRY(ctx, hipMemcpy(d.expected, exp.data(), tb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d.computed, ctx->dd_computed.data(), tb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d.r0, d.first.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
+    return NTC_OK;
+}
+// component c of the decoded strings: buf by offs (n_reads + 1 words, positions relative to offs[0])
+int dgd_add(ntc_ctx *ctx, DgDecode &d, uint32_t c, const void *buf, uint64_t buf_bytes, const uint64_t *offs) {
+    d.checkable |= 1u << c;
+    for (const auto &g : d.groups) {
+        DigestArgs a{};
+        a.buf = (const uint8_t *)buf;
+        a.buf_bytes = buf_bytes;
+        a.offs = offs + d.first[g.first];
+        a.origin = offs;
+        a.n_reads = d.first[g.second] - d.first[g.first];
+        a.block_reads = (uint32_t)ctx->dd_expected[g.first].n_reads;
+        a.out = d.computed[g.first].d + c;
+        a.out_stride = sizeof(DigestMetaDev) / 8;
+        a.status = ctx->d_status;
+        launch_digest(a, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+// the comparison on the device, the mailbox again (it may have set the status), and the
+// computed table on its way to the host: it arrives with the call's own synchronisation
+int dgd_compare(ntc_ctx *ctx, DgDecode &d, uint64_t n_reads, const uint64_t *d_offs) {
+    DigestCmpArgs a{};
+    a.expected = d.expected;
+    a.computed = d.computed;
+    a.r0 = d.r0;
+    a.n_blocks = ctx->dd_expected.size();
+    a.n_reads = n_reads;
+    a.offs = d_offs;
+    a.checkable = d.checkable;
+    a.status = ctx->d_status;
+    launch_digest_compare(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ctx->box_valid && ctx->last == kDecode)
+        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
+                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dd_computed.data(), d.computed, a.n_blocks * sizeof(DigestMetaDev),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    ctx->dd_checkable = d.checkable;
+    return NTC_OK;
+}
+// After the call's synchronisation: which components were checked, and for NTC_ERR_DIGEST the
+// message: the lowest block that differs, the component, both values
+int dgd_verdict(ntc_ctx *ctx, int rc) {
+    static const char *const names[4] = {"seq", "sym", "qual", "name"};
+    std::string msg;
+    for (size_t b = 0; b < ctx->dd_expected.size(); b++) {
+        ntc_digest_meta &e = ctx->dd_expected[b], &g = ctx->dd_computed[b];
+        const uint32_t check = e.components & ctx->dd_checkable;
+        g.components = check;
+        g.reserved = 0;
+        const uint64_t ed[4] = {e.d_seq, e.d_sym, e.d_qual, e.d_name}, gd[4] = {g.d_seq, g.d_sym, g.d_qual, g.d_name};
+        if (rc != NTC_ERR_DIGEST || !msg.empty()) continue;
+        char buf[200];
+        if (g.n_bases != e.n_bases) {
+            std::snprintf(buf, sizeof(buf), "digest mismatch in block %llu, component seq: %llu bases expected, %llu decoded",
+                          (unsigned long long)b, (unsigned long long)e.n_bases, (unsigned long long)g.n_bases);
+            msg = buf;
+        }
+        for (uint32_t c = 0; c < 4 && msg.empty(); c++)
+            if ((check >> c & 1) && ed[c] != gd[c]) {
+                std::snprintf(buf, sizeof(buf), "digest mismatch in block %llu, component %s: expected 0x%016llx, computed 0x%016llx",
+                              (unsigned long long)b, names[c], (unsigned long long)ed[c], (unsigned long long)gd[c]);
+                msg = buf;
+            }
+    }
+    if (rc == NTC_ERR_DIGEST && !msg.empty()) ctx->err = msg;
+    return rc;
 }
 
 // GPU packer (pack.hip) over the records of n_reads reads in HBM: block b = reads
@@ -1657,6 +1831,16 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
         ctx->n_mode = (int)value;
         return NTC_OK;
     }
+    if (std::strcmp(key, "discard_text") == 0) {  // ntc_decode_fasta*: no copy of the text to the host (ntcomp_codec.h)
+        if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "discard_text must be 0 or 1");
+        ctx->discard_text = (int)value;
+        return NTC_OK;
+    }
+    if (std::strcmp(key, "digests") == 0) {  // per-block content digests: 0 off, 1 on (ntcomp_codec.h)
+        if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "digests must be 0 or 1");
+        ctx->dg_opt = (int)value;
+        return NTC_OK;
+    }
     if (std::strcmp(key, "non_acgt") == 0) {  // N and IUPAC symbols: 0 error, 1 mask, 2 keep (ntcomp_gpu.h)
         if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)");
         ctx->nx_policy = (int)value;
@@ -1735,6 +1919,8 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "qualities") == 0) *value = ctx->q_mode;
     else if (std::strcmp(key, "quality_coder") == 0) *value = ctx->q_coder;
     else if (std::strcmp(key, "names") == 0) *value = ctx->n_mode;
+    else if (std::strcmp(key, "digests") == 0) *value = ctx->dg_opt;
+    else if (std::strcmp(key, "discard_text") == 0) *value = ctx->discard_text;
     else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
     else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
     else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
@@ -2090,10 +2276,13 @@ int ntc_pack_blocks_device(ntc_ctx *ctx, const uint64_t *d_recs, const uint64_t 
 namespace {
 // encode + GPU block packer over reads already in HBM (d_offs: n_reads + 1 offsets, room for
 // n_reads + 1 more behind them, where the record offsets go); the tail of
-// ntc_encode_pack_batch and ntc_encode_pack_fastq
+// ntc_encode_pack_batch and ntc_encode_pack_fastq.  dg: the digest components of the call (0:
+// none); sym and seq are taken here, around the non-ACGT pass, and again (zeroed first) when
+// the batch is staged afresh.  A re-run with grown pools encodes the same staged bases and
+// leaves the digests alone.
 int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offs, uint64_t n_reads, uint64_t total,
                        uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
-                       int64_t *bad_read, const std::function<int()> &restage) {
+                       int64_t *bad_read, const std::function<int()> &restage, uint32_t dg) {
     void *d_recs, *d_payload;
     int rc;
     if ((rc = ensure(ctx, WS_STAGE_RECS, (total + 1) * 8, &d_recs))) return rc;
@@ -2101,7 +2290,11 @@ int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_o
     // non-ACGT symbols are masked in the staged copy first (policy 0: nothing runs); a batch
     // with more runs than the list had room for is staged and run once more
     for (bool again = true; again;) {
+        // (qual and name were taken from the text before this point, where the call has them)
+        if (dg && (rc = dg_init(ctx, d_offs, n_reads, block_reads, dg, dg & (kDgQual | kDgName)))) return rc;
+        if ((dg & kDgSym) && (rc = dg_add(ctx, 1, d_bases, total, d_offs, nullptr, nullptr, n_reads, block_reads))) return rc;
         if ((rc = nx_mask(ctx, const_cast<uint8_t *>(d_bases), d_offs, n_reads, total))) return rc;
+        if (dg && (rc = dg_add(ctx, 0, d_bases, total, d_offs, nullptr, nullptr, n_reads, block_reads))) return rc;
         rc = encode4_impl(ctx, d_bases, d_offs, n_reads, total, (uint64_t *)d_recs, total + 1, d_roffs);
         if (rc) return rc;
         int64_t bad = -1;
@@ -2136,6 +2329,7 @@ int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_o
     }
     *payload = h;
     *payload_bytes = used;
+    if (dg) ctx->dg_blocks = n_blocks;
     return NTC_OK;
 }
 }  // namespace
@@ -2155,6 +2349,7 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
     if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_pack_batch");
     if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_pack_batch");
+    dg_begin(ctx);
     for (uint64_t r = 0; r < n_reads; r++)
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
@@ -2174,7 +2369,7 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
         return NTC_OK;
     };
     return encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads,
-                              meta, payload, payload_bytes, bad_read, restage);
+                              meta, payload, payload_bytes, bad_read, restage, dg_components(ctx, false));
 }
 
 }  // extern "C"
@@ -2275,11 +2470,21 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     nx_begin(ctx);
     q_begin(ctx);
     n_begin(ctx);
+    dg_begin(ctx);
     if (n_reads == 0) return NTC_OK;
+    // the digest table of the call (option "digests" 0: nothing runs here or below)
+    const uint32_t dg = dg_components(ctx, true);
+    if (dg && (rc = dg_init(ctx, (const uint64_t *)d_offs, n_reads, block_reads, dg, 0))) return rc;
     // the quality lines are packed from the text while the reads are encoded (mode 0: nothing runs)
     if ((rc = q_pack(ctx, (const uint64_t *)d_offs, n_reads, total, block_reads))) return rc;
+    if ((dg & kDgQual) && (rc = dg_add(ctx, 2, ctx->ws[WS_Q_QUALS].p, total, (const uint64_t *)d_offs, nullptr, nullptr,
+                                      n_reads, block_reads)))
+        return rc;
     // and the names are front-coded from it (mode 0: nothing runs)
     if ((rc = n_pack(ctx, n_reads, block_reads))) return rc;
+    if ((dg & kDgName) && (rc = dg_add(ctx, 3, ctx->fq_last.raw, ctx->fq_last.n_raw, nullptr, ctx->n_d_start, ctx->n_d_len,
+                                      n_reads, block_reads)))
+        return rc;
     const auto restage = [&]() -> int {  // the text is still in HBM: parse it again (it parsed clean once)
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
         ctx->fq_last.tmp = (uint64_t *)ctx->ws[WS_SCANTMP].p;  // the scan scratch may have grown (never shrinks) since
@@ -2288,7 +2493,7 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
         return NTC_OK;
     };
     rc = encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads, meta,
-                            payload, payload_bytes, bad_read, restage);
+                            payload, payload_bytes, bad_read, restage, dg);
     if (ctx->q_mode == 0 && ctx->n_mode == 0) return rc;
     // a read the quality or the names pass refused fails the call, whatever the encode said of it
     if (rc) (void)hipStreamSynchronize(ctx->stream);  // (an encode that failed early may not have synchronised)
@@ -2299,6 +2504,7 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     if (rc || src) {  // a failed call leaves no sections
         q_begin(ctx);
         n_begin(ctx);
+        dg_begin(ctx);
     }
     if (src && bad_read) *bad_read = qrc ? q_bad : n_bad;
     if (src && !rc) {
@@ -2348,8 +2554,10 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     std::vector<uint64_t> qp;
     std::vector<ntc_name_meta> nm;
     std::vector<uint64_t> np;
+    std::vector<ntc_digest_meta> dm;
     const bool fastq = q_take_pending(ctx, qm, qp);  // (all pending lists leave the context here)
     const bool named = n_take_pending(ctx, nm, np);
+    const bool digests = dg_take_pending(ctx, dm);
     if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= n_reads)
         return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
     if (fastq) {
@@ -2368,12 +2576,26 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
         }
         if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "name sections for fewer reads than decoded");
     }
+    DgDecode dg;
+    if (digests) {
+        uint64_t r = 0;
+        for (const ntc_digest_meta &m : dm) {
+            if (m.n_reads > n_reads - r) return set_err(ctx, NTC_ERR_FORMAT, "digest sections for more reads than decoded");
+            r += m.n_reads;
+        }
+        if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "digest sections for fewer reads than decoded");
+        if ((rc = dgd_begin(ctx, dm, dg))) return rc;
+    }
     if ((rc = ntc_decode_batch_device(ctx, d_recs, n_recs, (uint8_t *)d_bases, n_bases + 64, (uint64_t *)d_offs,
                                       n_reads + 2)))
         return rc;
+    // the walked bases are digested as they stand (seq), before the exception runs go in
+    if (digests && (rc = dgd_add(ctx, dg, 0, d_bases, n_bases, (const uint64_t *)d_offs))) return rc;
     // exception runs go over the substitute bases before the text is formatted
     if (!nx.empty() && (rc = nx_patch(ctx, nx, nx_sub, 0, n_reads, (uint8_t *)d_bases, (const uint64_t *)d_offs)))
         return rc;
+    // (sym: only then is there anything to tell from seq)
+    if (digests && !nx.empty() && (rc = dgd_add(ctx, dg, 1, d_bases, n_bases, (const uint64_t *)d_offs))) return rc;
     // and the qualities are unpacked by the decoded reads' offsets, after the patch
     uint8_t *d_quals = nullptr;
     if (fastq && (rc = q_unpack(ctx, qm, qp, n_reads, n_bases, (const uint64_t *)d_offs, &d_quals))) return rc;
@@ -2381,6 +2603,15 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     uint8_t *d_names = nullptr;
     uint64_t *d_name_off = nullptr;
     if (named && (rc = n_expand(ctx, nm, np, n_reads, &d_names, &d_name_off))) return rc;
+    // the other two components over what was just expanded, then the verdict on the device:
+    // a block that differs sets the status, and the formatters below write nothing
+    if (digests) {
+        uint64_t name_bytes = 0;
+        for (const ntc_name_meta &m : nm) name_bytes += m.name_bytes;
+        if (fastq && (rc = dgd_add(ctx, dg, 2, d_quals, n_bases, (const uint64_t *)d_offs))) return rc;
+        if (named && (rc = dgd_add(ctx, dg, 3, d_names, name_bytes, d_name_off))) return rc;
+        if ((rc = dgd_compare(ctx, dg, n_reads, (const uint64_t *)d_offs))) return rc;
+    }
     uint64_t *sizes = (uint64_t *)d_scan, *out_offs = sizes + (n_reads + 1), *tmp = out_offs + (n_reads + 1);
     if (named)
         launch_named_text((const uint8_t *)d_bases, d_quals, (const uint64_t *)d_offs, d_names, d_name_off, n_reads,
@@ -2392,9 +2623,11 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
         launch_fasta((const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status, sizes,
                      out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, ctx->stream));
+    if (!ctx->discard_text) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, ctx->stream));
     uint64_t nr = 0, nb = 0;
-    if ((rc = ntc_decode_status(ctx, &nr, &nb))) return rc;  // synchronises
+    rc = ntc_decode_status(ctx, &nr, &nb);  // synchronises
+    if (digests) rc = dgd_verdict(ctx, rc);
+    if (rc) return rc;
     if (nr != n_reads || nb != n_bases)
         return set_err(ctx, NTC_ERR_FORMAT, "records hold other read / base counts than given");
     return NTC_OK;
@@ -2430,13 +2663,15 @@ extern "C" {
 
 int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64_t n_reads, uint64_t n_bases,
                      uint64_t first_id, uint8_t *out, uint64_t out_capacity, uint64_t *out_len) {
-    if (!ctx || !out_len || (n_recs && !recs) || (n_reads && !out)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    if (!ctx || !out_len || (n_recs && !recs) || (n_reads && !out && !ctx->discard_text))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     const uint64_t need = text_bytes(ctx, n_reads, n_bases, first_id);
     *out_len = need;
-    if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+    if (need > out_capacity && !ctx->discard_text)
+        return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
     if (n_recs == 0) return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     void *d_recs;
     int rc;
@@ -2574,8 +2809,10 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     const uint64_t need = text_bytes(ctx, ctx->unp_reads, ctx->unp_bases, first_id);
     *out_len = need;  // (a size query: out_capacity 0)
-    if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
-    if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    if (!ctx->discard_text) {
+        if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+        if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    }
     if (ctx->unp_recs == 0) return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     return decode_fasta_dev(ctx, ctx->unp_d_recs, ctx->unp_recs, ctx->unp_reads, ctx->unp_bases, first_id, out, need);
 }
@@ -2706,6 +2943,43 @@ int ntc_decode_set_names(ntc_ctx *ctx, const ntc_name_meta *metas, uint64_t n_bl
     if (payload_bytes) std::memcpy(ctx->nd_payload.data(), payload, payload_bytes);
     ctx->nd_name_bytes = name_bytes;
     ctx->nd_has_pending = true;
+    return NTC_OK;
+}
+
+int ntc_encode_digests(ntc_ctx *ctx, ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks) {
+    if (!ctx || !n_blocks || (cap && !metas)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_blocks = ctx->dg_blocks;
+    if (ctx->dg_blocks > cap) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the digest table");
+    if (ctx->dg_blocks == 0) return NTC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(metas, ctx->ws[WS_DG_TABLE].p, ctx->dg_blocks * sizeof(ntc_digest_meta), hipMemcpyDeviceToHost));
+    return NTC_OK;
+}
+
+int ntc_decode_set_digests(ntc_ctx *ctx, const ntc_digest_meta *metas, uint64_t n_blocks) {
+    if (!ctx || (n_blocks && !metas)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    ctx->dd_metas.clear();
+    ctx->dd_has_pending = false;
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        const ntc_digest_meta &m = metas[b];
+        const uint64_t d[4] = {m.d_seq, m.d_sym, m.d_qual, m.d_name};
+        bool ok = !(m.components & ~kDgAll) && (m.components & kDgSeq) && !m.reserved && m.n_reads && !(m.n_reads >> 32);
+        for (uint32_t c = 0; c < 4; c++) ok = ok && ((m.components >> c & 1) || !d[c]);
+        if (!ok)
+            return set_err(ctx, NTC_ERR_INVALID_ARG, "digest section " + std::to_string(b) + ": components, reads or a digest "
+                                                     "of an absent component");
+    }
+    ctx->dd_metas.assign(metas, metas + n_blocks);
+    ctx->dd_has_pending = n_blocks != 0;
+    return NTC_OK;
+}
+
+int ntc_decode_digests(ntc_ctx *ctx, ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks) {
+    if (!ctx || !n_blocks || (cap && !metas)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_blocks = ctx->dd_computed.size();
+    if (ctx->dd_computed.size() > cap) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the digest table");
+    if (!ctx->dd_computed.empty())
+        std::memcpy(metas, ctx->dd_computed.data(), ctx->dd_computed.size() * sizeof(ntc_digest_meta));
     return NTC_OK;
 }
 
@@ -2980,6 +3254,14 @@ struct NxHookFill {
         ntc::g_n_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "names", mode); };
         ntc::g_n_hooks.encode_names = ntc_encode_names;
         ntc::g_n_hooks.decode_set_names = ntc_decode_set_names;
+        ntc::g_d_hooks.set_mode = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "digests", on); };
+        ntc::g_d_hooks.encode_digests = ntc_encode_digests;
+        ntc::g_d_hooks.decode_set_digests = ntc_decode_set_digests;
+        ntc::g_d_hooks.decode_digests = ntc_decode_digests;
+        ntc::g_d_hooks.index_info = [](ntc_ctx *ctx, uint64_t *n_nodes, uint32_t *k) {
+            return ntc_index_info(ctx, n_nodes, k, nullptr);
+        };
+        ntc::g_d_hooks.set_discard = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "discard_text", on); };
     }
 } g_nx_hook_fill;
 }  // namespace

@@ -406,6 +406,52 @@ void launch_named_text(const uint8_t *d_bases, const uint8_t *d_quals, const uin
                        const uint64_t *d_name_off, uint64_t n, const unsigned long long *d_status, uint64_t *sizes,
                        uint64_t *out_offs, uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s);
 
+// Per-block content digests (digest.hip, digest_core.h).  A table entry is the public
+// ntc_digest_meta: d[c] is the digest of component c (seq, sym, qual, name).
+struct DigestMetaDev {
+    uint64_t n_reads, n_bases, d[4];
+    uint32_t components, pad;
+};
+// encode: entry b = reads [b block_reads, ...) of offs (n_reads + 1 words), the digests zeroed
+// except those whose bit is set in keep
+void launch_digest_init(DigestMetaDev *table, uint64_t n_blocks, uint64_t n_reads, uint32_t block_reads,
+                        const uint64_t *offs, uint32_t components, uint32_t keep, hipStream_t s);
+// One component over n_reads strings of buf: string r is bytes [offs[r] - o, offs[r + 1] - o)
+// (offs: n_reads + 1 words; o = *origin, 0 when origin is null: the decoded offsets of a run
+// of blocks are relative to the call's first), or with offs null bytes [start[r], start[r] +
+// len[r]);
+// every position is clamped to buf_bytes, and buf has 8 readable bytes past them.  Block b =
+// strings [b block_reads, ...); its digest is ADDED to out[b out_stride] (zeroed by the
+// caller).  status (null: none): the pass does nothing unless *status is clear (~0).  Strings
+// past kDgLong bytes are taken by a whole workgroup, the others by a quarter-wave.
+constexpr uint64_t kDgLong = 2048;
+struct DigestArgs {
+    const uint8_t *buf;
+    uint64_t buf_bytes;
+    const uint64_t *offs, *origin;
+    const uint32_t *start, *len;
+    uint64_t n_reads;
+    uint32_t block_reads, bias;  // bias: set by the launcher
+    uint64_t *out;
+    uint64_t out_stride;         // in 64-bit words
+    const unsigned long long *status;
+};
+void launch_digest(const DigestArgs &a, hipStream_t s);
+// decode: block b covers reads [r0[b], r0[b + 1]) (r0: n_blocks + 1 words) of the decoded
+// offsets offs; computed[b].n_bases is written, and a block whose bases, or whose digest of a
+// component in expected[b].components & checkable, differ sets status to r0[b] << 8 |
+// NTC_ERR_DIGEST (lowest block first; a status already set stays).
+struct DigestCmpArgs {
+    const DigestMetaDev *expected;
+    DigestMetaDev *computed;
+    const uint64_t *r0;
+    uint64_t n_blocks, n_reads;
+    const uint64_t *offs;
+    uint32_t checkable;
+    unsigned long long *status;
+};
+void launch_digest_compare(const DigestCmpArgs &a, hipStream_t s);
+
 void launch_encode(const EncodeArgs &a, hipStream_t s);
 void launch_encode4(const Enc4Args &a, uint64_t total, uint32_t ms_blocks, hipStream_t s,
                     hipEvent_t ev_ms_begin, hipEvent_t ev_ms_end);

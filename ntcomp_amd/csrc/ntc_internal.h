@@ -94,6 +94,7 @@ struct ntc_ctx;
 struct ntc_nx_run;
 struct ntc_qual_meta;
 struct ntc_name_meta;
+struct ntc_digest_meta;
 namespace ntc {
 // a plain FASTQ that ntc_fastx_open mapped: its bytes (null for any other input), and
 // moving the mapped parser to byte pos (a record start) -- pipeline.cpp's GPU-parse reader
@@ -151,6 +152,17 @@ struct NHooks {
                             uint64_t payload_bytes);
 };
 extern NHooks g_n_hooks;
+// ... and for content digests: with the table null, ntc_encode_file_ex3 / ntc_decode_file_ex3
+// answer NTC_ERR_UNSUPPORTED to d_mode 1, to a digest file and to out_fd -1.
+struct DHooks {
+    int (*set_mode)(::ntc_ctx *ctx, int on);  // ctx option "digests"
+    int (*encode_digests)(::ntc_ctx *ctx, ::ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks);
+    int (*decode_set_digests)(::ntc_ctx *ctx, const ::ntc_digest_meta *metas, uint64_t n_blocks);
+    int (*decode_digests)(::ntc_ctx *ctx, ::ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks);
+    int (*index_info)(::ntc_ctx *ctx, uint64_t *n_nodes, uint32_t *k);  // ntc_index_info
+    int (*set_discard)(::ntc_ctx *ctx, int on);  // ctx option "discard_text"
+};
+extern DHooks g_d_hooks;
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

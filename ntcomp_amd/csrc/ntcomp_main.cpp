@@ -10,10 +10,14 @@
 //                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
 //                 [--non-acgt error|mask|keep] [--exceptions PATH]
 //                 [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]
-//                 [--names drop|keep|id] [--name-file PATH] FILE > encoded.dat
+//                 [--names drop|keep|id] [--name-file PATH] [--digest-file PATH] FILE > encoded.dat
 //   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
-//                 [--exceptions PATH] [--quality-file PATH] [--name-file PATH] FILE > out.fasta
-//                 (FASTQ with --quality-file, the reads' own names with --name-file)
+//                 [--exceptions PATH] [--quality-file PATH] [--name-file PATH] [--digest-file PATH]
+//                 FILE > out.fasta
+//                 (FASTQ with --quality-file, the reads' own names with --name-file; checked block by
+//                 block against the --digest-file)
+//   ntcomp verify -i P --digest-file PATH [--exceptions PATH] [--quality-file PATH] [--name-file PATH]
+//                 FILE        (decode without the text: one line on stdout, status 0 iff every block matched)
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -73,7 +77,8 @@ bool takes_value(const std::string &o) {
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
                               "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
-                              "--qualities", "--quality-file", "--quality-coder", "--names", "--name-file"};
+                              "--qualities", "--quality-file", "--quality-coder", "--names", "--name-file",
+                              "--digest-file"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -224,11 +229,28 @@ bool libdeflate_present() {
     return h != nullptr;
 }
 
+// --digest-file PATH as both commands take it: not empty, and no file the same call reads or writes
+std::string digest_path_of(const Args &a, const char *cmd, const std::vector<std::string> &others) {
+    if (!a.flag("--digest-file")) return "";
+    const std::string d = a.get("--digest-file", nullptr, "");
+    if (d.empty()) bad_args(std::string(cmd) + ": --digest-file needs a path");
+    for (const std::string &o : others)
+        if (!o.empty() && o == d) bad_args(std::string(cmd) + ": --digest-file names a file this call uses already: " + d);
+    return d;
+}
+// "seq,sym" for a mask of NTC_DIGEST_* bits ("-" for none)
+std::string component_names(uint32_t mask) {
+    static const char *const names[4] = {"seq", "sym", "qual", "name"};
+    std::string s;
+    for (int c = 0; c < 4; c++)
+        if (mask >> c & 1) s += (s.empty() ? "" : ",") + std::string(names[c]);
+    return s.empty() ? "-" : s;
+}
+
 int cmd_encode(const Args &a) {
     const auto t0 = Clock::now();
     if (a.pos.size() != 1) die("encode: one query file");
     const std::string prefix = a.get("-i", "--index", "");
-    if (prefix.empty()) die("encode: -i/--index is required");
     // N and IUPAC symbols: error (default), mask, or keep with the exception runs in a side file
     const std::string nx_name = a.get("--non-acgt", nullptr, "error"), nx_path = a.get("--exceptions", nullptr, "");
     const int policy = nx_name == "error" ? NTC_NX_ERROR : nx_name == "mask" ? NTC_NX_MASK : nx_name == "keep" ? NTC_NX_KEEP : -1;
@@ -254,6 +276,9 @@ int cmd_encode(const Args &a) {
     if (n_mode < 0) bad_args("encode: --names: drop, keep or id");
     if (n_mode > 0 && n_path.empty()) bad_args("encode: --names " + n_name + " requires --name-file PATH");
     if (n_mode == 0 && a.flag("--name-file")) bad_args("encode: --name-file is only written under --names keep or id");
+    // per-block content digests of everything this call encodes, for decode / verify --digest-file
+    const std::string d_path = digest_path_of(a, "encode", {nx_path, q_path, n_path, a.pos[0]});
+    if (prefix.empty()) die("encode: -i/--index is required");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
@@ -285,13 +310,20 @@ int cmd_encode(const Args &a) {
     int n_fd = -1;
     if (n_mode > 0 && (n_fd = ::open(n_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
         die("encode: cannot write " + n_path);
+    ntc_d_stats dst{};
+    int d_fd = -1;
+    if (!d_path.empty() && (d_fd = ::open(d_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
+        die("encode: cannot write " + d_path);
     if (q_mode > 0)  // the pipeline takes the coder from its contexts
         for (ntc_ctx *c : ctxs)
             if (ntc_ctx_set_option(c, "quality_coder", q_coder)) die("encode: --quality-coder: the option was refused");
     const ntc_file_opts fo{policy, nx_fd, q_mode, q_fd, nullptr, nullptr};
     const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd, nullptr};
+    const ntc_file_opts3 fo3{(uint32_t)sizeof(ntc_file_opts3), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd,
+                             nullptr, 1, d_fd, nullptr};
     std::fflush(stdout);
-    const int rc = n_mode > 0 ? ntc_encode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st, &nx, &qs, &ns)
+    const int rc = d_fd >= 0 ? ntc_encode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo3, &o, &st, &nx, &qs, &ns, &dst)
+                   : n_mode > 0 ? ntc_encode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st, &nx, &qs, &ns)
                    : q_mode > 0 ? ntc_encode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st, &nx, &qs)
                    : policy == NTC_NX_ERROR
                        ? ntc_encode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
@@ -299,7 +331,8 @@ int cmd_encode(const Args &a) {
     if (nx_fd >= 0 && ::close(nx_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + nx_path);
     if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
     if (n_fd >= 0 && ::close(n_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + n_path);
-    char qjson[704] = "";  // the quality and name files' figures, when they were written
+    if (d_fd >= 0 && ::close(d_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + d_path);
+    char qjson[960] = "";  // the quality and name files' figures, when they were written
     if (q_mode > 0)
         std::snprintf(qjson, 320, "\"qualities\": \"%s\", \"quality_coder\": \"%s\", \"q_sections\": %llu, "
                                   "\"q_quals\": %llu, \"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
@@ -312,6 +345,11 @@ int cmd_encode(const Args &a) {
                       n_name.c_str(), (unsigned long long)ns.sections, (unsigned long long)ns.names,
                       (unsigned long long)ns.name_bytes, (unsigned long long)ns.payload_bytes,
                       (unsigned long long)ns.deflated_bytes);
+    if (d_fd >= 0)
+        std::snprintf(qjson + std::strlen(qjson), 250, "\"d_sections\": %llu, \"d_blocks_seq\": %llu, \"d_blocks_sym\": %llu, "
+                                                       "\"d_blocks_qual\": %llu, \"d_blocks_name\": %llu, ",
+                      (unsigned long long)dst.sections, (unsigned long long)dst.blocks_seq, (unsigned long long)dst.blocks_sym,
+                      (unsigned long long)dst.blocks_qual, (unsigned long long)dst.blocks_name);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -345,17 +383,22 @@ bool host_unpack_on() {
     return h && std::atoi(h) > 0;
 }
 
-int cmd_decode(const Args &a) {
+// verify: decode with out_fd -1 -- nothing is copied off the device or written; one line on stdout
+int cmd_decode(const Args &a, bool verify = false) {
     const auto t0 = Clock::now();
-    if (a.pos.size() != 1) die("decode: one input file");
+    const char *cmd = verify ? "verify" : "decode";
+    if (a.pos.size() != 1) die(std::string(cmd) + ": one input file");
     const std::string prefix = a.get("-i", "--index", "");
-    if (prefix.empty()) die("decode: -i/--index is required");
+    const std::string d_path = digest_path_of(a, cmd, {a.get("--exceptions", nullptr, ""), a.get("--quality-file", nullptr, ""),
+                                                       a.get("--name-file", nullptr, ""), a.pos[0]});
+    if (verify && d_path.empty()) bad_args("verify: --digest-file PATH is required");
+    if (prefix.empty()) die(std::string(cmd) + ": -i/--index is required");
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
     const double t_load = since(t0);
     auto ctxs = open_gpus(ix, devices_of(a), per_gpu_of(a, kDecodeContextsPerGpu), true);
     const double t_gpu = since(t0);
-    info("Decoding encoded data...");
+    info(verify ? "Verifying encoded data..." : "Decoding encoded data...");
     ntc_pipeline_opts o{};
     o.threads = std::atoi(a.get("--threads", nullptr, "0").c_str());
     o.blocks_per_batch = std::atoi(a.get("--blocks-per-batch", nullptr, "2").c_str());
@@ -366,15 +409,36 @@ int cmd_decode(const Args &a) {
     const std::string n_path = a.get("--name-file", nullptr, "");  // ... of encode --names keep: the reads' names
     const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), 0, -1, 0, -1, fo.nx_path,
                              q_path.empty() ? nullptr : q_path.c_str(), 0, -1, n_path.c_str()};
+    const ntc_file_opts3 fo3{(uint32_t)sizeof(ntc_file_opts3), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1,
+                             n_path.empty() ? nullptr : n_path.c_str(), 0, -1, d_path.c_str()};
+    ntc_d_stats dst{};
     std::fflush(stdout);
-    const int rc = !n_path.empty() ? ntc_decode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st)
+    const int rc = !d_path.empty() ? ntc_decode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo3, &o, &st, &dst)
+                   : !n_path.empty() ? ntc_decode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st)
                    : !q_path.empty() ? ntc_decode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st)
                    : nx_path.empty()
                        ? ntc_decode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
                        : ntc_decode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), nx_path.c_str(), 1, &o, &st);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
-    if (rc) die(std::string("decode: ") + st.error);
+    if (rc) {
+        std::string m = std::string(cmd) + ": " + st.error;
+        if (rc == NTC_ERR_DIGEST && st.bad_read >= 0) m += " (read " + std::to_string(st.bad_read + 1) + ")";
+        die(m);
+    }
+    if (verify)
+        std::printf("verify: OK: %llu blocks, %llu reads, checked %s, not checkable %s\n", (unsigned long long)dst.sections,
+                    (unsigned long long)st.reads,
+                    component_names((dst.blocks_seq ? 1u : 0) | (dst.blocks_sym ? 2u : 0) | (dst.blocks_qual ? 4u : 0) |
+                                    (dst.blocks_name ? 8u : 0)).c_str(),
+                    component_names(dst.not_checkable).c_str());
+    char djson[320] = "";
+    if (!d_path.empty())
+        std::snprintf(djson, sizeof(djson), "\"d_sections\": %llu, \"d_blocks_seq\": %llu, \"d_blocks_sym\": %llu, "
+                                            "\"d_blocks_qual\": %llu, \"d_blocks_name\": %llu, \"d_not_checkable\": \"%s\", ",
+                      (unsigned long long)dst.sections, (unsigned long long)dst.blocks_seq, (unsigned long long)dst.blocks_sym,
+                      (unsigned long long)dst.blocks_qual, (unsigned long long)dst.blocks_name,
+                      component_names(dst.not_checkable).c_str());
     if (st.dropped_blocks)  // the reference's `while let Ok(..) = decode_block` just ends here (main.rs:202)
         std::fprintf(stderr, "warning: %s; %llu block(s) not decoded\n", st.error,
                      (unsigned long long)st.dropped_blocks);
@@ -382,12 +446,12 @@ int cmd_decode(const Args &a) {
         std::fprintf(stderr,
                      "{\"stats\": {\"index_load\": %.3f, \"gpu_init_upload\": %.3f, \"unzip\": %.3f, \"gpu\": %.3f, "
                      "\"write\": %.3f, \"alloc\": %.3f}, \"timeline\": {\"first_write\": %.3f, \"unzip_done\": %.3f, "
-                     "\"gpu_done\": %.3f}, \"command\": \"decode\", \"native\": true, \"gpus\": %zu, \"threads\": %d, "
+                     "\"gpu_done\": %.3f}, \"command\": \"%s\", \"native\": true, \"gpus\": %zu, \"threads\": %d, "
                      "\"reads\": %llu, \"blocks\": %llu, \"pipeline_wall_s\": %.3f, \"gpu_unpack\": %s, "
-                     "\"process_s\": %.3f}\n",
+                     "%s\"process_s\": %.3f}\n",
                      t_load, t_gpu - t_load, st.parse_s, st.gpu_s, st.write_s, st.alloc_s, st.first_batch_s,
-                     st.reader_done_s, st.gpu_done_s, ctxs.size(), st.threads, (unsigned long long)st.reads,
-                     (unsigned long long)st.blocks, st.wall_s, host_unpack_on() ? "false" : "true", since(t0));
+                     st.reader_done_s, st.gpu_done_s, cmd, ctxs.size(), st.threads, (unsigned long long)st.reads,
+                     (unsigned long long)st.blocks, st.wall_s, host_unpack_on() ? "false" : "true", djson, since(t0));
     return 0;
 }
 
@@ -489,9 +553,12 @@ void usage(FILE *f) {
                  "MI355X.\n\nusage: ntcomp build -o PREFIX [-k K] [-m MEM_GB] [--temp-dir DIR] FILES...\n"
                  "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH]\n"
                  "                     [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]\n"
-                 "                     [--names drop|keep|id] [--name-file PATH] FILE > encoded.dat\n"
-                 "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH] FILE\n"
-                 "                     > out.fasta\n\n"
+                 "                     [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]\n"
+                 "                     FILE > encoded.dat\n"
+                 "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH]\n"
+                 "                     [--digest-file PATH] FILE > out.fasta\n"
+                 "       ntcomp verify -i PREFIX --digest-file PATH [--exceptions PATH] [--quality-file PATH]\n"
+                 "                     [--name-file PATH] FILE\n\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
                  "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
                  "                     the replaced symbols to the --exceptions file (lossless)\n"
@@ -508,7 +575,11 @@ void usage(FILE *f) {
                  "                     after '@'), or id (the name up to its first space or tab, lossy); keep and id\n"
                  "                     write them, front-coded on the GPU, to the --name-file\n"
                  "  --name-file PATH   encode --names keep|id: the side file to write; decode: the side file whose\n"
-                 "                     names are printed instead of seq.N\n");
+                 "                     names are printed instead of seq.N\n"
+                 "  --digest-file PATH encode: also write per-block content digests, computed on the GPU; decode: check\n"
+                 "                     every block against them while decoding -- another index, a damaged or truncated\n"
+                 "                     file, a side file of another run end the call with an error that names the block\n"
+                 "                     and the component; verify: the same check without writing the text\n");
 }
 
 }  // namespace
@@ -534,8 +605,8 @@ int main(int argc, char **argv) {
     }
     const Args a = parse(argc, argv, 2);
     if (cmd == "build") return cmd_build(a);
-    if (cmd == "encode" || cmd == "decode") {
-        const int rc = cmd == "encode" ? cmd_encode(a) : cmd_decode(a);
+    if (cmd == "encode" || cmd == "decode" || cmd == "verify") {
+        const int rc = cmd == "encode" ? cmd_encode(a) : cmd_decode(a, cmd == "verify");
         // The output is complete and every device call has returned.  Free the contexts
         // (their device memory: ~15 ms) and leave without the rest of the HIP runtime's
         // teardown.  Exiting with the contexts alive cost more (wall clock after main 0.10-0.13 s

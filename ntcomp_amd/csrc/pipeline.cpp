@@ -46,11 +46,13 @@
 #include "../../include/ntcomp_host.h"
 #include "../../include/ntcomp_pipeline.h"
 #include "ntc_internal.h"
+#include "digest_core.h"
 
 namespace ntc {
 NxHooks g_nx_hooks = {nullptr, nullptr, nullptr, nullptr};  // capi.cpp fills it at load
 QHooks g_q_hooks = {nullptr, nullptr, nullptr, nullptr};
 NHooks g_n_hooks = {nullptr, nullptr, nullptr};
+DHooks g_d_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 }
 
 namespace {
@@ -218,6 +220,8 @@ struct BlockOut {  // a deflated block (its four streams' parts), or a dropped o
     ntc_name_meta nmeta{};
     uint8_t *nsec = nullptr;
     uint64_t nlen = 0;
+    bool has_d = false;              // digests on: its section of the "NTCD" file
+    ntc_digest_meta dmeta{};
 };
 
 struct Shared {
@@ -247,7 +251,7 @@ extern "C" {
 static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
                             const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx,
                             int q_mode = 0, int q_fd = -1, ntc_q_stats *qs = nullptr, int n_mode = 0, int n_fd = -1,
-                            ntc_n_stats *ns = nullptr) {
+                            ntc_n_stats *ns = nullptr, int d_mode = 0, int d_fd = -1, ntc_d_stats *ds = nullptr) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
@@ -267,6 +271,11 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     const ntc::NHooks &nh = ntc::g_n_hooks;
     if (n_mode && (!nh.set_mode || !nh.encode_names)) return NTC_ERR_UNSUPPORTED;
     ntc_n_stats NS{};
+    // d_mode / d_fd / ds: ntc_encode_file_ex3's digest side file (d_mode 0: none)
+    if (d_mode < 0 || d_mode > 1 || (d_mode ? d_fd < 0 : d_fd != -1)) return NTC_ERR_INVALID_ARG;
+    const ntc::DHooks &dh = ntc::g_d_hooks;
+    if (d_mode && (!dh.set_mode || !dh.encode_digests || !dh.index_info)) return NTC_ERR_UNSUPPORTED;
+    ntc_d_stats DS{};
     const bool keep = policy == NTC_NX_KEEP;
     ntc_nx_stats NX{};
     uint32_t nx_sub = 0;
@@ -320,6 +329,26 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             for (int i = 0; i < n; i++) ntc::g_n_hooks.set_mode(ctxs[i], 0);
         }
     } names_reset{ctxs, n_mode ? n_ctx : 0};
+    uint32_t d_k = 0;
+    uint64_t d_nodes = 0;
+    if (d_mode) {
+        if (int r = dh.index_info(ctxs[0], &d_nodes, &d_k)) return r;
+        for (int i = 0; i < n_ctx; i++)
+            if (int r = dh.set_mode(ctxs[i], 1)) {
+                for (int j = 0; j < i; j++) dh.set_mode(ctxs[j], 0);
+                return r;
+            }
+    }
+    struct DigestsReset {  // ... and with digests off
+        ntc_ctx *const *ctxs;
+        int n;
+        ~DigestsReset() {
+            for (int i = 0; i < n; i++) ntc::g_d_hooks.set_mode(ctxs[i], 0);
+        }
+    } digests_reset{ctxs, d_mode ? n_ctx : 0};
+    // the components the file can hold: what the modes of this call yield
+    const uint32_t d_components = ntc::kDgSeq | (keep ? ntc::kDgSym : 0) | (q_mode ? ntc::kDgQual : 0) |
+                                  (n_mode ? ntc::kDgName : 0);
     ntc_pipeline_opts o{};
     if (opts) o = *opts;
     const int T = o.threads > 0 ? o.threads : ntc_host_threads();
@@ -787,6 +816,22 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         return;
                     }
                 }
+                // ... and its digests (digests on), one entry per block
+                std::vector<ntc_digest_meta> dmetas;
+                if (d_mode) {
+                    uint64_t dn = 0;
+                    int rd = dh.encode_digests(ctxs[c], nullptr, 0, &dn);
+                    if (rd == NTC_ERR_CAPACITY && dn == nblk) {
+                        dmetas.resize(dn);
+                        rd = dh.encode_digests(ctxs[c], dmetas.data(), dn, &dn);
+                    } else if (rd == NTC_OK || rd == NTC_ERR_CAPACITY) {
+                        rd = NTC_ERR_FORMAT;  // (never expected: an entry per block)
+                    }
+                    if (rd) {
+                        sh.fail(rd, std::string("encode: digests: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                }
                 etrace("gpu done, first block", b.first_block);
                 std::lock_guard<std::mutex> g(sh.mu);
                 S.gpu_done_s = secs(t0, Clock::now());
@@ -816,6 +861,10 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         bo.nmeta = nmetas[k];
                         bo.left++;
                         tasks.push_back(Task{pl, metas[k], b.first_block + k, 5, npl});
+                    }
+                    if (d_mode && ok) {  // (nothing to deflate: the writer puts the 56 bytes out)
+                        bo.has_d = true;
+                        bo.dmeta = dmetas[k];
                     }
                     int order[4] = {0, 1, 2, 3};
                     std::sort(order, order + 4, [&](int x, int y) {
@@ -927,6 +976,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     };
     if (q_mode && ntc_q_write_header2(q_fd, q_mode, q_coder)) sh.fail(NTC_ERR_IO, "qualities: write failed");
     if (n_mode && ntc_n_write_header(n_fd, n_mode)) sh.fail(NTC_ERR_IO, "names: write failed");
+    if (d_mode && ntc_d_write_header(d_fd, d_components, d_k, d_nodes)) sh.fail(NTC_ERR_IO, "digests: write failed");
     uint64_t reads_written = 0;
     for (uint64_t blk = 0;; blk++) {
         BlockOut out;
@@ -978,6 +1028,15 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 NS.payload_bytes += out.nmeta.payload_bytes;
                 NS.deflated_bytes += out.nlen - 32;
             }
+            if (out.has_d) {
+                if (const int rd = ntc_d_write_section(d_fd, &out.dmeta))
+                    sh.fail(rd == NTC_ERR_IO ? rd : NTC_ERR_FORMAT, "digests: write failed");
+                DS.sections++;
+                DS.blocks_seq += out.dmeta.components & ntc::kDgSeq ? 1 : 0;
+                DS.blocks_sym += out.dmeta.components & ntc::kDgSym ? 1 : 0;
+                DS.blocks_qual += out.dmeta.components & ntc::kDgQual ? 1 : 0;
+                DS.blocks_name += out.dmeta.components & ntc::kDgName ? 1 : 0;
+            }
         } else {
             S.dropped_blocks++;
             NX.runs_in_dropped_blocks += out.nx.size();
@@ -1028,6 +1087,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     if (nx) *nx = NX;
     if (qs) *qs = QS;
     if (ns) *ns = NS;
+    if (ds) *ds = DS;
     return result;
 }
 
@@ -1055,6 +1115,14 @@ int ntc_encode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
     if (!fo || fo->struct_bytes < sizeof(ntc_file_opts2) || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
     return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
                             fo->q_fd, q, fo->n_mode, fo->n_fd, n);
+}
+
+int ntc_encode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts3 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n, ntc_d_stats *d) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts3) || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
+    return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
+                            fo->q_fd, q, fo->n_mode, fo->n_fd, n, fo->d_mode, fo->d_fd, d);
 }
 
 }  // extern "C"
@@ -1147,8 +1215,12 @@ extern "C" {
 // q_path: ntc_decode_file_ex's quality file (null: none; the output is then FASTA)
 static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
                             const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, const char *q_path = nullptr,
-                            const char *n_path = nullptr) {
-    if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
+                            const char *n_path = nullptr, const char *d_path = nullptr, ntc_d_stats *ds = nullptr,
+                            bool may_discard = false) {
+    // d_path / ds: ntc_decode_file_ex3's digest file (null: none); may_discard: out_fd -1 runs
+    // everything but the copy of the text off the device and its write
+    const bool discard = may_discard && out_fd == -1;
+    if (!ctxs || n_ctx <= 0 || !in_path || (out_fd < 0 && !discard)) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
     // the exception runs, read once; each batch finds its own by its first read (put_runs)
@@ -1235,6 +1307,82 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         for (auto &m : tmp) m.payload_off -= base;
         const uint64_t bytes = tmp.back().payload_off + tmp.back().payload_bytes;
         return ntc::g_n_hooks.decode_set_names(ctx, tmp.data(), n, nf.payload + base, bytes);
+    };
+    // the expected digests, likewise; the file names the index it was written against
+    struct DFile {
+        ntc_digest_meta *metas = nullptr;
+        uint64_t n = 0, n_nodes = 0;
+        uint32_t components = 0, k = 0;
+        ~DFile() { ntc_buffer_free(metas); }
+    } df;
+    ntc_d_stats DS{};
+    const ntc::DHooks &dh = ntc::g_d_hooks;
+    if (discard && !dh.set_discard) return NTC_ERR_UNSUPPORTED;
+    if (d_path) {
+        if (!dh.decode_set_digests || !dh.decode_digests || !dh.index_info) return NTC_ERR_UNSUPPORTED;
+        int r = ntc_d_read(d_path, &df.components, &df.k, &df.n_nodes, &df.metas, &df.n);
+        char why[200];
+        std::snprintf(why, sizeof(why), "digests: %s", r == NTC_ERR_IO ? "cannot read the side file" : "malformed side file");
+        uint64_t nodes = 0;
+        uint32_t k = 0;
+        if (!r && (r = dh.index_info(ctxs[0], &nodes, &k))) std::snprintf(why, sizeof(why), "digests: no index uploaded");
+        if (!r && (k != df.k || nodes != df.n_nodes)) {
+            r = NTC_ERR_DIGEST;
+            std::snprintf(why, sizeof(why), "digests: the file was written against another index (k = %u, %llu nodes; "
+                          "the index uploaded has k = %u, %llu nodes)", df.k, (unsigned long long)df.n_nodes, k,
+                          (unsigned long long)nodes);
+        }
+        if (r) {
+            if (stats) {
+                std::memset(stats, 0, sizeof(*stats));
+                stats->bad_read = -1;
+                std::snprintf(stats->error, sizeof(stats->error), "%s", why);
+            }
+            return r;
+        }
+    }
+    // hands ctx the expected digests of blocks [first, first + n)
+    auto put_digests = [&](ntc_ctx *ctx, uint64_t first, uint64_t n) -> int {
+        if (!d_path) return NTC_OK;
+        if (first + n > df.n) return NTC_ERR_FORMAT;
+        return dh.decode_set_digests(ctx, df.metas + first, n);
+    };
+    // after a batch's decode call (rc): what it checked into the stats (under sh.mu), and for
+    // NTC_ERR_DIGEST the block in the file's numbering, its first read and the component
+    auto digest_verdict = [&](ntc_ctx *ctx, int rc, uint64_t first, uint64_t n, uint64_t first_read, std::string &msg,
+                              int64_t &bad_read) {
+        if (!d_path || n == 0 || (rc != NTC_OK && rc != NTC_ERR_DIGEST)) return;
+        std::vector<ntc_digest_meta> got(n);
+        uint64_t have = 0;
+        if (dh.decode_digests(ctx, got.data(), n, &have) != NTC_OK || have != n) return;
+        static const char *const names[4] = {"seq", "sym", "qual", "name"};
+        uint64_t read = first_read;
+        for (uint64_t b = 0; b < n; b++) {
+            const ntc_digest_meta &e = df.metas[first + b], &g = got[b];
+            const uint64_t ed[4] = {e.d_seq, e.d_sym, e.d_qual, e.d_name}, gd[4] = {g.d_seq, g.d_sym, g.d_qual, g.d_name};
+            if (rc == NTC_ERR_DIGEST) {
+                int at = g.n_bases != e.n_bases ? 0 : -1;
+                for (int c = 0; c < 4 && at < 0; c++)
+                    if ((g.components >> c & 1) && ed[c] != gd[c]) at = c;
+                if (at >= 0) {
+                    char buf[240];
+                    std::snprintf(buf, sizeof(buf), "digest mismatch in block %llu (first read %llu), component %s: expected "
+                                  "0x%016llx, computed 0x%016llx", (unsigned long long)(first + b), (unsigned long long)read,
+                                  names[at], (unsigned long long)ed[at], (unsigned long long)gd[at]);
+                    msg = buf;
+                    bad_read = (int64_t)read;
+                    return;
+                }
+            } else {
+                DS.sections++;
+                DS.blocks_seq += g.components & ntc::kDgSeq ? 1 : 0;
+                DS.blocks_sym += g.components & ntc::kDgSym ? 1 : 0;
+                DS.blocks_qual += g.components & ntc::kDgQual ? 1 : 0;
+                DS.blocks_name += g.components & ntc::kDgName ? 1 : 0;
+                DS.not_checkable |= e.components & ~g.components;
+            }
+            read += e.n_reads;
+        }
     };
     // the names' bytes of blocks [first, first + n) (those the side file has): room in the text
     auto name_room = [&](uint64_t first, uint64_t n) -> uint64_t {
@@ -1436,6 +1584,17 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     return;
                 }
             }
+            // out_fd -1: the text stays on the device (the context drops the option when this thread ends)
+            struct Discard {
+                ntc_ctx *ctx;
+                ~Discard() {
+                    if (ctx) ntc::g_d_hooks.set_discard(ctx, 0);
+                }
+            } discard_reset{discard ? ctxs[c] : nullptr};
+            if (discard && dh.set_discard(ctxs[c], 1)) {
+                sh.fail(NTC_ERR_HIP, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                return;
+            }
             std::vector<ntc_nx_run> nx_tmp;  // a batch's exception runs, renumbered from its first read
             std::vector<ntc_qual_meta> q_tmp;  // ... and its quality sections
             std::vector<ntc_name_meta> n_tmp;  // ... and its name sections
@@ -1481,7 +1640,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
                                           digits_total(sl.first_id, sl.n_reads) + name_room(sl.first_block, nb) + 64;
                     const auto tf = Clock::now();
-                    if (!ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
+                    if (!discard && !ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
                         sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
                         return;
                     }
@@ -1502,13 +1661,26 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                                                          : std::string("decode: ") + ntc_last_error(ctxs[c]));
                         return;
                     }
-                    const int rf = ntc_decode_fasta_unpacked(ctxs[c], sl.first_id, sl.text, sl.cap_text, &len);
+                    if (const int rx = put_digests(ctxs[c], sl.first_block, nb)) {
+                        sh.fail(rx, rx == NTC_ERR_FORMAT ? "digests: fewer sections than blocks"
+                                                         : std::string("decode: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
+                    const int rf = ntc_decode_fasta_unpacked(ctxs[c], sl.first_id, sl.text, discard ? 0 : sl.cap_text, &len);
                     add_time(t_gpu, secs(tf, Clock::now()));
                     if (rf) {
-                        sh.fail(rf, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                        std::string msg = std::string("decode: ") + ntc_last_error(ctxs[c]);
+                        int64_t bad = -1;
+                        digest_verdict(ctxs[c], rf, sl.first_block, nb, sl.first_id - 1, msg, bad);
+                        sh.fail(rf, msg, bad);
                         return;
                     }
                     std::lock_guard<std::mutex> g(sh.mu);
+                    {
+                        std::string unused;
+                        int64_t bad = -1;
+                        digest_verdict(ctxs[c], NTC_OK, sl.first_block, nb, sl.first_id - 1, unused, bad);
+                    }
                     sl.text_len = len;
                     sl.decoded = true;
                     trace("decoded", b);
@@ -1530,7 +1702,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
                                       digits_total(sl.first_id, sl.n_reads) + name_room(sl.first_block, sl.n_blocks) + 64;
                 const auto tg = Clock::now();
-                if (!ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
+                if (!discard && !ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
                     sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
                     return;
                 }
@@ -1553,14 +1725,28 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                                                      : std::string("decode: ") + ntc_last_error(ctxs[c]));
                     return;
                 }
+                const uint64_t nbk = sl.bad_block >= 0 ? (uint64_t)sl.bad_block : sl.n_blocks;
+                if (const int rx = put_digests(ctxs[c], sl.first_block, nbk)) {
+                    sh.fail(rx, rx == NTC_ERR_FORMAT ? "digests: fewer sections than blocks"
+                                                     : std::string("decode: ") + ntc_last_error(ctxs[c]));
+                    return;
+                }
                 const int rc = ntc_decode_fasta(ctxs[c], sl.recs, nrec, sl.n_reads, sl.n_bases, sl.first_id, sl.text,
-                                                sl.cap_text, &len);
+                                                discard ? 0 : sl.cap_text, &len);
                 add_time(t_gpu, secs(tg, Clock::now()));
                 if (rc) {
-                    sh.fail(rc, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                    std::string msg = std::string("decode: ") + ntc_last_error(ctxs[c]);
+                    int64_t bad = -1;
+                    digest_verdict(ctxs[c], rc, sl.first_block, nbk, sl.first_id - 1, msg, bad);
+                    sh.fail(rc, msg, bad);
                     return;
                 }
                 std::lock_guard<std::mutex> g(sh.mu);
+                {
+                    std::string unused;
+                    int64_t bad = -1;
+                    digest_verdict(ctxs[c], NTC_OK, sl.first_block, nbk, sl.first_id - 1, unused, bad);
+                }
                 sl.text_len = len;
                 sl.decoded = true;
                 trace("decoded", b);
@@ -1586,7 +1772,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 DSlot &sl = slots[(size_t)j];
                 const bool ok = (gpu_unpack ? ensure_pinned((void **)&sl.pay, &sl.cap_pay, np + 8)
                                             : ensure_pinned((void **)&sl.recs, &sl.cap_recs, nr * 8 + 8)) &&
-                                ensure_pinned((void **)&sl.text, &sl.cap_text, nr * 48 + (1u << 20));
+                                (discard || ensure_pinned((void **)&sl.text, &sl.cap_text, nr * 48 + (1u << 20)));
                 if (!ok) sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
             });
         for (auto &t : pre) t.join();
@@ -1736,7 +1922,7 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             slp = &slot_of(b);
         }
         const auto tw = Clock::now();
-        if (!write_text(slp->text, slp->text_len)) sh.fail(NTC_ERR_IO, "write failed");
+        if (!discard && !write_text(slp->text, slp->text_len)) sh.fail(NTC_ERR_IO, "write failed");
         add_time(t_write, secs(tw, Clock::now()));
         std::lock_guard<std::mutex> g(sh.mu);
         if (b == 0) S.first_batch_s = secs(t0, Clock::now());
@@ -1780,6 +1966,22 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         result = NTC_ERR_FORMAT;
         sh.msg = "names: more sections than blocks (the side file belongs to another encoding)";
     }
+    // under a digest file the lenient endings are errors: the file is known not to be whole
+    if (result == NTC_OK && d_path && stop_batch >= 0) {
+        result = NTC_ERR_FORMAT;
+        char buf[120];
+        std::snprintf(buf, sizeof(buf), "damaged block %llu: the output ends before it", (unsigned long long)S.blocks);
+        sh.msg = buf;
+    }
+    if (result == NTC_OK && d_path && !clean_end) {
+        result = NTC_ERR_FORMAT;
+        sh.msg = "truncated input: the file ends inside a block";
+    }
+    if (result == NTC_OK && d_path && df.n != blocks.size()) {
+        result = NTC_ERR_FORMAT;
+        sh.msg = "digests: more sections than blocks (the input is truncated, or the side file belongs to another "
+                 "encoding)";
+    }
     S.dropped_blocks = blocks.size() - S.blocks;  // after a damaged block (or none)
     S.alloc_s += t_pin.load();
     S.parse_s = t_unzip.load();
@@ -1787,7 +1989,8 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     S.write_s = t_write.load();
     S.wall_s = secs(t0, Clock::now());
     S.threads = T;
-    S.bad_read = -1;
+    S.bad_read = result == NTC_ERR_DIGEST ? sh.bad_read : -1;
+    if (ds) *ds = DS;
     if (result != NTC_OK)
         std::snprintf(S.error, sizeof(S.error), "%s", sh.msg.c_str());
     else if (stop_batch >= 0)  // not an error for the reference either: its loop just ends
@@ -1817,6 +2020,13 @@ int ntc_decode_file_ex2(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
                         const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats) {
     if (!fo || fo->struct_bytes < sizeof(ntc_file_opts2)) return NTC_ERR_INVALID_ARG;
     return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path, fo->n_path);
+}
+
+int ntc_decode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts3 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts3)) return NTC_ERR_INVALID_ARG;
+    return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path, fo->n_path, fo->d_path, d,
+                            true);
 }
 
 }  // extern "C"
