@@ -445,6 +445,43 @@ int ntc_d_write_section(int fd, const ntc_digest_meta *meta);
 int ntc_d_read(const char *path, uint32_t *components, uint32_t *k, uint64_t *n_nodes, ntc_digest_meta **metas,
                uint64_t *n_blocks);
 
+/* ---- paired-end reads ------------------------------------------------------------------------ */
+/* A paired archive is an ordinary one whose reads alternate: read 2p is mate 1 of pair p, read
+ * 2p + 1 its mate 2.  No format changes and nothing records it: the caller says so, here as at
+ * decode.  ntc_ctx_set_option(ctx, "paired", v): 0 off (default: nothing below is launched),
+ * 1 pairs with the mate check, 2 pairs without it; anything else NTC_ERR_INVALID_ARG.
+ *
+ * The mate rule (check 1): id(N) = the name N cut before its first space or tab; with a =
+ * id(name of read 2p) and b = id(name of read 2p + 1), when a ends in "/1" and b ends in "/2"
+ * both lose those two bytes; the mates agree iff a == b byte for byte.  (Two empty names
+ * agree; "x/1" beside "x" and "x/2" beside "x/1" do not.)
+ *
+ * Under 1 and 2:
+ *   ntc_encode_pack_fastq takes its text as interleaved pairs: n_reads and block_reads must be
+ *     even (NTC_ERR_INVALID_ARG).  Under 1 the lowest pair whose mates disagree fails the call
+ *     with NTC_ERR_FORMAT, bad_read = 2p, before anything is encoded; a failed call leaves no
+ *     sections.
+ *   ntc_encode_pack_fastq_paired takes the mates as two texts of n_pairs records each, weaves
+ *     them on the GPU (record p of text 1, then record p of text 2; a last line without its
+ *     newline gets one; line ends are otherwise copied as they are) and does what
+ *     ntc_encode_pack_fastq does for 2 n_pairs reads: same metas, payload and sections as that
+ *     call on the interleaved text.  NTC_ERR_INVALID_ARG under "paired" 0; NTC_ERR_CAPACITY,
+ *     before anything is read, unless bytes1 + bytes2 + 2 < 4 GiB; NTC_ERR_FORMAT, before
+ *     anything is woven or encoded, when a text does not hold exactly 4 n_pairs lines (a last
+ *     line without its newline counts as one).
+ *   ntc_decode_fasta and ntc_decode_fasta_unpacked return the text split: all mate-1 records
+ *     in order, then all mate-2 records.  *out_len and the capacity protocol are unchanged (the
+ *     size is the total); an odd read count is NTC_ERR_FORMAT.  Without names the reads keep
+ *     the archive's numbering (seq.1, seq.3, ... in part 1).  Under "discard_text" nothing is
+ *     split.  ntc_decode_pair_split: *first_bytes = the bytes of part 1 of the last such call
+ *     (0 when it failed); NTC_ERR_INVALID_ARG when the last text decode was not a paired one.
+ * The calls that carry neither names nor text (ntc_encode_pack_batch, ntc_encode_batch*,
+ * ntc_decode_batch*) ignore the option.                                                       */
+int ntc_encode_pack_fastq_paired(ntc_ctx *ctx, const uint8_t *fastq1, uint64_t bytes1, const uint8_t *fastq2,
+                                 uint64_t bytes2, uint64_t n_pairs, uint32_t block_reads, ntc_block_meta *meta,
+                                 uint8_t **payload, uint64_t *payload_bytes, uint64_t *n_bases, int64_t *bad_read);
+int ntc_decode_pair_split(ntc_ctx *ctx, uint64_t *first_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,64 @@ int ntc_encode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
 int ntc_decode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts3 *fo,
                         const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d);
 
+/* ---- paired-end reads: two mate files in, two out -------------------------------------------- */
+/* ntc_encode_file_ex4 / ntc_decode_file_ex4 are ntc_encode_file_ex3 / ntc_decode_file_ex3 for
+ * paired archives (ntcomp_codec.h "paired-end reads": read 2p is mate 1 of pair p, read 2p + 1
+ * its mate 2; no format changes).  ntc_file_opts4 holds ntc_file_opts3's fields in the same
+ * order, then its own; struct_bytes must be at least sizeof(ntc_file_opts4).  pair_mode 0: the
+ * calls are the ex3 ones (mate_path must be NULL, out_fd2 -1).  pair_mode 1 (mates checked by
+ * their ids) or 2 (not checked):
+ * Encode: with mate_path, in_path holds the mate-1 records and mate_path the mate-2 records;
+ * both go through the same ingest (mapped plain, or streamed from any supported compression,
+ * not necessarily the same), a batch is n records of each -- 2 n a multiple of 65,536, or the
+ * inputs' end -- and the GPU weaves them (ntc_encode_pack_fastq_paired).  encoded.dat and the
+ * side files are byte for byte those of a single-file encode of the interleaved file, whatever
+ * the number of contexts and the compression of either input.  One input ending while the other
+ * still holds a record is NTC_ERR_FORMAT, "mate files hold different numbers of records" in
+ * stats->error.  Without mate_path, in_path is interleaved: the check is the only new work, and
+ * an odd number of reads is NTC_ERR_FORMAT.  A pair whose mates disagree (mode 1) ends the call
+ * with NTC_ERR_FORMAT and stats->bad_read = the file index of its mate 1.  Pairs exist only where
+ * the GPU parses the text: host_parse = 1, an input that is not FASTQ and a batch that needs the
+ * host parser (a blank line, records that are not four lines each) are NTC_ERR_UNSUPPORTED, with
+ * the case in stats->error.  The contexts' "paired" option is set for the call and left at 0.
+ * p (may be NULL): pairs encoded, the mode, the text bytes of each mate.
+ * Decode: out_fd gets the mate-1 records of every batch and out_fd2 (>= 0, not closed) the
+ * mate-2 records, in batch order; out_fd2 < 0 is NTC_ERR_INVALID_ARG unless out_fd is -1 (the
+ * verification pass, which splits nothing).  The side files work as ever, keyed by the read's
+ * index in the archive; without a name file the reads keep the archive's numbering (seq.1,
+ * seq.3, ... in out_fd).  p: pairs decoded, the bytes written to each.
+ * With the GPU stage's hook table null (a build without it), pair_mode != 0 is
+ * NTC_ERR_UNSUPPORTED.                                                                         */
+typedef struct ntc_file_opts4 {
+    uint32_t struct_bytes; /* sizeof(ntc_file_opts4)                           */
+    int32_t nx_policy;     /* NTC_NX_*                                         */
+    int32_t nx_fd;         /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;        /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;          /* encode: quality file, -1 = none                  */
+    const char *nx_path;   /* decode: exceptions file, NULL = none             */
+    const char *q_path;    /* decode: quality file, NULL = none                */
+    int32_t n_mode;        /* 0 drop, 1 keep, 2 id                             */
+    int32_t n_fd;          /* encode: name file, -1 = none                     */
+    const char *n_path;    /* decode: name file, NULL = none                   */
+    int32_t d_mode;        /* 0 none, 1 write digests                          */
+    int32_t d_fd;          /* encode: digest file, -1 = none                   */
+    const char *d_path;    /* decode: digest file, NULL = none                 */
+    int32_t pair_mode;     /* 0 off, 1 pairs + mate check, 2 pairs, no check   */
+    const char *mate_path; /* encode: the mate-2 input, NULL = in_path is interleaved */
+    int32_t out_fd2;       /* decode: the mate-2 text, -1 = none               */
+} ntc_file_opts4;
+typedef struct ntc_p_stats {
+    uint64_t pairs;        /* encoded / decoded                                */
+    uint64_t bytes1, bytes2; /* text of each mate read (encode, mate_path) / written (decode) */
+    uint32_t mode;         /* the pair_mode of the call                        */
+    uint32_t reserved;
+} ntc_p_stats;
+int ntc_encode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts4 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n, ntc_d_stats *d, ntc_p_stats *p);
+int ntc_decode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts4 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,7 @@ EXPORTED = [
     "ntc_n_write_section", "ntc_n_read", "ntc_encode_file_ex2", "ntc_decode_file_ex2",
     "ntc_encode_digests", "ntc_decode_set_digests", "ntc_decode_digests", "ntc_d_write_header",
     "ntc_d_write_section", "ntc_d_read", "ntc_encode_file_ex3", "ntc_decode_file_ex3",
+    "ntc_encode_pack_fastq_paired", "ntc_decode_pair_split", "ntc_encode_file_ex4", "ntc_decode_file_ex4",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -86,6 +87,15 @@ NAME_MAX, NAME_GROUP = 4095, 64
 
 def _names_code(names):
     return NAMES[names] if isinstance(names, str) else int(names)
+
+
+# paired-end reads (ctx option "paired", include/ntcomp_codec.h): off, pairs with the mate
+# check on the ids, pairs without a check
+PAIR_MODES = {"off": 0, "ids": 1, "nocheck": 2}
+
+
+def _pair_code(paired):
+    return PAIR_MODES[paired] if isinstance(paired, str) else int(paired)
 
 
 def _policy_code(non_acgt):
@@ -193,6 +203,20 @@ class FileOpts2(ctypes.Structure):
 class FileOpts3(ctypes.Structure):
     """ntc_file_opts3 (include/ntcomp_pipeline.h): the three side files and the digest file."""
     _fields_ = FileOpts2._fields_ + [("d_mode", ctypes.c_int32), ("d_fd", ctypes.c_int32), ("d_path", ctypes.c_char_p)]
+
+
+class FileOpts4(ctypes.Structure):
+    """ntc_file_opts4 (include/ntcomp_pipeline.h): ntc_file_opts3 and the pairs."""
+    _fields_ = FileOpts3._fields_ + [("pair_mode", ctypes.c_int32), ("mate_path", ctypes.c_char_p), ("out_fd2", ctypes.c_int32)]
+
+
+class PStats(ctypes.Structure):
+    """ntc_p_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [("pairs", ctypes.c_uint64), ("bytes1", ctypes.c_uint64), ("bytes2", ctypes.c_uint64),
+                ("mode", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class DStats(ctypes.Structure):
@@ -332,6 +356,9 @@ def lib():
         "ntc_fastq_parse": (I, [P, P, u64, u64, P, u64, P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int64)]),
         "ntc_encode_pack_fastq": (I, [P, P, u64, u64, u32, P, ctypes.POINTER(P), ctypes.POINTER(u64),
                                       ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int64)]),
+        "ntc_encode_pack_fastq_paired": (I, [P, P, u64, P, u64, u64, u32, P, ctypes.POINTER(P), ctypes.POINTER(u64),
+                                             ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int64)]),
+        "ntc_decode_pair_split": (I, [P, ctypes.POINTER(u64)]),
         "ntc_fastx_open": (I, [ctypes.c_char_p, ctypes.POINTER(P)]),
         "ntc_fastx_next_batch": (I, [P, u64, u64, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(u64)]),
         "ntc_fastx_close": (None, [P]),
@@ -378,6 +405,11 @@ def lib():
         "ntc_encode_file_ex3": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts3), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
                                     ctypes.POINTER(NStats), ctypes.POINTER(DStats)]),
+        "ntc_encode_file_ex4": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts4), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
+                                    ctypes.POINTER(NStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats)]),
+        "ntc_decode_file_ex4": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts4), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats)]),
         "ntc_decode_file_ex3": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts3), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats)]),
         "ntc_nx_write": (I, [I, P, u64, u32, I]),
@@ -915,6 +947,59 @@ class GpuContext:
             out += (self.encode_digests(),)
         return out
 
+    # ---- paired-end reads ---------------------------------------------------------------
+    @property
+    def paired(self):
+        """Option "paired" (PAIR_MODES): 0 off, 1 reads 2p and 2p + 1 are mates and their ids are
+        checked at encode, 2 mates without the check.  Set, encode_pack_fastq takes interleaved
+        text and decode_fasta_unpacked returns the two parts."""
+        return self.get_option("paired")
+
+    @paired.setter
+    def paired(self, mode):
+        self.set_option("paired", _pair_code(mode))
+
+    def encode_pack_fastq_paired(self, text1, text2, n_pairs, block_reads=65536, non_acgt=None, qualities=None,
+                                 names=None, quality_coder=None, digests=None):
+        """encode_pack_fastq of the two mate texts woven on the GPU
+        (ntc_encode_pack_fastq_paired): record p of text1, then record p of text2.  Needs
+        `paired` set; returns what encode_pack_fastq returns for the interleaved text."""
+        t1 = np.frombuffer(bytes(text1), dtype=np.uint8) if len(text1) else np.zeros(1, dtype=np.uint8)
+        t2 = np.frombuffer(bytes(text2), dtype=np.uint8) if len(text2) else np.zeros(1, dtype=np.uint8)
+        nb = (2 * n_pairs + block_reads - 1) // block_reads
+        metas = (BlockMeta * max(nb, 1))()
+        out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
+        with self._policy(non_acgt), self._qmode(qualities), self._nmode(names), self._qcoder(quality_coder), \
+                self._digests(digests):
+            rc = self.L.ntc_encode_pack_fastq_paired(self.h, _p(t1), len(text1), _p(t2), len(text2), n_pairs,
+                                                     block_reads, metas, ctypes.byref(out), ctypes.byref(used),
+                                                     ctypes.byref(nbases), ctypes.byref(bad))
+        if rc:
+            self.L.ntc_buffer_free(out)
+            e = NtcError(rc, self.L.ntc_last_error(self.h).decode(errors="replace"))
+            e.bad_read = bad.value
+            raise e
+        try:
+            payload = ctypes.string_at(out.value, used.value) if used.value else b""
+        finally:
+            self.L.ntc_buffer_free(out)
+        out = (list(metas)[:nb], payload, int(nbases.value))
+        if non_acgt is not None:
+            out += (self.exceptions(),)
+        if qualities is not None:
+            out += (self.qualities(),)
+        if names is not None:
+            out += (self.names(),)
+        if digests is not None:
+            out += (self.encode_digests(),)
+        return out
+
+    def pair_split(self):
+        """Bytes of part 1 of the last paired text decode (ntc_decode_pair_split)."""
+        first = ctypes.c_uint64()
+        self._check(self.L.ntc_decode_pair_split(self.h, ctypes.byref(first)), "ntc_decode_pair_split")
+        return int(first.value)
+
     def encode_status(self):
         bad, n = ctypes.c_int64(-1), ctypes.c_uint64()
         self._check(self.L.ntc_encode_status(self.h, ctypes.byref(bad), ctypes.byref(n)), "ntc_encode_status")
@@ -956,7 +1041,11 @@ class GpuContext:
         out = np.zeros(max(1, need.value), dtype=np.uint8)
         self._check(self.L.ntc_decode_fasta_unpacked(self.h, first_id, _p(out), len(out), ctypes.byref(need)),
                     "ntc_decode_fasta_unpacked")
-        return out[:need.value].tobytes()
+        text = out[:need.value].tobytes()
+        if self.paired and not self.get_option("discard_text"):  # the two parts: all mate-1 records, all mate-2 records
+            first = self.pair_split()
+            return text[:first], text[first:]
+        return text
 
     def synchronize(self):
         self._check(self.L.ntc_ctx_synchronize(self.h), "ntc_ctx_synchronize")
@@ -1174,7 +1263,8 @@ def concat_streams(blocks):
 
 # ---- FASTX ingest ---------------------------------------------------------------------
 def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_bases=0, deflate="zlib",
-                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1, names=None, n_fd=-1, d_fd=None):
+                host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1, names=None, n_fd=-1, d_fd=None,
+                mate_path=None, pair_mode=None):
     """`ntcomp encode` file to file (ntc_encode_file, include/ntcomp_pipeline.h): FASTX ->
     GPU encode + block packer on every context -> deflate pool -> encoded.dat on out_fd.
     A plain FASTQ is parsed on the GPU unless host_parse.  Returns the per-stage stats as
@@ -1186,8 +1276,29 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     (ntc_q_stats).  names ("drop", "keep", "id"; ntc_encode_file_ex2): "keep" and "id" write the
     blocks' name sections to n_fd ("NTCN"), and the stats gain an "n" dict (ntc_n_stats).  d_fd (None:
     no digests; ntc_encode_file_ex3): the blocks' content digests, computed on the GPU, go to that
-    descriptor ("NTCD"), and the stats gain a "d" dict (ntc_d_stats)."""
+    descriptor ("NTCD"), and the stats gain a "d" dict (ntc_d_stats).  pair_mode ("ids", "nocheck";
+    ntc_encode_file_ex4): the reads are pairs, in_path interleaved, or with mate_path the mate-1 file
+    beside the mate-2 file mate_path (then pair_mode defaults to "ids"); the stats gain a "p" dict
+    (ntc_p_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
+    if mate_path is not None and pair_mode is None:
+        pair_mode = "ids"
+    if pair_mode is not None and _pair_code(pair_mode):
+        fo = FileOpts4(ctypes.sizeof(FileOpts4), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
+                       None, None, _names_code(names or 0), n_fd, None, 0 if d_fd is None else 1, -1 if d_fd is None else d_fd,
+                       None, _pair_code(pair_mode), None if mate_path is None else os.fsencode(mate_path), -1)
+        nx, q, n, ds, ps = NxStats(), QStats(), NStats(), DStats(), PStats()
+        d = _run_pipeline("ntc_encode_file_ex4", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                          tail=(ctypes.byref(nx), ctypes.byref(q), ctypes.byref(n), ctypes.byref(ds), ctypes.byref(ps)))
+        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
+        if qualities is not None:
+            d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
+        if names is not None:
+            d["n"] = {k: int(getattr(n, k)) for k, _ in NStats._fields_}
+        if d_fd is not None:
+            d["d"] = ds.as_dict()
+        d["p"] = ps.as_dict()
+        return d
     if d_fd is not None:
         fo = FileOpts3(ctypes.sizeof(FileOpts3), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
                        None, None, _names_code(names or 0), n_fd, None, 1, d_fd, None)
@@ -1230,7 +1341,7 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
 
 
 def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None, n_path=None,
-                d_path=None):
+                d_path=None, out_fd2=-1, pair_mode=None):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
@@ -1244,8 +1355,25 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
     block is checked on the GPU against it (ntc_decode_file_ex3); NtcError(NTC_ERR_DIGEST) with
     .bad_read = the first read of the block that differs, or for a file written against another
     index; a damaged or truncated input is then NTC_ERR_FORMAT; the stats gain a "d" dict
-    (ntc_d_stats).  With d_path, out_fd -1 checks without copying or writing the text."""
+    (ntc_d_stats).  With d_path, out_fd -1 checks without copying or writing the text.  pair_mode
+    ("ids" or "nocheck": the archive holds pairs; ntc_decode_file_ex4): the mate-1 records go to
+    out_fd and the mate-2 records to out_fd2; the stats gain a "p" dict (ntc_p_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
+    if pair_mode is not None and _pair_code(pair_mode):
+        enc = lambda p: None if p is None else os.fsencode(p)
+        fo = FileOpts4(ctypes.sizeof(FileOpts4), 0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1,
+                       enc(d_path), _pair_code(pair_mode), None, out_fd2)
+        ds, ps = DStats(), PStats()
+        try:
+            d = _run_pipeline("ntc_decode_file_ex4", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                              tail=(ctypes.byref(ds), ctypes.byref(ps)))
+        except NtcError as e:
+            e.stats["d"] = ds.as_dict()
+            raise
+        if d_path is not None:
+            d["d"] = ds.as_dict()
+        d["p"] = ps.as_dict()
+        return d
     if d_path is not None:
         enc = lambda p: None if p is None else os.fsencode(p)
         fo = FileOpts3(ctypes.sizeof(FileOpts3), 0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1,

@@ -215,6 +215,22 @@ def _check_d_args(args, command, others):
         _bad_args(f"{command}: --digest-file names a file this call uses already: {d}")
 
 
+def _check_p_args(args):
+    """encode: --mate-file R2 or --interleaved make the reads pairs; --mate-check ids|off goes with either."""
+    if args.mate_file is not None and args.interleaved:
+        _bad_args("encode: --mate-file and --interleaved exclude each other")
+    if args.mate_file == "":
+        _bad_args("encode: --mate-file needs a path")
+    pairs = args.mate_file is not None or args.interleaved
+    if args.mate_check is not None and not pairs:
+        _bad_args("encode: --mate-check needs --mate-file or --interleaved")
+    if args.mate_check not in (None, "ids", "off"):
+        _bad_args("encode: --mate-check: ids or off")
+    if pairs and args.host_parse:
+        _bad_args("encode: pairs are woven and checked on the GPU: not with --host-parse")
+    return None if not pairs else "nocheck" if args.mate_check == "off" else "ids"
+
+
 def _component_names(mask):
     return ",".join(n for c, n in enumerate(("seq", "sym", "qual", "name")) if mask >> c & 1) or "-"
 
@@ -227,6 +243,7 @@ def cmd_encode(args):
     _check_q_args(args)
     _check_n_args(args)
     _check_d_args(args, "encode", (args.exceptions, args.quality_file, args.name_file, args.query_file))
+    pair_mode = _check_p_args(args)
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     log("Loading SBWT index...")
@@ -269,6 +286,8 @@ def cmd_encode(args):
             nx_args.update(names=args.names, n_fd=n_file.fileno())
         if d_file:
             nx_args.update(d_fd=d_file.fileno())
+        if pair_mode:
+            nx_args.update(pair_mode=pair_mode, mate_path=args.mate_file)
         res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, deflate=args.deflate,
                                                   host_parse=args.host_parse, **nx_args)
@@ -300,7 +319,9 @@ def cmd_encode(args):
               **({"qualities": args.qualities, "quality_coder": args.quality_coder or "pack",
                   **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}),
               **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}),
-              **({"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"} if "d" in res else {}))
+              **({"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"} if "d" in res else {}),
+              **({"pairs": res["p"]["pairs"], "mate_check": "off" if pair_mode == "nocheck" else "ids",
+                  "mate1_bytes": res["p"]["bytes1"], "mate2_bytes": res["p"]["bytes2"]} if "p" in res else {}))
 
 
 def cmd_decode(args, verify=False):
@@ -317,16 +338,25 @@ def cmd_decode(args, verify=False):
     log("Verifying encoded data..." if verify else "Decoding encoded data...")
     out = sys.stdout.buffer
     out.flush()
+    mate_out = None  # a paired archive: the mate-1 records to stdout, the mate-2 records to --mate-out
+    if getattr(args, "mate_out", None) is not None:
+        try:
+            mate_out = open(args.mate_out, "wb")
+        except OSError:
+            raise SystemExit(f"ntcomp: decode: cannot write {args.mate_out}")
+    p_args = dict(out_fd2=mate_out.fileno(), pair_mode="nocheck") if mate_out else {}
     try:
         res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, -1 if verify else out.fileno(),
                                                   threads=args.threads, blocks_per_batch=args.blocks_per_batch,
                                                   nx_path=args.exceptions, q_path=args.quality_file,
-                                                  n_path=args.name_file, d_path=args.digest_file)
+                                                  n_path=args.name_file, d_path=args.digest_file, **p_args)
     except nt.NtcError as e:
         bad = getattr(e, "bad_read", -1)
         raise SystemExit(f"ntcomp {command}: {e}" + (f" (read {bad + 1})" if e.code == 12 and bad is not None and bad >= 0
                                                      else ""))
     finally:
+        if mate_out:
+            mate_out.close()
         for c in ctxs:
             c.close()
     if res["dropped_blocks"]:
@@ -343,7 +373,9 @@ def cmd_decode(args, verify=False):
     st.report(command=command, gpus=len(ctxs), threads=res["threads"], reads=res["reads"], blocks=res["blocks"],
               pipeline_wall_s=round(res["wall_s"], 3),
               **({**{"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"},
-                  "d_not_checkable": _component_names(res["d"]["not_checkable"])} if "d" in res else {}))
+                  "d_not_checkable": _component_names(res["d"]["not_checkable"])} if "d" in res else {}),
+              **({"pairs": res["p"]["pairs"], "mate1_bytes": res["p"]["bytes1"], "mate2_bytes": res["p"]["bytes2"]}
+                 if "p" in res else {}))
 
 
 def main(argv=None):
@@ -413,6 +445,13 @@ def main(argv=None):
     e.add_argument("--name-file", metavar="PATH", help="with --names keep or id: the side file to write")
     e.add_argument("--digest-file", metavar="PATH",
                    help="also write per-block content digests, computed on the GPU, for decode / verify --digest-file")
+    e.add_argument("--mate-file", metavar="R2",
+                   help="paired-end reads: the query file holds the mate-1 records, R2 the mate-2 records (any supported "
+                        "compression each); the GPU weaves them, reads 2p and 2p+1 of the archive are a pair")
+    e.add_argument("--interleaved", action="store_true", help="paired-end reads: the query file already alternates the mates")
+    e.add_argument("--mate-check", default=None, metavar="CHECK",
+                   help="ids (default): the mates' ids (cut at the first blank, /1 and /2 stripped) are compared on the "
+                        "GPU; off: they are not")
     d = sub.add_parser("decode", help="Decode data written with Encode")
     d.add_argument("input_path", help="File with encoded fastX data.")
     d.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
@@ -433,6 +472,8 @@ def main(argv=None):
                    help="the digest file of encode --digest-file: every block is checked against it on the GPU; another "
                         "index, a damaged or truncated file or a side file of another run is an error that names the "
                         "block and the component")
+    d.add_argument("--mate-out", metavar="R2.out",
+                   help="the archive holds pairs: the mate-1 records go to stdout, the mate-2 records to R2.out")
     v = sub.add_parser("verify", help="Check encoded data against its digest file without writing the text")
     v.add_argument("input_path", help="File with encoded fastX data.")
     v.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")

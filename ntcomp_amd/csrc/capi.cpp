@@ -24,6 +24,7 @@
 #include "quality_core.h"
 #include "names_core.h"
 #include "digest_core.h"
+#include "pair_core.h"
 #include "ntc_internal.h"
 
 using namespace ntc;
@@ -51,7 +52,8 @@ enum WsSlot {
     WS_Q_QUALS, WS_Q_BLOCKS, WS_Q_PAYLOAD, WS_QD_IN, WS_QD_QUALS,
     WS_QR_COUNTS, WS_QR_CUM, WS_QR_SCRATCH, WS_QR_SCAN,
     WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES,
-    WS_DG_TABLE, WS_DGD_IN, WS_COUNT
+    WS_DG_TABLE, WS_DGD_IN,
+    WS_PAIR_IN, WS_PAIR_TAB, WS_PAIR_ST, WS_PAIR_SCAN, WS_PAIR_OUT, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -81,7 +83,7 @@ struct ntc_ctx {
     unsigned long long *d_status = nullptr;
     // status mailbox in pinned host memory: {status, count a, count b}, written by k_status_box
     // at the end of a device call, so *_status() is one stream sync instead of D2H copies
-    // (16 words: 0-3 k_status_box, 4-5 non-ACGT, 6-7 qualities, 8-9 names)
+    // (16 words: 0-3 k_status_box, 4-5 non-ACGT, 6-7 qualities, 8-9 names, 10-12 pairs)
     uint64_t *h_box = nullptr;
     bool box_valid = false;
     // the records of the last ntc_unpack_streams (in WS_UNP_RECS) and their read / base counts
@@ -174,6 +176,11 @@ struct ntc_ctx {
     std::vector<ntc_digest_meta> dd_expected, dd_computed;
     int discard_text = 0;  // option "discard_text": a FASTA decode call formats its text and leaves it on the device
     uint32_t dd_checkable = 0;  // the components that call could compute
+    // paired-end reads (pairs.hip): the option (0 off, 1 pairs with the mate check, 2 pairs
+    // without it); whether the last text decode was split, and the bytes of its first part
+    int paired = 0;
+    bool pair_valid = false;
+    uint64_t pair_first = 0;
     FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
@@ -1836,6 +1843,11 @@ int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
         ctx->discard_text = (int)value;
         return NTC_OK;
     }
+    if (std::strcmp(key, "paired") == 0) {  // paired-end reads: 0 off, 1 pairs + mate check, 2 pairs (ntcomp_codec.h)
+        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "paired must be 0 (off), 1 (ids) or 2 (no check)");
+        ctx->paired = (int)value;
+        return NTC_OK;
+    }
     if (std::strcmp(key, "digests") == 0) {  // per-block content digests: 0 off, 1 on (ntcomp_codec.h)
         if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "digests must be 0 or 1");
         ctx->dg_opt = (int)value;
@@ -1921,6 +1933,7 @@ int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     else if (std::strcmp(key, "names") == 0) *value = ctx->n_mode;
     else if (std::strcmp(key, "digests") == 0) *value = ctx->dg_opt;
     else if (std::strcmp(key, "discard_text") == 0) *value = ctx->discard_text;
+    else if (std::strcmp(key, "paired") == 0) *value = ctx->paired;
     else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
     else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
     else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
@@ -2378,8 +2391,56 @@ namespace {
 // FASTQ text -> bases (WS_STAGE_BASES) + read offsets (WS_STAGE_OFFS, room for the record
 // offsets behind them) in HBM, parsed on the device (fastq.hip); synchronous, so the
 // structure checks are answered before anything is encoded.  *total = bases kept.
+//
+// Pairs (option "paired", pairs.hip): with pair given, the text is woven on the device from the
+// two mate texts (bytes = the woven size, fastq unused); with mate_check the names of reads 2p
+// and 2p + 1 are compared after the parse.  Both verdicts arrive with the parse's own, at the
+// one sync below.
+struct PairSrc {
+    const uint8_t *text[2];
+    uint64_t bytes[2];
+};
+
+int pair_weave(ntc_ctx *ctx, const PairSrc &src, uint64_t n_pairs, uint8_t *d_raw, uint64_t woven, uint64_t *tmp,
+               unsigned long long *status) {
+    if (n_pairs == 0) return NTC_OK;
+    const uint64_t at1 = (src.bytes[0] + 63) & ~63ull;  // (the line passes load 16 bytes at a time)
+    const uint64_t tiles[2] = {fastq_tiles(src.bytes[0]), fastq_tiles(src.bytes[1])};
+    void *in, *tab;
+    int rc;
+    if ((rc = ensure(ctx, WS_PAIR_IN, at1 + src.bytes[1] + 64, &in))) return rc;
+    const uint64_t words = (tiles[0] + 1) + (tiles[1] + 1) + (n_pairs + 1);
+    if ((rc = ensure(ctx, WS_PAIR_TAB, words * 8 + (tiles[0] + tiles[1] + 8 * n_pairs + n_pairs + 1) * 4 + 8, &tab)))
+        return rc;
+    PairWeaveArgs a{};
+    uint64_t *w = (uint64_t *)tab;
+    uint64_t *tile_base[2] = {w, w + tiles[0] + 1};
+    a.offs = w + (tiles[0] + 1) + (tiles[1] + 1);
+    uint32_t *h = (uint32_t *)(w + words);
+    uint32_t *tile_cnt[2] = {h, h + tiles[0]};
+    uint32_t *nl[2] = {h + tiles[0] + tiles[1], h + tiles[0] + tiles[1] + 4 * n_pairs};
+    a.sizes = nl[1] + 4 * n_pairs;
+    for (int t = 0; t < 2; t++) {
+        uint8_t *d = (uint8_t *)in + (t ? at1 : 0);
+        if (src.bytes[t]) HIP_TRY(ctx, hipMemcpyAsync(d, src.text[t], src.bytes[t], hipMemcpyHostToDevice, ctx->stream));
+        launch_fastq_lines(d, src.bytes[t], tile_cnt[t], tile_base[t], nl[t], 4 * n_pairs, tmp, ctx->stream);
+        a.raw[t] = d;
+        a.n_raw[t] = src.bytes[t];
+        a.nl[t] = nl[t];
+        a.n_nl_p[t] = tile_base[t] + tiles[t];
+    }
+    a.n_pairs = n_pairs;
+    a.tmp = tmp;
+    a.out = d_raw;
+    a.out_bytes = woven;
+    a.status = status;
+    launch_pair_weave(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+
 int fastq_stage(ntc_ctx *ctx, const uint8_t *fastq, uint64_t bytes, uint64_t n_reads, void **d_bases, void **d_offs,
-                uint64_t *total, int64_t *bad_read) {
+                uint64_t *total, int64_t *bad_read, const PairSrc *pair = nullptr, bool mate_check = false) {
     if (bad_read) *bad_read = -1;
     *total = 0;
     // The parse reuses d_status and the mailbox: whatever an earlier encode or decode
@@ -2411,20 +2472,61 @@ int fastq_stage(ntc_ctx *ctx, const uint8_t *fastq, uint64_t bytes, uint64_t n_r
     a.tmp = (uint64_t *)tmp;
     a.bases = (uint8_t *)*d_bases;
     a.status = ctx->d_status;
+    unsigned long long *pst = nullptr;  // the weave's status word and the mate check's
+    if (pair || mate_check) {
+        void *p;
+        if ((rc = ensure(ctx, WS_PAIR_ST, 64, &p))) return rc;
+        pst = (unsigned long long *)p;
+        HIP_TRY(ctx, hipMemsetAsync(pst, 0xFF, 16, ctx->stream));
+        ctx->h_box[10] = ctx->h_box[11] = ~0ull;  // (no kernel of an earlier call writes them: each ends synchronised)
+    }
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
-    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(raw, fastq, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (pair) {
+        if ((rc = pair_weave(ctx, *pair, n_reads / 2, (uint8_t *)raw, bytes, (uint64_t *)tmp, pst))) return rc;
+    } else if (bytes) {
+        HIP_TRY(ctx, hipMemcpyAsync(raw, fastq, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
     ctx->fq_last = a;
     launch_fastq_parse(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
+    if (pst) {
+        if (mate_check) {
+            PairCheckArgs c{};
+            c.raw = a.raw;
+            c.nl = a.nl;
+            c.n_pairs = n_reads / 2;
+            c.parse_status = ctx->d_status;
+            c.status = pst + 1;
+            launch_pair_check(c, ctx->stream);
+        }
+        launch_pair_box(pst, pst + 1, ctx->h_box, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     launch_status_box(ctx->d_status, a.offs + n_reads, nullptr, nullptr, ctx->h_box, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (pst && ((volatile uint64_t *)ctx->h_box)[10] != ~0ULL) {  // (the parse then saw a text nobody wrote)
+        const uint64_t w = ((volatile uint64_t *)ctx->h_box)[10];
+        if (bad_read) *bad_read = (int64_t)(w >> 8);
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "mate texts hold different record counts: read %lld has no whole record",
+                      (long long)(w >> 8));
+        return set_err(ctx, (int)(w & 0xFF), buf);
+    }
     const uint64_t st = ((volatile uint64_t *)ctx->h_box)[0];
     if (st != ~0ULL) {
         if (bad_read) *bad_read = (int64_t)(st >> 8);
         char buf[160];
         std::snprintf(buf, sizeof(buf), "malformed FASTQ record at index %lld", (long long)(st >> 8));
         return set_err(ctx, (int)(st & 0xFF), buf);
+    }
+    if (pst && ((volatile uint64_t *)ctx->h_box)[11] != ~0ULL) {
+        const uint64_t c = ((volatile uint64_t *)ctx->h_box)[11];
+        if (bad_read) *bad_read = (int64_t)(c >> 8);
+        char buf[160];
+        std::snprintf(buf, sizeof(buf), "the names of the mates disagree at pair %lld (reads %lld and %lld)",
+                      (long long)(c >> 9), (long long)(c >> 8), (long long)(c >> 8) + 1);
+        return set_err(ctx, (int)(c & 0xFF), buf);
     }
     *total = ((volatile uint64_t *)ctx->h_box)[1];
     return NTC_OK;
@@ -2450,21 +2552,32 @@ int ntc_fastq_parse(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_bytes, ui
     return NTC_OK;
 }
 
-int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_bytes, uint64_t n_reads,
-                          uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
-                          uint64_t *n_bases, int64_t *bad_read) {
-    if (bad_read) *bad_read = -1;
-    if (!ctx || (fastq_bytes && !fastq) || !meta || !payload || !payload_bytes || block_reads == 0)
-        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument or block_reads = 0");
+}  // extern "C"
+
+namespace {
+// ntc_encode_pack_fastq, and ntc_encode_pack_fastq_paired (pair: the two texts to weave into
+// the text of fastq_bytes bytes first)
+int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_bytes, uint64_t n_reads,
+                           uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
+                           uint64_t *n_bases, int64_t *bad_read, const PairSrc *pair) {
     *payload = nullptr;
     *payload_bytes = 0;
     if (n_bases) *n_bases = 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
+    if (ctx->paired && ((n_reads & 1) || (block_reads & 1)))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "paired: n_reads and block_reads must be even");
     void *d_bases, *d_offs;
     uint64_t total = 0;
-    int rc = fastq_stage(ctx, fastq, fastq_bytes, n_reads, &d_bases, &d_offs, &total, bad_read);
+    int rc = fastq_stage(ctx, fastq, fastq_bytes, n_reads, &d_bases, &d_offs, &total, bad_read, pair,
+                         ctx->paired == kPairIds);
+    if (rc && ctx->paired) {  // a failed call leaves no sections
+        nx_begin(ctx);
+        q_begin(ctx);
+        n_begin(ctx);
+        dg_begin(ctx);
+    }
     if (rc) return rc;
     if (n_bases) *n_bases = total;
     nx_begin(ctx);
@@ -2514,6 +2627,45 @@ int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_byt
     }
     return src ? src : rc;
 }
+}  // namespace
+
+extern "C" {
+
+int ntc_encode_pack_fastq(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_bytes, uint64_t n_reads,
+                          uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
+                          uint64_t *n_bases, int64_t *bad_read) {
+    if (bad_read) *bad_read = -1;
+    if (!ctx || (fastq_bytes && !fastq) || !meta || !payload || !payload_bytes || block_reads == 0)
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument or block_reads = 0");
+    return encode_pack_fastq_impl(ctx, fastq, fastq_bytes, n_reads, block_reads, meta, payload, payload_bytes, n_bases,
+                                  bad_read, nullptr);
+}
+
+int ntc_encode_pack_fastq_paired(ntc_ctx *ctx, const uint8_t *fastq1, uint64_t bytes1, const uint8_t *fastq2,
+                                 uint64_t bytes2, uint64_t n_pairs, uint32_t block_reads, ntc_block_meta *meta,
+                                 uint8_t **payload, uint64_t *payload_bytes, uint64_t *n_bases, int64_t *bad_read) {
+    if (bad_read) *bad_read = -1;
+    if (!ctx || (bytes1 && !fastq1) || (bytes2 && !fastq2) || !meta || !payload || !payload_bytes || block_reads == 0)
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument or block_reads = 0");
+    *payload = nullptr;
+    *payload_bytes = 0;
+    if (n_bases) *n_bases = 0;
+    if (!ctx->paired) return set_err(ctx, NTC_ERR_INVALID_ARG, "ntc_encode_pack_fastq_paired needs the option paired 1 or 2");
+    nx_begin(ctx);  // a failed call leaves no sections
+    q_begin(ctx);
+    n_begin(ctx);
+    dg_begin(ctx);
+    // (the weave may add a newline to each text)
+    if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32) || bytes1 + bytes2 + 2 >= (1ull << 32))
+        return set_err(ctx, NTC_ERR_CAPACITY, "mate texts of 4 GiB or more together: split the batch");
+    // a record is four lines: a count no text under 4 GiB can hold fails before it sizes a table
+    if (n_pairs > (1ull << 30) || (n_pairs == 0 && (bytes1 || bytes2)))
+        return set_err(ctx, NTC_ERR_FORMAT, "mate texts hold different record counts: text given for zero pairs, or too many pairs");
+    const PairSrc src{{fastq1, fastq2}, {bytes1, bytes2}};
+    const uint64_t woven = bytes1 + bytes2 + (bytes1 && fastq1[bytes1 - 1] != '\n') + (bytes2 && fastq2[bytes2 - 1] != '\n');
+    return encode_pack_fastq_impl(ctx, nullptr, woven, 2 * n_pairs, block_reads, meta, payload, payload_bytes, n_bases,
+                                  bad_read, &src);
+}
 
 }  // extern "C"
 
@@ -2548,6 +2700,13 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if ((rc = ensure(ctx, WS_FA_OFFS, (n_reads + 2) * 8, &d_offs))) return rc;
     if ((rc = ensure(ctx, WS_FA_SCAN, (2 * (n_reads + 1) + scan_tmp_words(n_reads + 1)) * 8, &d_scan))) return rc;
     if ((rc = ensure(ctx, WS_STAGE_BASES, need + 64, &d_out))) return rc;
+    // pairs: the formatted text is split into its two parts on the device before the copy
+    const bool split = ctx->paired && !ctx->discard_text && n_reads;
+    void *d_pscan = nullptr, *d_split = nullptr;
+    if (split) {
+        if ((rc = ensure(ctx, WS_PAIR_SCAN, 4 * (n_reads / 2 + 1) * 8, &d_pscan))) return rc;
+        if ((rc = ensure(ctx, WS_PAIR_OUT, need + 64, &d_split))) return rc;
+    }
     std::vector<ntc_nx_run> nx;
     uint32_t nx_sub = 0;
     std::vector<ntc_qual_meta> qm;
@@ -2623,6 +2782,23 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
         launch_fasta((const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status, sizes,
                      out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
+    if (split) {
+        PairSplitArgs p{};
+        p.text = (const uint8_t *)d_out;
+        p.out_offs = out_offs;
+        p.n_pairs = n_reads / 2;
+        p.cap = need;
+        p.s1 = (uint64_t *)d_pscan;
+        p.s2 = p.s1 + (p.n_pairs + 1);
+        p.o1 = p.s2 + (p.n_pairs + 1);
+        p.o2 = p.o1 + (p.n_pairs + 1);
+        p.tmp = tmp;  // (the formatter's scan is done with it)
+        p.out = (uint8_t *)d_split;
+        p.box = ctx->h_box;
+        launch_pair_split(p, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+        d_out = d_split;
+    }
     if (!ctx->discard_text) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, ctx->stream));
     uint64_t nr = 0, nb = 0;
     rc = ntc_decode_status(ctx, &nr, &nb);  // synchronises
@@ -2630,6 +2806,7 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if (rc) return rc;
     if (nr != n_reads || nb != n_bases)
         return set_err(ctx, NTC_ERR_FORMAT, "records hold other read / base counts than given");
+    if (split) ctx->pair_first = ((volatile uint64_t *)ctx->h_box)[12];
     return NTC_OK;
 }
 }  // namespace
@@ -2667,11 +2844,15 @@ int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
+    ctx->pair_valid = false;
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
+    if (ctx->paired && (n_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, n_reads, n_bases, first_id);
     *out_len = need;
     if (need > out_capacity && !ctx->discard_text)
         return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+    ctx->pair_valid = ctx->paired && !ctx->discard_text;  // (the parts stay empty unless the call succeeds)
+    ctx->pair_first = 0;
     if (n_recs == 0) return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     void *d_recs;
     int rc;
@@ -2806,15 +2987,27 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     if (!ctx || !out_len) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
+    ctx->pair_valid = false;
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
+    if (ctx->paired && (ctx->unp_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, ctx->unp_reads, ctx->unp_bases, first_id);
     *out_len = need;  // (a size query: out_capacity 0)
     if (!ctx->discard_text) {
         if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
         if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     }
+    ctx->pair_valid = ctx->paired && !ctx->discard_text;
+    ctx->pair_first = 0;
     if (ctx->unp_recs == 0) return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     return decode_fasta_dev(ctx, ctx->unp_d_recs, ctx->unp_recs, ctx->unp_reads, ctx->unp_bases, first_id, out, need);
+}
+
+int ntc_decode_pair_split(ntc_ctx *ctx, uint64_t *first_bytes) {
+    if (!ctx || !first_bytes) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *first_bytes = 0;
+    if (!ctx->pair_valid) return set_err(ctx, NTC_ERR_INVALID_ARG, "the last text decode of this context was not a paired one");
+    *first_bytes = ctx->pair_first;
+    return NTC_OK;
 }
 
 int ntc_encode_exceptions(ntc_ctx *ctx, ntc_nx_run *out, uint64_t capacity, uint64_t *n_runs) {
@@ -3244,6 +3437,9 @@ struct NxHookFill {
         };
         ntc::g_nx_hooks.encode_exceptions = ntc_encode_exceptions;
         ntc::g_nx_hooks.decode_set_exceptions = ntc_decode_set_exceptions;
+        ntc::g_p_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "paired", mode); };
+        ntc::g_p_hooks.encode_paired = ntc_encode_pack_fastq_paired;
+        ntc::g_p_hooks.pair_split = ntc_decode_pair_split;
         ntc::g_q_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "qualities", mode); };
         ntc::g_q_hooks.encode_qualities = ntc_encode_qualities;
         ntc::g_q_hooks.get_coder = [](ntc_ctx *ctx) {

@@ -205,16 +205,22 @@ __global__ __launch_bounds__(kFqThreads) void k_fq_norm(const uint8_t *raw, uint
 
 uint64_t fastq_tiles(uint64_t n_raw) { return (n_raw + kFqTile - 1) / kFqTile; }
 
+void launch_fastq_lines(const uint8_t *raw, uint64_t n_raw, uint32_t *tile_cnt, uint64_t *tile_base, uint32_t *nl,
+                        uint64_t nl_cap, uint64_t *tmp, hipStream_t s) {
+    const uint64_t tiles = fastq_tiles(n_raw);
+    if (tiles == 0) {
+        (void)hipMemsetAsync(tile_base, 0, 8, s);
+        return;
+    }
+    hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)tiles), dim3(kFqThreads), 0, s, raw, n_raw, tile_cnt);
+    scan_excl_u32(tile_cnt, tiles, tile_base, tmp, s);
+    hipLaunchKernelGGL(k_fq_lines, dim3((uint32_t)tiles), dim3(kFqThreads), 0, s, raw, n_raw,
+                       (const uint64_t *)tile_base, nl, nl_cap);
+}
+
 void launch_fastq_parse(const FastqArgs &a, hipStream_t s) {
     const uint64_t tiles = fastq_tiles(a.n_raw);
-    if (tiles == 0) {
-        (void)hipMemsetAsync(a.tile_base, 0, 8, s);
-    } else {
-        hipLaunchKernelGGL(k_fq_count, dim3((uint32_t)tiles), dim3(kFqThreads), 0, s, a.raw, a.n_raw, a.tile_cnt);
-        scan_excl_u32(a.tile_cnt, tiles, a.tile_base, a.tmp, s);
-        hipLaunchKernelGGL(k_fq_lines, dim3((uint32_t)tiles), dim3(kFqThreads), 0, s, a.raw, a.n_raw,
-                           (const uint64_t *)a.tile_base, a.nl, 4 * a.n_reads);
-    }
+    launch_fastq_lines(a.raw, a.n_raw, a.tile_cnt, a.tile_base, a.nl, 4 * a.n_reads, a.tmp, s);
     if (a.n_reads == 0) {
         (void)hipMemsetAsync(a.offs, 0, 8, s);
         return;

@@ -221,6 +221,58 @@ struct FastqArgs {
 };
 uint64_t fastq_tiles(uint64_t n_raw);
 void launch_fastq_parse(const FastqArgs &a, hipStream_t s);
+// its first two passes alone: the positions of the first nl_cap newlines of raw, in order, and
+// tile_base[fastq_tiles(n_raw)] = the newlines found (tile_cnt, tile_base, tmp as above)
+void launch_fastq_lines(const uint8_t *raw, uint64_t n_raw, uint32_t *tile_cnt, uint64_t *tile_base, uint32_t *nl,
+                        uint64_t nl_cap, uint64_t *tmp, hipStream_t s);
+
+// Paired-end reads (pairs.hip, pair_core.h).  The weave: two FASTQ texts of n_pairs records
+// each (raw[t] 16-byte aligned, nl[t] / n_nl_p[t] from launch_fastq_lines with nl_cap = 4
+// n_pairs) -> out, record p of text 1 then record p of text 2, a newline added after a last
+// line that lacks one; out_bytes = the woven size (the host knows it: both texts and the
+// newlines added).  sizes: n_pairs + 1 words, offs: n_pairs + 1, tmp: scan_tmp_words(n_pairs).
+// status: the weave's own word (preset here), read << 8 | NTC_ERR_FORMAT when a text does not
+// hold exactly 4 n_pairs lines; then nothing is woven.
+struct PairWeaveArgs {
+    const uint8_t *raw[2];
+    uint64_t n_raw[2];
+    const uint32_t *nl[2];
+    const uint64_t *n_nl_p[2];
+    uint64_t n_pairs;
+    uint32_t *sizes;
+    uint64_t *offs;
+    uint64_t *tmp;
+    uint8_t *out;
+    uint64_t out_bytes;
+    unsigned long long *status;
+};
+void launch_pair_weave(const PairWeaveArgs &a, hipStream_t s);
+// The mate check, after launch_fastq_parse over the interleaved text (its raw, nl and status):
+// status, a word of the check's own (preset here), gets (2 p) << 8 | NTC_ERR_FORMAT for the
+// lowest pair p whose names disagree.  Nothing is looked at when the parse failed.
+struct PairCheckArgs {
+    const uint8_t *raw;
+    const uint32_t *nl;
+    uint64_t n_pairs;
+    const unsigned long long *parse_status;
+    unsigned long long *status;
+};
+void launch_pair_check(const PairCheckArgs &a, hipStream_t s);
+// box[10] = the weave's status, box[11] = the check's
+void launch_pair_box(const unsigned long long *weave, const unsigned long long *check, uint64_t *box, hipStream_t s);
+// The split, after a formatter (launch_fasta, launch_fastq_text, launch_named_text) left text
+// and out_offs[2 n_pairs + 1]: all even reads' records in order, then all odd reads', into out
+// (cap bytes); box[12] = the bytes of the first part.  s1, s2, o1, o2: n_pairs + 1 words each,
+// tmp: scan_tmp_words(n_pairs).  Writes nothing when the formatter wrote nothing.
+struct PairSplitArgs {
+    const uint8_t *text;
+    const uint64_t *out_offs;
+    uint64_t n_pairs, cap;
+    uint64_t *s1, *s2, *o1, *o2, *tmp;
+    uint8_t *out;
+    uint64_t *box;
+};
+void launch_pair_split(const PairSplitArgs &a, hipStream_t s);
 
 // Non-ACGT symbols (nonacgt.hip, nonacgt_core.h).  Encode side, over staged (writable)
 // bases: M / S / E bitmaps of nx_words(total) words each, cnt_s / cnt_e as many u32, soff /

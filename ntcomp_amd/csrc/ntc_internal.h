@@ -163,6 +163,16 @@ struct DHooks {
     int (*set_discard)(::ntc_ctx *ctx, int on);  // ctx option "discard_text"
 };
 extern DHooks g_d_hooks;
+// ... and for paired-end reads: with the table null, ntc_encode_file_ex4 / ntc_decode_file_ex4
+// answer NTC_ERR_UNSUPPORTED to pair_mode 1 and 2.
+struct PHooks {
+    int (*set_mode)(::ntc_ctx *ctx, int mode);  // ctx option "paired"
+    int (*encode_paired)(::ntc_ctx *ctx, const uint8_t *fastq1, uint64_t bytes1, const uint8_t *fastq2, uint64_t bytes2,
+                         uint64_t n_pairs, uint32_t block_reads, ::ntc_block_meta *meta, uint8_t **payload,
+                         uint64_t *payload_bytes, uint64_t *n_bases, int64_t *bad_read);  // ntc_encode_pack_fastq_paired
+    int (*pair_split)(::ntc_ctx *ctx, uint64_t *first_bytes);  // ntc_decode_pair_split
+};
+extern PHooks g_p_hooks;
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

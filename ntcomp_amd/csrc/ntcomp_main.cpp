@@ -10,12 +10,16 @@
 //                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
 //                 [--non-acgt error|mask|keep] [--exceptions PATH]
 //                 [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]
-//                 [--names drop|keep|id] [--name-file PATH] [--digest-file PATH] FILE > encoded.dat
+//                 [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]
+//                 [--mate-file R2 | --interleaved] [--mate-check ids|off] FILE > encoded.dat
+//                 (paired-end reads: FILE holds the mate-1 records and R2 the mate-2 records, or FILE
+//                 is interleaved; the archive alternates the mates, whose ids are checked on the GPU)
 //   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
 //                 [--exceptions PATH] [--quality-file PATH] [--name-file PATH] [--digest-file PATH]
-//                 FILE > out.fasta
+//                 [--mate-out R2.out] FILE > out.fasta
 //                 (FASTQ with --quality-file, the reads' own names with --name-file; checked block by
-//                 block against the --digest-file)
+//                 block against the --digest-file; with --mate-out the archive holds pairs: the mate-1
+//                 records go to stdout, the mate-2 records to R2.out)
 //   ntcomp verify -i P --digest-file PATH [--exceptions PATH] [--quality-file PATH] [--name-file PATH]
 //                 FILE        (decode without the text: one line on stdout, status 0 iff every block matched)
 #include <dlfcn.h>
@@ -78,14 +82,14 @@ bool takes_value(const std::string &o) {
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
                               "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
                               "--qualities", "--quality-file", "--quality-coder", "--names", "--name-file",
-                              "--digest-file"};
+                              "--digest-file", "--mate-file", "--mate-check", "--mate-out"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
 }
 
 bool is_switch(const std::string &o) {
-    static const char *v[] = {"-d", "--dedup-batches", "--verbose", "--stats", "--host-parse"};
+    static const char *v[] = {"-d", "--dedup-batches", "--verbose", "--stats", "--host-parse", "--interleaved"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -278,6 +282,15 @@ int cmd_encode(const Args &a) {
     if (n_mode == 0 && a.flag("--name-file")) bad_args("encode: --name-file is only written under --names keep or id");
     // per-block content digests of everything this call encodes, for decode / verify --digest-file
     const std::string d_path = digest_path_of(a, "encode", {nx_path, q_path, n_path, a.pos[0]});
+    // paired-end reads: the mate-2 file beside the input, or an interleaved input; the mates' ids are checked
+    const std::string mate_path = a.get("--mate-file", nullptr, ""), check_name = a.get("--mate-check", nullptr, "ids");
+    if (a.flag("--mate-file") && a.flag("--interleaved")) bad_args("encode: --mate-file and --interleaved exclude each other");
+    if (a.flag("--mate-file") && mate_path.empty()) bad_args("encode: --mate-file needs a path");
+    const bool pairs = a.flag("--mate-file") || a.flag("--interleaved");
+    if (a.flag("--mate-check") && !pairs) bad_args("encode: --mate-check needs --mate-file or --interleaved");
+    if (check_name != "ids" && check_name != "off") bad_args("encode: --mate-check: ids or off");
+    if (pairs && a.flag("--host-parse")) bad_args("encode: pairs are woven and checked on the GPU: not with --host-parse");
+    const int pair_mode = !pairs ? 0 : check_name == "ids" ? 1 : 2;
     if (prefix.empty()) die("encode: -i/--index is required");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
@@ -321,8 +334,12 @@ int cmd_encode(const Args &a) {
     const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd, nullptr};
     const ntc_file_opts3 fo3{(uint32_t)sizeof(ntc_file_opts3), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd,
                              nullptr, 1, d_fd, nullptr};
+    const ntc_file_opts4 fo4{(uint32_t)sizeof(ntc_file_opts4), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd,
+                             nullptr, d_fd >= 0 ? 1 : 0, d_fd, nullptr, pair_mode, mate_path.empty() ? nullptr : mate_path.c_str(), -1};
+    ntc_p_stats pst{};
     std::fflush(stdout);
-    const int rc = d_fd >= 0 ? ntc_encode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo3, &o, &st, &nx, &qs, &ns, &dst)
+    const int rc = pair_mode ? ntc_encode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &nx, &qs, &ns, &dst, &pst)
+                   : d_fd >= 0 ? ntc_encode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo3, &o, &st, &nx, &qs, &ns, &dst)
                    : n_mode > 0 ? ntc_encode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st, &nx, &qs, &ns)
                    : q_mode > 0 ? ntc_encode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st, &nx, &qs)
                    : policy == NTC_NX_ERROR
@@ -332,7 +349,7 @@ int cmd_encode(const Args &a) {
     if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
     if (n_fd >= 0 && ::close(n_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + n_path);
     if (d_fd >= 0 && ::close(d_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + d_path);
-    char qjson[960] = "";  // the quality and name files' figures, when they were written
+    char qjson[1280] = "";  // the quality and name files' figures, when they were written
     if (q_mode > 0)
         std::snprintf(qjson, 320, "\"qualities\": \"%s\", \"quality_coder\": \"%s\", \"q_sections\": %llu, "
                                   "\"q_quals\": %llu, \"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
@@ -350,6 +367,11 @@ int cmd_encode(const Args &a) {
                                                        "\"d_blocks_qual\": %llu, \"d_blocks_name\": %llu, ",
                       (unsigned long long)dst.sections, (unsigned long long)dst.blocks_seq, (unsigned long long)dst.blocks_sym,
                       (unsigned long long)dst.blocks_qual, (unsigned long long)dst.blocks_name);
+    if (pair_mode)
+        std::snprintf(qjson + std::strlen(qjson), 250, "\"pairs\": %llu, \"mate_check\": \"%s\", \"mate1_bytes\": %llu, "
+                                                       "\"mate2_bytes\": %llu, ",
+                      (unsigned long long)pst.pairs, check_name.c_str(), (unsigned long long)pst.bytes1,
+                      (unsigned long long)pst.bytes2);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -392,6 +414,10 @@ int cmd_decode(const Args &a, bool verify = false) {
     const std::string d_path = digest_path_of(a, cmd, {a.get("--exceptions", nullptr, ""), a.get("--quality-file", nullptr, ""),
                                                        a.get("--name-file", nullptr, ""), a.pos[0]});
     if (verify && d_path.empty()) bad_args("verify: --digest-file PATH is required");
+    // a paired archive: the mate-1 records to stdout, the mate-2 records to --mate-out
+    const std::string mate_out = a.get("--mate-out", nullptr, "");
+    if (verify && a.flag("--mate-out")) bad_args("verify: writes no text: not with --mate-out");
+    if (a.flag("--mate-out") && mate_out.empty()) bad_args("decode: --mate-out needs a path");
     if (prefix.empty()) die(std::string(cmd) + ": -i/--index is required");
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
@@ -412,13 +438,21 @@ int cmd_decode(const Args &a, bool verify = false) {
     const ntc_file_opts3 fo3{(uint32_t)sizeof(ntc_file_opts3), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1,
                              n_path.empty() ? nullptr : n_path.c_str(), 0, -1, d_path.c_str()};
     ntc_d_stats dst{};
+    int fd2 = -1;
+    if (!mate_out.empty() && (fd2 = ::open(mate_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
+        die("decode: cannot write " + mate_out);
+    const ntc_file_opts4 fo4{(uint32_t)sizeof(ntc_file_opts4), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1, fo3.n_path, 0, -1,
+                             d_path.empty() ? nullptr : d_path.c_str(), 2, nullptr, fd2};
+    ntc_p_stats pst{};
     std::fflush(stdout);
-    const int rc = !d_path.empty() ? ntc_decode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo3, &o, &st, &dst)
+    const int rc = fd2 >= 0 ? ntc_decode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &dst, &pst)
+                   : !d_path.empty() ? ntc_decode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo3, &o, &st, &dst)
                    : !n_path.empty() ? ntc_decode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st)
                    : !q_path.empty() ? ntc_decode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st)
                    : nx_path.empty()
                        ? ntc_decode_file(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &o, &st)
                        : ntc_decode_file_nx(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), nx_path.c_str(), 1, &o, &st);
+    if (fd2 >= 0 && ::close(fd2) != 0 && rc == NTC_OK) die("decode: cannot write " + mate_out);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -432,9 +466,12 @@ int cmd_decode(const Args &a, bool verify = false) {
                     component_names((dst.blocks_seq ? 1u : 0) | (dst.blocks_sym ? 2u : 0) | (dst.blocks_qual ? 4u : 0) |
                                     (dst.blocks_name ? 8u : 0)).c_str(),
                     component_names(dst.not_checkable).c_str());
-    char djson[320] = "";
+    char djson[560] = "";
+    if (fd2 >= 0)
+        std::snprintf(djson, 240, "\"pairs\": %llu, \"mate1_bytes\": %llu, \"mate2_bytes\": %llu, ",
+                      (unsigned long long)pst.pairs, (unsigned long long)pst.bytes1, (unsigned long long)pst.bytes2);
     if (!d_path.empty())
-        std::snprintf(djson, sizeof(djson), "\"d_sections\": %llu, \"d_blocks_seq\": %llu, \"d_blocks_sym\": %llu, "
+        std::snprintf(djson + std::strlen(djson), 320, "\"d_sections\": %llu, \"d_blocks_seq\": %llu, \"d_blocks_sym\": %llu, "
                                             "\"d_blocks_qual\": %llu, \"d_blocks_name\": %llu, \"d_not_checkable\": \"%s\", ",
                       (unsigned long long)dst.sections, (unsigned long long)dst.blocks_seq, (unsigned long long)dst.blocks_sym,
                       (unsigned long long)dst.blocks_qual, (unsigned long long)dst.blocks_name,
@@ -555,8 +592,9 @@ void usage(FILE *f) {
                  "                     [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]\n"
                  "                     [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]\n"
                  "                     FILE > encoded.dat\n"
+                 "                     [--mate-file R2 | --interleaved] [--mate-check ids|off]\n"
                  "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH]\n"
-                 "                     [--digest-file PATH] FILE > out.fasta\n"
+                 "                     [--digest-file PATH] [--mate-out R2.out] FILE > out.fasta\n"
                  "       ntcomp verify -i PREFIX --digest-file PATH [--exceptions PATH] [--quality-file PATH]\n"
                  "                     [--name-file PATH] FILE\n\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
@@ -579,7 +617,13 @@ void usage(FILE *f) {
                  "  --digest-file PATH encode: also write per-block content digests, computed on the GPU; decode: check\n"
                  "                     every block against them while decoding -- another index, a damaged or truncated\n"
                  "                     file, a side file of another run end the call with an error that names the block\n"
-                 "                     and the component; verify: the same check without writing the text\n");
+                 "                     and the component; verify: the same check without writing the text\n"
+                 "  --mate-file R2     encode: paired-end reads, FILE holds the mate-1 records and R2 the mate-2 records\n"
+                 "                     (any supported compression each); the GPU weaves them, read 2p and 2p+1 are a pair\n"
+                 "  --interleaved      encode: FILE already alternates the mates\n"
+                 "  --mate-check ids|off  encode: compare the mates' ids (cut at the first blank, /1 and /2 stripped)\n"
+                 "                     on the GPU (default), or not\n"
+                 "  --mate-out R2.out  decode: the archive holds pairs: mate-1 records to stdout, mate-2 records to R2.out\n");
 }
 
 }  // namespace

@@ -53,6 +53,7 @@ NxHooks g_nx_hooks = {nullptr, nullptr, nullptr, nullptr};  // capi.cpp fills it
 QHooks g_q_hooks = {nullptr, nullptr, nullptr, nullptr};
 NHooks g_n_hooks = {nullptr, nullptr, nullptr};
 DHooks g_d_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+PHooks g_p_hooks = {nullptr, nullptr, nullptr};
 }
 
 namespace {
@@ -139,6 +140,8 @@ struct Batch {  // one pinned buffer of the ring
     uint8_t *text = nullptr;  // plain FASTQ text for the GPU parse (text_len bytes, n_process records)
     uint64_t text_cap = 0, text_len = 0;
     bool is_text = false;
+    bool is_pair = false;    // two mate texts: text_len bytes at text, text2_len bytes at text + text2_off
+    uint64_t text2_off = 0, text2_len = 0;
     uint64_t n_reads = 0;    // reads in the buffer (carry + new)
     uint64_t n_process = 0;  // reads handed to the GPU (whole blocks, or all at the end)
     uint64_t first_read = 0; // file index of the buffer's first read
@@ -251,10 +254,17 @@ extern "C" {
 static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, int policy, int nx_fd,
                             const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx,
                             int q_mode = 0, int q_fd = -1, ntc_q_stats *qs = nullptr, int n_mode = 0, int n_fd = -1,
-                            ntc_n_stats *ns = nullptr, int d_mode = 0, int d_fd = -1, ntc_d_stats *ds = nullptr) {
+                            ntc_n_stats *ns = nullptr, int d_mode = 0, int d_fd = -1, ntc_d_stats *ds = nullptr,
+                            int pair_mode = 0, const char *mate_path = nullptr, ntc_p_stats *ps = nullptr) {
     if (!ctxs || n_ctx <= 0 || !in_path || out_fd < 0) return NTC_ERR_INVALID_ARG;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
+    // pair_mode / mate_path / ps: ntc_encode_file_ex4's pairs (pair_mode 0: none)
+    if (pair_mode < 0 || pair_mode > 2 || (!pair_mode && mate_path)) return NTC_ERR_INVALID_ARG;
+    const ntc::PHooks &ph = ntc::g_p_hooks;
+    if (pair_mode && (!ph.set_mode || !ph.encode_paired)) return NTC_ERR_UNSUPPORTED;
+    ntc_p_stats PS{};
+    PS.mode = (uint32_t)pair_mode;
     if (q_mode < 0 || q_mode > 2 || (q_mode ? q_fd < 0 : q_fd != -1)) return NTC_ERR_INVALID_ARG;
     const ntc::QHooks &qh = ntc::g_q_hooks;
     if (q_mode && (!qh.set_mode || !qh.encode_qualities)) return NTC_ERR_UNSUPPORTED;
@@ -346,6 +356,19 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             for (int i = 0; i < n; i++) ntc::g_d_hooks.set_mode(ctxs[i], 0);
         }
     } digests_reset{ctxs, d_mode ? n_ctx : 0};
+    if (pair_mode)
+        for (int i = 0; i < n_ctx; i++)
+            if (int r = ph.set_mode(ctxs[i], pair_mode)) {
+                for (int j = 0; j < i; j++) ph.set_mode(ctxs[j], 0);
+                return r;
+            }
+    struct PairsReset {  // ... and with pairs off
+        ntc_ctx *const *ctxs;
+        int n;
+        ~PairsReset() {
+            for (int i = 0; i < n; i++) ntc::g_p_hooks.set_mode(ctxs[i], 0);
+        }
+    } pairs_reset{ctxs, pair_mode ? n_ctx : 0};
     // the components the file can hold: what the modes of this call yield
     const uint32_t d_components = ntc::kDgSeq | (keep ? ntc::kDgSym : 0) | (q_mode ? ntc::kDgQual : 0) |
                                   (n_mode ? ntc::kDgName : 0);
@@ -376,6 +399,16 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     // a mapped plain FASTQ goes to the GPU as text
     uint64_t text_n = 0;
     const uint8_t *text = o.host_parse ? nullptr : ntc::fastx_mapped(fx, &text_n);
+    // the mate-2 input goes through the same ingest; the two decoders share the thread budget
+    ntc_fastx *fx2 = nullptr;
+    if (mate_path) {
+        if ((rc = ntc_fastx_open(mate_path, &fx2))) {
+            ntc_fastx_close(fx);
+            return rc;
+        }
+        ntc_fastx_set_threads(fx, std::max(1, T / 2));
+        ntc_fastx_set_threads(fx2, std::max(1, T / 2));
+    }
 
     // pinned ring: the GPU threads hold at most n_ctx buffers, the reader fills one more.
     // A slot's base buffer (the large part, ~320 MB) is pinned by the reader when it first
@@ -389,6 +422,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         if (!(b.offs = (uint64_t *)pinned_alloc(b.cap_reads * 8))) {
             for (auto &x : ring) pinned_free(x.offs);
             ntc_fastx_close(fx);
+            if (fx2) ntc_fastx_close(fx2);
             return NTC_ERR_HIP;
         }
     }
@@ -447,6 +481,28 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         sh.fail(NTC_ERR_UNSUPPORTED, "names: host_parse = 1 parses on the host, which drops the header lines");
     else if (n_mode && !text && !streamed)
         sh.fail(NTC_ERR_UNSUPPORTED, "names: the input is not FASTQ (names are kept from FASTQ text only)");
+    // ... and so do pairs (DESIGN.md "Paired-end reads"): both inputs must reach the GPU as text
+    struct TextSrc {  // one FASTQ input of the pair reader
+        ntc_fastx *fx = nullptr;
+        const uint8_t *map = nullptr;  // mapped plain text; null: streamed from a decoder
+        uint64_t map_n = 0, pos = 0;   // mapped: the next record's start
+        std::vector<uint8_t> pend;     // streamed: decoded text not yet sent
+        bool at_end = false;           // streamed: the decoder has ended
+        uint64_t sent = 0;             // text bytes sent so far
+    } msrc[2];
+    if (pair_mode && o.host_parse) {
+        sh.fail(NTC_ERR_UNSUPPORTED, "pairs: host_parse = 1 parses on the host, which drops the header lines");
+    } else if (pair_mode && !text && !streamed) {
+        sh.fail(NTC_ERR_UNSUPPORTED, "pairs: the input is not FASTQ (mates are checked and woven in FASTQ text only)");
+    } else if (mate_path) {
+        msrc[0].fx = fx;
+        msrc[0].map = text;
+        msrc[0].map_n = text_n;
+        msrc[1].fx = fx2;
+        msrc[1].map = ntc::fastx_mapped(fx2, &msrc[1].map_n);
+        if (!msrc[1].map && !ntc::fastx_streamed_fastq(fx2))
+            sh.fail(NTC_ERR_UNSUPPORTED, "pairs: the mate input is not FASTQ (mates are checked and woven in FASTQ text only)");
+    }
     uint64_t text_pos = 0;
     const uint8_t *carry_p = nullptr;
     uint64_t carry_n = 0;
@@ -569,11 +625,129 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             return 1;
         }
     };
+    // The same for two mate inputs (mate_path): the next n records of each, the same n from
+    // both -- 2 n a multiple of 65,536, or the inputs' end -- into b's one pinned buffer at two
+    // offsets, for the GPU to weave.  The host newline counts make the cuts exact.  1 = filled,
+    // 0 = no input left, -1 = a text the GPU cannot take (as above), -2 = a decoder failed, -3 =
+    // one input ended while the other still holds a record
+    auto fill_pair = [&](ntc::Gang &gang, Batch &b, bool &eof) -> int {
+        const uint64_t kMaxHalf = ((1ull << 32) - (64u << 20)) / 2;  // both texts in one call of < 4 GiB
+        const uint64_t half = per_batch / 2;
+        constexpr uint64_t kPiece = 1u << 20;
+        struct Win {
+            const uint8_t *p = nullptr;
+            uint64_t len = 0, recs = 0, blank = UINT64_MAX, cut = 0;
+            bool end = false;
+            std::vector<FqScan> sc;
+        } w[2];
+        for (int s = 0; s < 2; s++) {
+            TextSrc &src = msrc[s];
+            uint64_t want = std::min(kMaxHalf, (uint64_t)((double)half * rec_bytes * 1.03) + (256u << 10));
+            for (;;) {
+                if (src.map) {
+                    w[s].p = src.map + src.pos;
+                    w[s].len = std::min(src.map_n - src.pos, want);
+                    w[s].end = src.pos + w[s].len == src.map_n;
+                } else {
+                    while (src.pend.size() < want && !src.at_end) {
+                        const uint64_t old = src.pend.size();
+                        src.pend.resize(want);
+                        bool io_err = false;
+                        const uint64_t got = ntc::fastx_stream_read(src.fx, src.pend.data() + old, want - old, &io_err);
+                        if (io_err) return -2;
+                        src.pend.resize(old + got);
+                        src.at_end = got < want - old;
+                    }
+                    w[s].p = src.pend.data();
+                    w[s].len = std::min<uint64_t>(src.pend.size(), want);
+                    w[s].end = src.at_end && w[s].len == src.pend.size();
+                }
+                Win &x = w[s];
+                x.recs = 0;
+                if (x.len == 0) break;
+                if (x.p[0] != '@') return -1;
+                const uint64_t np = (x.len + kPiece - 1) / kPiece;
+                x.sc.assign(np, FqScan{});
+                std::atomic<uint64_t> next{0};
+                gang.run([&](int) {
+                    for (uint64_t q; (q = next.fetch_add(1)) < np;) {
+                        const uint64_t a = q * kPiece, e = std::min(x.len, a + kPiece);
+                        x.sc[q] = fq_copy_scan<false>(x.p + a, nullptr, e - a);
+                    }
+                });
+                uint64_t nl = 0;
+                x.blank = UINT64_MAX;
+                for (uint64_t q = 0; q < np; q++) {
+                    const uint64_t a = q * kPiece;
+                    if (x.blank == UINT64_MAX && a && x.p[a - 1] == '\n' && (x.p[a] == '\n' || x.p[a] == '\r')) x.blank = a;
+                    if (x.blank == UINT64_MAX && x.sc[q].blank != SIZE_MAX) x.blank = a + x.sc[q].blank;
+                    nl += x.sc[q].nl;
+                }
+                const uint64_t lines = nl + (x.end && x.p[x.len - 1] != '\n');
+                if (x.end && lines % 4 != 0) return -1;  // records that are not four lines each
+                x.recs = x.end ? lines / 4 : nl / 4;
+                if (x.recs >= half || x.end) break;
+                if (want >= kMaxHalf) return -1;  // half of 4 GiB without half a batch
+                want = std::min(want * 2, kMaxHalf);
+            }
+        }
+        if (w[0].len == 0 && w[1].len == 0) return 0;
+        const bool last = w[0].end && w[1].end && w[0].recs == w[1].recs && w[0].recs <= half;
+        // an input that is not at its end holds at least half a batch here
+        for (int s = 0; s < 2; s++)
+            if (!last && w[s].end && w[s].recs < half && w[1 - s].recs > w[s].recs) return -3;
+        const uint64_t n = last ? w[0].recs : half;
+        for (int s = 0; s < 2; s++) {
+            Win &x = w[s];
+            x.cut = x.len;
+            if (!last && !(x.end && x.recs == n)) {  // the batch ends after newline 4 n: find the piece holding it
+                uint64_t before = 0, q = 0;
+                while (before + x.sc[q].nl < 4 * n) before += x.sc[q++].nl;
+                const uint64_t a = q * kPiece;
+                x.cut = a + nth_newline_end(x.p + a, std::min(x.len, a + kPiece) - a, 4 * n - before);
+            }
+            if (x.blank < x.cut) return -1;  // a blank line: only the host parser takes it
+        }
+        const uint64_t at2 = (w[0].cut + 63) & ~63ull, need = at2 + w[1].cut + 64;
+        if (b.text_cap < need) {
+            const auto ta = Clock::now();
+            uint8_t *nt = (uint8_t *)pinned_alloc(need + need / 8);
+            if (!nt) return -1;
+            pinned_free(b.text);
+            b.text = nt;
+            b.text_cap = need + need / 8;
+            t_pin = t_pin.load() + secs(ta, Clock::now());
+        }
+        {  // both texts into the pinned buffer, piece by piece
+            const uint64_t np0 = (w[0].cut + kPiece - 1) / kPiece, np1 = (w[1].cut + kPiece - 1) / kPiece;
+            std::atomic<uint64_t> next{0};
+            gang.run([&](int) {
+                for (uint64_t q; (q = next.fetch_add(1)) < np0 + np1;) {
+                    const int s = q < np0 ? 0 : 1;
+                    const uint64_t a = (s ? q - np0 : q) * kPiece, e = std::min(w[s].cut, a + kPiece);
+                    std::memcpy(b.text + (s ? at2 : 0) + a, w[s].p + a, e - a);
+                }
+            });
+        }
+        b.text_len = w[0].cut;
+        b.text2_off = at2;
+        b.text2_len = w[1].cut;
+        b.n_reads = b.n_process = 2 * n;
+        rec_bytes = (double)std::max(w[0].cut, w[1].cut) / (double)std::max<uint64_t>(n, 1);
+        for (int s = 0; s < 2; s++) {
+            TextSrc &src = msrc[s];
+            src.sent += w[s].cut;
+            if (src.map) src.pos += w[s].cut;
+            else src.pend.erase(src.pend.begin(), src.pend.begin() + (ptrdiff_t)w[s].cut);
+        }
+        eof = last;
+        return 1;
+    };
     std::thread reader([&] {
         uint64_t next_read = 0, next_block = 0, batch_no = 0;
         int prev = -1;
         uint64_t carry = 0;  // reads at the tail of ring[prev] past its processed blocks
-        bool as_text = text != nullptr || streamed;
+        bool as_text = text != nullptr || streamed || mate_path;  // (a mate input that is no text failed above)
         std::unique_ptr<ntc::Gang> gang(as_text ? new ntc::Gang(RT) : nullptr);
         for (;;) {
             int bi;
@@ -584,15 +758,16 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 if (sh.error != NTC_OK) break;
             }
             Batch &b = ring[(size_t)bi];
-            b.is_text = false;
+            b.is_text = b.is_pair = false;
             if (as_text) {
                 const auto tp = Clock::now();
                 bool eof = false;
-                const int r = fill_text(*gang, b, eof);
+                const int r = mate_path ? fill_pair(*gang, b, eof) : fill_text(*gang, b, eof);
                 add_time(t_parse, secs(tp, Clock::now()));
                 if (r > 0) {
                     if (batch_no == 0) S.first_batch_s = secs(t0, Clock::now());
                     b.is_text = true;
+                    b.is_pair = mate_path != nullptr;
                     b.first_read = next_read;
                     b.first_block = next_block;
                     next_read += b.n_process;
@@ -612,6 +787,16 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 if (r == 0) break;
                 if (r == -2) {
                     sh.fail(NTC_ERR_IO, "FASTX input: malformed or unreadable");
+                    break;
+                }
+                if (r == -3) {
+                    sh.fail(NTC_ERR_FORMAT, "mate files hold different numbers of records", (int64_t)next_read);
+                    break;
+                }
+                if (pair_mode) {
+                    sh.fail(NTC_ERR_UNSUPPORTED, "pairs: a blank line, or records that are not four lines each: "
+                                                 "this batch needs the host parser, which drops the header lines",
+                            (int64_t)next_read);
                     break;
                 }
                 if (q_mode) {
@@ -746,14 +931,20 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 int64_t bad = -1;
                 uint64_t nb = 0;
                 const auto tg = Clock::now();
-                const int r = b.is_text ? ntc_encode_pack_fastq(ctxs[c], b.text, b.text_len, b.n_process, BR,
-                                                                metas.data(), &payload, &plen, &nb, &bad)
-                                        : ntc_encode_pack_batch(ctxs[c], b.bases, b.offs, b.n_process, BR,
-                                                                metas.data(), &payload, &plen, &bad);
+                if (pair_mode && (b.n_process & 1)) {  // (only the input's last batch can be odd)
+                    sh.fail(NTC_ERR_FORMAT, "pairs: an odd number of reads in an interleaved input", (int64_t)(b.first_read + b.n_process - 1));
+                    return;
+                }
+                const int r = b.is_pair ? ph.encode_paired(ctxs[c], b.text, b.text_len, b.text + b.text2_off, b.text2_len,
+                                                           b.n_process / 2, BR, metas.data(), &payload, &plen, &nb, &bad)
+                              : b.is_text ? ntc_encode_pack_fastq(ctxs[c], b.text, b.text_len, b.n_process, BR,
+                                                                  metas.data(), &payload, &plen, &nb, &bad)
+                                          : ntc_encode_pack_batch(ctxs[c], b.bases, b.offs, b.n_process, BR,
+                                                                  metas.data(), &payload, &plen, &bad);
                 add_time(t_gpu, secs(tg, Clock::now()));
                 if (r) {
                     ntc_buffer_free(payload);
-                    if (b.is_text && r == NTC_ERR_FORMAT && !q_mode && !n_mode)  // as the host parser reports it
+                    if (b.is_text && r == NTC_ERR_FORMAT && !q_mode && !n_mode && !pair_mode)  // as the host parser reports it
                         sh.fail(r, "FASTX input: malformed or unreadable");
                     else
                         sh.fail(r, std::string("encode: ") + ntc_last_error(ctxs[c]),
@@ -1071,6 +1262,7 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     }
     etrace("buffers freed", 0);
     ntc_fastx_close(fx);
+    if (fx2) ntc_fastx_close(fx2);
     etrace("input closed", 0);
     const int result = sh.error == -1 ? NTC_OK : sh.error;
     S.alloc_s += t_pin.load();
@@ -1088,6 +1280,10 @@ static int encode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     if (qs) *qs = QS;
     if (ns) *ns = NS;
     if (ds) *ds = DS;
+    PS.pairs = pair_mode ? S.reads / 2 : 0;
+    PS.bytes1 = msrc[0].sent;
+    PS.bytes2 = msrc[1].sent;
+    if (ps) *ps = PS;
     return result;
 }
 
@@ -1123,6 +1319,14 @@ int ntc_encode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
     if (!fo || fo->struct_bytes < sizeof(ntc_file_opts3) || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
     return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
                             fo->q_fd, q, fo->n_mode, fo->n_fd, n, fo->d_mode, fo->d_fd, d);
+}
+
+int ntc_encode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts4 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n, ntc_d_stats *d, ntc_p_stats *p) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts4) || fo->nx_policy < 0) return NTC_ERR_INVALID_ARG;
+    return encode_file_impl(ctxs, n_ctx, in_path, out_fd, fo->nx_policy, fo->nx_fd, opts, stats, nx, fo->q_mode,
+                            fo->q_fd, q, fo->n_mode, fo->n_fd, n, fo->d_mode, fo->d_fd, d, fo->pair_mode, fo->mate_path, p);
 }
 
 }  // extern "C"
@@ -1175,6 +1379,7 @@ struct DSlot {  // one batch in flight
     uint64_t batch = ~0ULL;  // batch held, ~0 = free
     uint64_t first_block = 0, n_blocks = 0;
     uint64_t n_recs = 0, n_reads = 0, n_bases = 0, text_len = 0;
+    uint64_t first_len = 0;  // pairs: the bytes of the mate-1 part, at the head of text
     uint64_t first_id = 0;
     uint64_t finished = 0;   // blocks of this batch unzipped or found damaged
     int bad_block = -1;      // first damaged block (index in the batch)
@@ -1216,11 +1421,19 @@ extern "C" {
 static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, const char *nx_path, int out_fd,
                             const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, const char *q_path = nullptr,
                             const char *n_path = nullptr, const char *d_path = nullptr, ntc_d_stats *ds = nullptr,
-                            bool may_discard = false) {
+                            bool may_discard = false, int pair_mode = 0, int out_fd2 = -1, ntc_p_stats *ps = nullptr) {
     // d_path / ds: ntc_decode_file_ex3's digest file (null: none); may_discard: out_fd -1 runs
     // everything but the copy of the text off the device and its write
     const bool discard = may_discard && out_fd == -1;
     if (!ctxs || n_ctx <= 0 || !in_path || (out_fd < 0 && !discard)) return NTC_ERR_INVALID_ARG;
+    // pair_mode / out_fd2 / ps: ntc_decode_file_ex4's pairs (pair_mode 0: none): each batch's text
+    // comes back split, its mate-1 records go to out_fd and its mate-2 records to out_fd2
+    if (pair_mode < 0 || pair_mode > 2 || (pair_mode ? out_fd2 < 0 && !discard : out_fd2 != -1)) return NTC_ERR_INVALID_ARG;
+    const ntc::PHooks &ph = ntc::g_p_hooks;
+    if (pair_mode && (!ph.set_mode || !ph.pair_split)) return NTC_ERR_UNSUPPORTED;
+    const bool split = pair_mode && !discard;
+    ntc_p_stats PS{};
+    PS.mode = (uint32_t)pair_mode;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
     // the exception runs, read once; each batch finds its own by its first read (put_runs)
@@ -1595,6 +1808,17 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                 sh.fail(NTC_ERR_HIP, std::string("decode: ") + ntc_last_error(ctxs[c]));
                 return;
             }
+            // pairs: every text call of this thread returns its two parts (option dropped at its end)
+            struct Pairs {
+                ntc_ctx *ctx;
+                ~Pairs() {
+                    if (ctx) ntc::g_p_hooks.set_mode(ctx, 0);
+                }
+            } pairs_reset{split ? ctxs[c] : nullptr};
+            if (split && ph.set_mode(ctxs[c], pair_mode)) {
+                sh.fail(NTC_ERR_HIP, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                return;
+            }
             std::vector<ntc_nx_run> nx_tmp;  // a batch's exception runs, renumbered from its first read
             std::vector<ntc_qual_meta> q_tmp;  // ... and its quality sections
             std::vector<ntc_name_meta> n_tmp;  // ... and its name sections
@@ -1675,12 +1899,18 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                         sh.fail(rf, msg, bad);
                         return;
                     }
+                    uint64_t first = 0;
+                    if (split && ph.pair_split(ctxs[c], &first)) {
+                        sh.fail(NTC_ERR_FORMAT, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                        return;
+                    }
                     std::lock_guard<std::mutex> g(sh.mu);
                     {
                         std::string unused;
                         int64_t bad = -1;
                         digest_verdict(ctxs[c], NTC_OK, sl.first_block, nb, sl.first_id - 1, unused, bad);
                     }
+                    sl.first_len = first;
                     sl.text_len = len;
                     sl.decoded = true;
                     trace("decoded", b);
@@ -1741,12 +1971,18 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
                     sh.fail(rc, msg, bad);
                     return;
                 }
+                uint64_t first = 0;
+                if (split && ph.pair_split(ctxs[c], &first)) {
+                    sh.fail(NTC_ERR_FORMAT, std::string("decode: ") + ntc_last_error(ctxs[c]));
+                    return;
+                }
                 std::lock_guard<std::mutex> g(sh.mu);
                 {
                     std::string unused;
                     int64_t bad = -1;
                     digest_verdict(ctxs[c], NTC_OK, sl.first_block, nbk, sl.first_id - 1, unused, bad);
                 }
+                sl.first_len = first;
                 sl.text_len = len;
                 sl.decoded = true;
                 trace("decoded", b);
@@ -1907,6 +2143,16 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
         }
         return true;
     };
+    auto write_mate = [&](const uint8_t *p, uint64_t n) -> bool {
+        while (n) {
+            const ssize_t w = ::write(out_fd2, p, n);
+            if (w < 0 && errno == EINTR) continue;
+            if (w <= 0) return false;
+            p += w;
+            n -= (uint64_t)w;
+        }
+        return true;
+    };
     for (uint64_t b = 0; b < n_batches; b++) {
         DSlot *slp;
         {
@@ -1922,7 +2168,15 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
             slp = &slot_of(b);
         }
         const auto tw = Clock::now();
-        if (!discard && !write_text(slp->text, slp->text_len)) sh.fail(NTC_ERR_IO, "write failed");
+        if (split) {  // the mate-1 records to out_fd, the mate-2 records to out_fd2
+            const uint64_t f = std::min(slp->first_len, slp->text_len);
+            if (!write_text(slp->text, f) || !write_mate(slp->text + f, slp->text_len - f)) sh.fail(NTC_ERR_IO, "write failed");
+            PS.bytes1 += f;
+            PS.bytes2 += slp->text_len - f;
+            PS.pairs += slp->n_reads / 2;
+        } else if (!discard && !write_text(slp->text, slp->text_len)) {
+            sh.fail(NTC_ERR_IO, "write failed");
+        }
         add_time(t_write, secs(tw, Clock::now()));
         std::lock_guard<std::mutex> g(sh.mu);
         if (b == 0) S.first_batch_s = secs(t0, Clock::now());
@@ -1991,6 +2245,8 @@ static int decode_file_impl(ntc_ctx *const *ctxs, int n_ctx, const char *in_path
     S.threads = T;
     S.bad_read = result == NTC_ERR_DIGEST ? sh.bad_read : -1;
     if (ds) *ds = DS;
+    if (pair_mode && discard) PS.pairs = S.reads / 2;
+    if (ps) *ps = PS;
     if (result != NTC_OK)
         std::snprintf(S.error, sizeof(S.error), "%s", sh.msg.c_str());
     else if (stop_batch >= 0)  // not an error for the reference either: its loop just ends
@@ -2027,6 +2283,13 @@ int ntc_decode_file_ex3(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
     if (!fo || fo->struct_bytes < sizeof(ntc_file_opts3)) return NTC_ERR_INVALID_ARG;
     return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path, fo->n_path, fo->d_path, d,
                             true);
+}
+
+int ntc_decode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts4 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts4)) return NTC_ERR_INVALID_ARG;
+    return decode_file_impl(ctxs, n_ctx, in_path, fo->nx_path, out_fd, opts, stats, fo->q_path, fo->n_path, fo->d_path, d,
+                            true, fo->pair_mode, fo->out_fd2, p);
 }
 
 }  // extern "C"
