@@ -1283,60 +1283,21 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
     if mate_path is not None and pair_mode is None:
         pair_mode = "ids"
-    if pair_mode is not None and _pair_code(pair_mode):
-        fo = FileOpts4(ctypes.sizeof(FileOpts4), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
-                       None, None, _names_code(names or 0), n_fd, None, 0 if d_fd is None else 1, -1 if d_fd is None else d_fd,
-                       None, _pair_code(pair_mode), None if mate_path is None else os.fsencode(mate_path), -1)
-        nx, q, n, ds, ps = NxStats(), QStats(), NStats(), DStats(), PStats()
-        d = _run_pipeline("ntc_encode_file_ex4", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
-                          tail=(ctypes.byref(nx), ctypes.byref(q), ctypes.byref(n), ctypes.byref(ds), ctypes.byref(ps)))
-        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
-        if qualities is not None:
-            d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
-        if names is not None:
-            d["n"] = {k: int(getattr(n, k)) for k, _ in NStats._fields_}
-        if d_fd is not None:
-            d["d"] = ds.as_dict()
-        d["p"] = ps.as_dict()
-        return d
-    if d_fd is not None:
-        fo = FileOpts3(ctypes.sizeof(FileOpts3), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
-                       None, None, _names_code(names or 0), n_fd, None, 1, d_fd, None)
-        nx, q, n, ds = NxStats(), QStats(), NStats(), DStats()
-        d = _run_pipeline("ntc_encode_file_ex3", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
-                          tail=(ctypes.byref(nx), ctypes.byref(q), ctypes.byref(n), ctypes.byref(ds)))
-        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
-        if qualities is not None:
-            d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
-        if names is not None:
-            d["n"] = {k: int(getattr(n, k)) for k, _ in NStats._fields_}
-        d["d"] = ds.as_dict()
-        return d
-    if names is not None:
-        fo = FileOpts2(ctypes.sizeof(FileOpts2), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd,
-                       None, None, _names_code(names), n_fd, None)
-        nx, q, n = NxStats(), QStats(), NStats()
-        d = _run_pipeline("ntc_encode_file_ex2", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
-                          tail=(ctypes.byref(nx), ctypes.byref(q), ctypes.byref(n)))
-        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
-        if qualities is not None:
-            d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
-        d["n"] = {k: int(getattr(n, k)) for k, _ in NStats._fields_}
-        return d
-    if qualities is not None:
-        fo = FileOpts(_policy_code(non_acgt or 0), nx_fd, _quality_code(qualities), q_fd, None, None)
-        nx, q = NxStats(), QStats()
-        d = _run_pipeline("ntc_encode_file_ex", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
-                          tail=(ctypes.byref(nx), ctypes.byref(q)))
-        d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
-        d["q"] = {k: int(getattr(q, k)) for k, _ in QStats._fields_}
-        return d
-    if non_acgt is None:
+    pairs = _pair_code(pair_mode) if pair_mode is not None else 0
+    level = 4 if pairs else 3 if d_fd is not None else 2 if names is not None else 1 if qualities is not None else 0
+    if level == 0 and non_acgt is None:
         return _run_pipeline("ntc_encode_file", ctxs, in_path, out_fd, o)
-    nx = NxStats()
-    d = _run_pipeline("ntc_encode_file_nx", ctxs, in_path, out_fd, o, mid=(_policy_code(non_acgt), nx_fd),
-                      tail=(ctypes.byref(nx),))
-    d["nx"] = {k: int(getattr(nx, k)) for k, _ in NxStats._fields_}
+    side = [("nx", NxStats()), ("q", QStats()), ("n", NStats()), ("d", DStats()), ("p", PStats())][:level + 1]
+    if level == 0:
+        fn, mid = "ntc_encode_file_nx", (_policy_code(non_acgt), nx_fd)
+    else:
+        fo = _file_opts(level, (_policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd, None, None,
+                                _names_code(names or 0), n_fd, None, 0 if d_fd is None else 1, -1 if d_fd is None else d_fd,
+                                None, pairs, None if mate_path is None else os.fsencode(mate_path), -1))
+        fn, mid = _LEVELS[level].format("encode"), (ctypes.byref(fo),)
+    d = _run_pipeline(fn, ctxs, in_path, out_fd, o, mid=mid, tail=tuple(ctypes.byref(s) for _, s in side))
+    asked = {"nx": True, "q": qualities is not None, "n": names is not None, "d": d_fd is not None, "p": True}
+    d.update({key: _stats_dict(s) for key, s in side if asked[key]})
     return d
 
 
@@ -1359,44 +1320,26 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
     ("ids" or "nocheck": the archive holds pairs; ntc_decode_file_ex4): the mate-1 records go to
     out_fd and the mate-2 records to out_fd2; the stats gain a "p" dict (ntc_p_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
-    if pair_mode is not None and _pair_code(pair_mode):
-        enc = lambda p: None if p is None else os.fsencode(p)
-        fo = FileOpts4(ctypes.sizeof(FileOpts4), 0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1,
-                       enc(d_path), _pair_code(pair_mode), None, out_fd2)
-        ds, ps = DStats(), PStats()
-        try:
-            d = _run_pipeline("ntc_decode_file_ex4", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
-                              tail=(ctypes.byref(ds), ctypes.byref(ps)))
-        except NtcError as e:
-            e.stats["d"] = ds.as_dict()
-            raise
-        if d_path is not None:
-            d["d"] = ds.as_dict()
-        d["p"] = ps.as_dict()
-        return d
-    if d_path is not None:
-        enc = lambda p: None if p is None else os.fsencode(p)
-        fo = FileOpts3(ctypes.sizeof(FileOpts3), 0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1,
-                       enc(d_path))
-        ds = DStats()
-        try:
-            d = _run_pipeline("ntc_decode_file_ex3", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
-                              tail=(ctypes.byref(ds),))
-        except NtcError as e:
-            e.stats["d"] = ds.as_dict()
-            raise
-        d["d"] = ds.as_dict()
-        return d
-    if n_path is not None:
-        fo = FileOpts2(ctypes.sizeof(FileOpts2), 0, -1, 0, -1, None if nx_path is None else os.fsencode(nx_path),
-                       None if q_path is None else os.fsencode(q_path), 0, -1, os.fsencode(n_path))
-        return _run_pipeline("ntc_decode_file_ex2", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),))
-    if q_path is not None:
-        fo = FileOpts(0, -1, 0, -1, None if nx_path is None else os.fsencode(nx_path), os.fsencode(q_path))
-        return _run_pipeline("ntc_decode_file_ex", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),))
-    if nx_path is None:
-        return _run_pipeline("ntc_decode_file", ctxs, in_path, out_fd, o)
-    return _run_pipeline("ntc_decode_file_nx", ctxs, in_path, out_fd, o, pre_fd=(os.fsencode(nx_path),))
+    pairs = _pair_code(pair_mode) if pair_mode is not None else 0
+    level = 4 if pairs else 3 if d_path is not None else 2 if n_path is not None else 1 if q_path is not None else 0
+    if level == 0:
+        if nx_path is None:
+            return _run_pipeline("ntc_decode_file", ctxs, in_path, out_fd, o)
+        return _run_pipeline("ntc_decode_file_nx", ctxs, in_path, out_fd, o, pre_fd=(os.fsencode(nx_path),))
+    enc = lambda p: None if p is None else os.fsencode(p)
+    fo = _file_opts(level, (0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1, enc(d_path), pairs, None,
+                            out_fd2))
+    side = [("d", DStats()), ("p", PStats())][:max(0, level - 2)]
+    try:
+        d = _run_pipeline(_LEVELS[level].format("decode"), ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                          tail=tuple(ctypes.byref(s) for _, s in side))
+    except NtcError as e:
+        if side:
+            e.stats["d"] = side[0][1].as_dict()
+        raise
+    asked = {"d": d_path is not None, "p": True}
+    d.update({key: _stats_dict(s) for key, s in side if asked[key]})
+    return d
 
 
 def read_exceptions(path):
@@ -1526,6 +1469,23 @@ def write_exceptions(fd, runs, sub, header=True):
     rc = lib().ntc_nx_write(fd, _p(runs) if len(runs) else None, len(runs), sub, 1 if header else 0)
     if rc:
         raise NtcError(rc, "ntc_nx_write")
+
+
+# the entry points that take an ntc_file_opts struct, by level, and their struct
+_LEVELS = {1: "ntc_{}_file_ex", 2: "ntc_{}_file_ex2", 3: "ntc_{}_file_ex3", 4: "ntc_{}_file_ex4"}
+
+
+def _file_opts(level, values):
+    """The ntc_file_opts struct of a level from the values of ntc_file_opts4's fields (after
+    struct_bytes) in order: each level's struct holds a prefix of them."""
+    cls = (FileOpts, FileOpts2, FileOpts3, FileOpts4)[level - 1]
+    if level == 1:
+        return cls(*values[:len(cls._fields_)])
+    return cls(ctypes.sizeof(cls), *values[:len(cls._fields_) - 1])
+
+
+def _stats_dict(s):
+    return s.as_dict() if hasattr(s, "as_dict") else {k: int(getattr(s, k)) for k, _ in s._fields_}
 
 
 def _run_pipeline(fn, ctxs, in_path, out_fd, o, pre_fd=(), mid=(), tail=()):

@@ -403,3 +403,108 @@ def test_warm_dma_option():
         with pytest.raises(nt.NtcError):
             ctx.set_option("warm_dma", bad)
     ctx.close()
+
+
+# ---- the entry-point ladder (ntc_{en,de}code_file, _nx, _ex, _ex2, _ex3, _ex4) -------------------
+def _ladder_reads():
+    """300 reads of 30-60 bases (one partial block, an even count), mates named /1 and /2, N runs
+    in a handful of them"""
+    rng = np.random.default_rng(77)
+    g = nt.synth_genome(12, 400_000).tobytes()
+    reads = []
+    for i in range(300):
+        ln = int(rng.integers(30, 61))
+        s = int(rng.integers(0, len(g) - 60))
+        r = bytearray(g[s:s + ln])
+        if i % 41 == 3:
+            r[ln // 2:ln // 2 + 2] = b"NN"
+        reads.append(bytes(r))
+    names = [b"r%d/%d" % (i // 2, i % 2 + 1) for i in range(300)]
+    return names, reads
+
+
+def _fastq(names, reads):
+    return b"".join(b"@%s\n%s\n+\n%s\n" % (n, r, b"I" * len(r)) for n, r in zip(names, reads))
+
+
+@pytest.mark.parametrize("n_ctx", [1, 2])
+def test_entry_point_ladder_is_only_a_ladder(setup, tmp_path, n_ctx):
+    """Every exported file entry point reaches the same pipeline: the levels the binding selects
+    write byte-identical encoded.dat and exception files, and every decode level, handed only
+    null paths beyond the exception file (the digest file at _ex3, the second descriptor at
+    _ex4), writes the same text."""
+    import ctypes
+
+    import pair_lib as pl
+
+    d, genome, ix = setup
+    ctxs = [nt.GpuContext(0).upload(ix)]
+    if n_ctx == 2:
+        ctxs.append(nt.GpuContext(0).share_index(ctxs[0]))
+    try:
+        names, reads = _ladder_reads()
+        assert len(reads) % 2 == 0 and 0 < sum(b"N" in r for r in reads) < 20
+        fq = tmp_path / "l.fq"
+        fq.write_bytes(_fastq(names, reads))
+        levels = {"nx": {}, "ex": dict(qualities="drop"), "ex2": dict(names="drop"), "ex3": dict(d_fd=True),
+                  "ex4": dict(pair_mode="nocheck")}
+        got = {}
+        for tag, kw in levels.items():
+            with open(tmp_path / f"{tag}.dat", "wb") as f, open(tmp_path / f"{tag}.ntcx", "wb") as fx, \
+                    open(tmp_path / f"{tag}.ntcd", "wb") as fd:
+                if "d_fd" in kw:
+                    kw = dict(d_fd=fd.fileno())
+                st = nt.encode_file(ctxs, str(fq), f.fileno(), threads=2, non_acgt="keep", nx_fd=fx.fileno(), **kw)
+            assert st["reads"] == 300 and st["blocks"] == 1 and st["gpu_parsed"] == 1, tag
+            assert st["nx"]["runs"] > 0, tag
+            assert ("q" in st, "n" in st, "d" in st, "p" in st) == (tag == "ex", tag == "ex2", tag == "ex3", tag == "ex4")
+            got[tag] = ((tmp_path / f"{tag}.dat").read_bytes(), (tmp_path / f"{tag}.ntcx").read_bytes())
+        for tag in levels:
+            assert got[tag] == got["nx"], tag
+        assert len((tmp_path / "ex3.ntcd").read_bytes()) > 0
+
+        # plain ntc_encode_file / ntc_decode_file on the reads without N
+        clean = [(n, r) for n, r in zip(names, reads) if b"N" not in r]
+        (tmp_path / "c.fq").write_bytes(_fastq(*zip(*clean)))
+        with open(tmp_path / "c.dat", "wb") as f:
+            st = nt.encode_file(ctxs, str(tmp_path / "c.fq"), f.fileno(), threads=2)
+        assert "nx" not in st and st["reads"] == len(clean)
+        with open(tmp_path / "c.fa", "wb") as f:
+            nt.decode_file(ctxs, str(tmp_path / "c.dat"), f.fileno(), threads=2)
+        assert (tmp_path / "c.fa").read_bytes() == b"".join(b">seq.%d\n%s\n" % (i + 1, r) for i, (_, r) in enumerate(clean))
+
+        # the _nx archive through every decode level
+        o = nt.PipelineOpts(2, 2, 0, 0, 0)
+        dat, nxp, dp = str(tmp_path / "nx.dat"), os.fsencode(str(tmp_path / "nx.ntcx")), os.fsencode(str(tmp_path / "ex3.ntcd"))
+
+        def run(fn, fds, kw):
+            with open(tmp_path / "o1", "wb") as f1, open(tmp_path / "o2", "wb") as f2:
+                fo = fds(f2.fileno())
+                nt._run_pipeline(fn, ctxs, dat, f1.fileno(), o, **kw(fo))
+            return (tmp_path / "o1").read_bytes(), (tmp_path / "o2").read_bytes()
+
+        mid = lambda fo: dict(mid=(ctypes.byref(fo),))
+        ds, ps = nt.DStats(), nt.PStats()
+        text = {
+            "nx": run("ntc_decode_file_nx", lambda _: None, lambda _: dict(pre_fd=(nxp,))),
+            "ex": run("ntc_decode_file_ex", lambda _: nt.FileOpts(0, -1, 0, -1, nxp, None), mid),
+            "ex2": run("ntc_decode_file_ex2",
+                       lambda _: nt.FileOpts2(ctypes.sizeof(nt.FileOpts2), 0, -1, 0, -1, nxp, None, 0, -1, None), mid),
+            "ex3": run("ntc_decode_file_ex3",
+                       lambda _: nt.FileOpts3(ctypes.sizeof(nt.FileOpts3), 0, -1, 0, -1, nxp, None, 0, -1, None, 0, -1, dp),
+                       lambda fo: dict(mid=(ctypes.byref(fo),), tail=(ctypes.byref(ds),))),
+            "ex4": run("ntc_decode_file_ex4",
+                       lambda fd2: nt.FileOpts4(ctypes.sizeof(nt.FileOpts4), 0, -1, 0, -1, nxp, None, 0, -1, None, 0, -1, None,
+                                                2, None, fd2),
+                       lambda fo: dict(mid=(ctypes.byref(fo),), tail=(ctypes.byref(ds), ctypes.byref(ps)))),
+        }
+        exp = b"".join(b">seq.%d\n%s\n" % (i + 1, r) for i, r in enumerate(reads))
+        for tag in ("nx", "ex", "ex2", "ex3"):
+            assert text[tag] == (exp, b""), tag
+        o1, o2 = text["ex4"]
+        assert (o1, o2) == pl.split(exp, 2)
+        assert b"".join(a + b for a, b in zip(pl._records(o1, 2), pl._records(o2, 2))) == exp
+        assert ps.as_dict()["pairs"] == 150
+    finally:
+        for c in ctxs:
+            c.close()
