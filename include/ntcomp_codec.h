@@ -482,6 +482,21 @@ int ntc_encode_pack_fastq_paired(ntc_ctx *ctx, const uint8_t *fastq1, uint64_t b
                                  uint8_t **payload, uint64_t *payload_bytes, uint64_t *n_bases, int64_t *bad_read);
 int ntc_decode_pair_split(ntc_ctx *ctx, uint64_t *first_bytes);
 
+/* ---- a window on a batch's text ---------------------------------------------------------------- */
+/* ntc_decode_set_window: the next ntc_decode_fasta or ntc_decode_fasta_unpacked call on this
+ * context decodes its batch whole -- walk, exception runs, qualities, names, digests: a digest
+ * that differs outside the window still fails the call -- and formats only reads
+ * [first, first + count) of it.  Read r of the batch keeps the id first_id + r, its name and
+ * its quality line.  The window is dropped by the call that used it, whatever it returned (a
+ * call that only reports sizes keeps it).  count = 0 is NTC_ERR_INVALID_ARG and drops a pending
+ * window.  In the call that takes it: first + count > the batch's reads is
+ * NTC_ERR_INVALID_ARG; under "paired" both numbers must be even (whole pairs), else
+ * NTC_ERR_INVALID_ARG, and the split is that of the window's pairs.  out_capacity must hold the
+ * whole batch's text, as a size query reports it (the window's bytes depend on each read's
+ * bases and name and are only known on the device); the call copies the window's bytes alone
+ * and *out_len, and ntc_decode_pair_split, report those.                                       */
+int ntc_decode_set_window(ntc_ctx *ctx, uint64_t first, uint64_t count);
+
 #ifdef __cplusplus
 }
 #endif

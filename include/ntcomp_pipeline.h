@@ -293,6 +293,76 @@ int ntc_encode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
 int ntc_decode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts4 *fo,
                         const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p);
 
+/* ---- a range of reads: seek by block, window the text ------------------------------------------ */
+/* ntc_archive_info (host only, no context): the blocks of the encoded.dat at path, from their
+ * stream headers alone -- nothing is inflated.  *blocks (freed with ntc_buffer_free; null when
+ * there are none): byte offset and length, reads (BlockHeader.num_records), records (the flag
+ * stream's num_u64) and bad = 1 for a block whose headers cannot describe their gzip streams
+ * (its reads and records are then 0: the numbering of every read after it is unknown).
+ * *n_reads / *n_records sum the blocks that are not bad; *tail_bytes = the bytes after the last
+ * whole block (0 for a file that ends cleanly).  Any output but blocks may be null.
+ * NTC_ERR_IO if the file cannot be read.
+ *
+ * ntc_decode_file_ex5 is ntc_decode_file_ex4 for reads [read_first, read_first + read_count) of
+ * the archive, counted from 0.  ntc_file_opts5 holds ntc_file_opts4's fields in the same order,
+ * then its own; struct_bytes must be at least sizeof(ntc_file_opts5).  read_count = 0: the whole
+ * file, exactly as ntc_decode_file_ex4 decodes it (read_first is ignored).  Otherwise only the
+ * blocks that hold the range are inflated and decoded -- the gzip payload of a skipped block is
+ * never inflated -- and of the first and last of them only the range's reads are formatted
+ * (ntc_decode_set_window); every read keeps its number in the archive (seq.N), its name, its
+ * qualities and its exception runs, and the digests of the touched blocks are checked whole.
+ * The texts of ranges that partition the archive, concatenated, are the full decode byte for
+ * byte.  Under pair_mode both numbers must be even.
+ * A range request is strict, as a decode under a digest file is: NTC_ERR_FORMAT, with the case
+ * in stats->error, for a bad block anywhere up to the range's last block, a touched block that
+ * does not inflate or decodes to another read count than its header's, a side file (quality,
+ * name, digest) whose section count differs from the archive's block count or a section whose
+ * n_reads differs from its block's header (both checked before any GPU call, from metadata
+ * alone).  NTC_ERR_INVALID_ARG, with the archive's read count in stats->error: read_first >=
+ * the archive's reads, or read_first + read_count > them.
+ * stats: blocks = the touched blocks, reads = the reads written, bases = the bases decoded
+ * (those of the touched blocks), bytes_out = the text written.  r (may be NULL): the
+ * archive's blocks and reads, the first touched block and how many, the reads written, and the
+ * reads of the first / last touched block left out of the text.                                 */
+typedef struct ntc_archive_block {
+    uint64_t offset, bytes;    /* the block in the file                            */
+    uint64_t reads, records;   /* 0 when bad                                       */
+    uint32_t bad;              /* 1: damaged headers                               */
+    uint32_t reserved;
+} ntc_archive_block;
+int ntc_archive_info(const char *path, ntc_archive_block **blocks, uint64_t *n_blocks, uint64_t *n_reads,
+                     uint64_t *n_records, uint64_t *tail_bytes);
+
+typedef struct ntc_file_opts5 {
+    uint32_t struct_bytes; /* sizeof(ntc_file_opts5)                           */
+    int32_t nx_policy;     /* NTC_NX_*                                         */
+    int32_t nx_fd;         /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;        /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;          /* encode: quality file, -1 = none                  */
+    const char *nx_path;   /* decode: exceptions file, NULL = none             */
+    const char *q_path;    /* decode: quality file, NULL = none                */
+    int32_t n_mode;        /* 0 drop, 1 keep, 2 id                             */
+    int32_t n_fd;          /* encode: name file, -1 = none                     */
+    const char *n_path;    /* decode: name file, NULL = none                   */
+    int32_t d_mode;        /* 0 none, 1 write digests                          */
+    int32_t d_fd;          /* encode: digest file, -1 = none                   */
+    const char *d_path;    /* decode: digest file, NULL = none                 */
+    int32_t pair_mode;     /* 0 off, 1 pairs + mate check, 2 pairs, no check   */
+    const char *mate_path; /* encode: the mate-2 input, NULL = in_path is interleaved */
+    int32_t out_fd2;       /* decode: the mate-2 text, -1 = none               */
+    uint64_t read_first;   /* decode: the range's first read, from 0           */
+    uint64_t read_count;   /* decode: its reads, 0 = the whole file            */
+} ntc_file_opts5;
+typedef struct ntc_r_stats {
+    uint64_t blocks_total, reads_total; /* the archive's                                  */
+    uint64_t first_block, blocks_read;  /* the touched blocks                             */
+    uint64_t reads_written;
+    uint64_t head_skipped, tail_skipped; /* reads of the first / last touched block not written */
+} ntc_r_stats;
+int ntc_decode_file_ex5(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts5 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p,
+                        ntc_r_stats *r);
+
 #ifdef __cplusplus
 }
 #endif

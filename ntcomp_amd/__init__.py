@@ -57,6 +57,7 @@ EXPORTED = [
     "ntc_encode_digests", "ntc_decode_set_digests", "ntc_decode_digests", "ntc_d_write_header",
     "ntc_d_write_section", "ntc_d_read", "ntc_encode_file_ex3", "ntc_decode_file_ex3",
     "ntc_encode_pack_fastq_paired", "ntc_decode_pair_split", "ntc_encode_file_ex4", "ntc_decode_file_ex4",
+    "ntc_decode_set_window", "ntc_decode_file_ex5", "ntc_archive_info",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -208,6 +209,26 @@ class FileOpts3(ctypes.Structure):
 class FileOpts4(ctypes.Structure):
     """ntc_file_opts4 (include/ntcomp_pipeline.h): ntc_file_opts3 and the pairs."""
     _fields_ = FileOpts3._fields_ + [("pair_mode", ctypes.c_int32), ("mate_path", ctypes.c_char_p), ("out_fd2", ctypes.c_int32)]
+
+
+class FileOpts5(ctypes.Structure):
+    """ntc_file_opts5 (include/ntcomp_pipeline.h): ntc_file_opts4 and the range of reads."""
+    _fields_ = FileOpts4._fields_ + [("read_first", ctypes.c_uint64), ("read_count", ctypes.c_uint64)]
+
+
+class RStats(ctypes.Structure):
+    """ntc_r_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("blocks_total", "reads_total", "first_block", "blocks_read",
+                                               "reads_written", "head_skipped", "tail_skipped")]
+
+
+class ArchiveBlock(ctypes.Structure):
+    """ntc_archive_block (include/ntcomp_pipeline.h): one block of an encoded.dat, from its headers."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("offset", "bytes", "reads", "records")] + \
+               [("bad", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
 class PStats(ctypes.Structure):
@@ -412,6 +433,12 @@ def lib():
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats)]),
         "ntc_decode_file_ex3": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts3), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats)]),
+        "ntc_decode_file_ex5": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts5), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats),
+                                    ctypes.POINTER(RStats)]),
+        "ntc_decode_set_window": (I, [P, u64, u64]),
+        "ntc_archive_info": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                 ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "ntc_nx_write": (I, [I, P, u64, u32, I]),
         "ntc_nx_read": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "ntc_encode_file_nx": (I, [P, I, ctypes.c_char_p, I, I, I, ctypes.POINTER(PipelineOpts),
@@ -1000,6 +1027,12 @@ class GpuContext:
         self._check(self.L.ntc_decode_pair_split(self.h, ctypes.byref(first)), "ntc_decode_pair_split")
         return int(first.value)
 
+    def set_window(self, first, count):
+        """Only reads [first, first + count) of the next decode_fasta / decode_fasta_unpacked
+        batch are formatted (ntc_decode_set_window); the batch is still decoded and checked
+        whole, and the reads keep their ids, names and qualities."""
+        self._check(self.L.ntc_decode_set_window(self.h, int(first), int(count)), "ntc_decode_set_window")
+
     def encode_status(self):
         bad, n = ctypes.c_int64(-1), ctypes.c_uint64()
         self._check(self.L.ntc_encode_status(self.h, ctypes.byref(bad), ctypes.byref(n)), "ntc_encode_status")
@@ -1302,7 +1335,7 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
 
 
 def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None, n_path=None,
-                d_path=None, out_fd2=-1, pair_mode=None):
+                d_path=None, out_fd2=-1, pair_mode=None, reads=None):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
@@ -1318,18 +1351,24 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
     index; a damaged or truncated input is then NTC_ERR_FORMAT; the stats gain a "d" dict
     (ntc_d_stats).  With d_path, out_fd -1 checks without copying or writing the text.  pair_mode
     ("ids" or "nocheck": the archive holds pairs; ntc_decode_file_ex4): the mate-1 records go to
-    out_fd and the mate-2 records to out_fd2; the stats gain a "p" dict (ntc_p_stats)."""
+    out_fd and the mate-2 records to out_fd2; the stats gain a "p" dict (ntc_p_stats).
+    reads=(first, count): only that range of the archive's reads, counted from 0
+    (ntc_decode_file_ex5; count 0 = the whole file): the blocks that hold it are decoded, the
+    reads keep their numbers, names and qualities, and the stats gain an "r" dict (ntc_r_stats).
+    A range is strict: a damaged block at or before it, or a side file that does not describe the
+    archive's blocks, is NTC_ERR_FORMAT; a range the archive does not hold is
+    NTC_ERR_INVALID_ARG."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
     pairs = _pair_code(pair_mode) if pair_mode is not None else 0
-    level = 4 if pairs else 3 if d_path is not None else 2 if n_path is not None else 1 if q_path is not None else 0
+    level = 5 if reads is not None else 4 if pairs else 3 if d_path is not None else 2 if n_path is not None else 1 if q_path is not None else 0
     if level == 0:
         if nx_path is None:
             return _run_pipeline("ntc_decode_file", ctxs, in_path, out_fd, o)
         return _run_pipeline("ntc_decode_file_nx", ctxs, in_path, out_fd, o, pre_fd=(os.fsencode(nx_path),))
     enc = lambda p: None if p is None else os.fsencode(p)
     fo = _file_opts(level, (0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1, enc(d_path), pairs, None,
-                            out_fd2))
-    side = [("d", DStats()), ("p", PStats())][:max(0, level - 2)]
+                            out_fd2) + (tuple(int(x) for x in reads) if reads is not None else ()))
+    side = [("d", DStats()), ("p", PStats()), ("r", RStats())][:max(0, level - 2)]
     try:
         d = _run_pipeline(_LEVELS[level].format("decode"), ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
                           tail=tuple(ctypes.byref(s) for _, s in side))
@@ -1337,9 +1376,35 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
         if side:
             e.stats["d"] = side[0][1].as_dict()
         raise
-    asked = {"d": d_path is not None, "p": True}
+    asked = {"d": d_path is not None, "p": bool(pairs), "r": True}
     d.update({key: _stats_dict(s) for key, s in side if asked[key]})
     return d
+
+
+def archive_info(path):
+    """The blocks of an encoded.dat from their headers alone (ntc_archive_info; host only, no
+    context): {"blocks": [{"offset", "bytes", "reads", "records", "bad"}, ...], "n_blocks",
+    "n_reads", "n_records", "tail_bytes"}.  A bad block (damaged headers) counts no reads."""
+    p, nb, nr, nrec, tail = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    rc = lib().ntc_archive_info(os.fsencode(path), ctypes.byref(p), ctypes.byref(nb), ctypes.byref(nr),
+                                ctypes.byref(nrec), ctypes.byref(tail))
+    if rc:
+        raise NtcError(rc, f"ntc_archive_info: {path}")
+    try:
+        arr = ctypes.cast(p, ctypes.POINTER(ArchiveBlock))
+        blocks = [arr[i].as_dict() for i in range(nb.value)]
+    finally:
+        lib().ntc_buffer_free(p)
+    return {"blocks": blocks, "n_blocks": int(nb.value), "n_reads": int(nr.value), "n_records": int(nrec.value),
+            "tail_bytes": int(tail.value)}
+
+
+def shard_blocks(i, n, n_blocks):
+    """Blocks [lo, hi) of the i-th (from 1) of n contiguous slices of n_blocks whole blocks:
+    [(i - 1) n_blocks / n, i n_blocks / n), rounded down.  The n slices partition the blocks."""
+    if not 1 <= i <= n:
+        raise ValueError(f"shard {i}/{n}: need 1 <= I <= N")
+    return (i - 1) * n_blocks // n, i * n_blocks // n
 
 
 def read_exceptions(path):
@@ -1472,13 +1537,14 @@ def write_exceptions(fd, runs, sub, header=True):
 
 
 # the entry points that take an ntc_file_opts struct, by level, and their struct
-_LEVELS = {1: "ntc_{}_file_ex", 2: "ntc_{}_file_ex2", 3: "ntc_{}_file_ex3", 4: "ntc_{}_file_ex4"}
+_LEVELS = {1: "ntc_{}_file_ex", 2: "ntc_{}_file_ex2", 3: "ntc_{}_file_ex3", 4: "ntc_{}_file_ex4",
+           5: "ntc_{}_file_ex5"}  # (decode only)
 
 
 def _file_opts(level, values):
-    """The ntc_file_opts struct of a level from the values of ntc_file_opts4's fields (after
+    """The ntc_file_opts struct of a level from the values of ntc_file_opts5's fields (after
     struct_bytes) in order: each level's struct holds a prefix of them."""
-    cls = (FileOpts, FileOpts2, FileOpts3, FileOpts4)[level - 1]
+    cls = (FileOpts, FileOpts2, FileOpts3, FileOpts4, FileOpts5)[level - 1]
     if level == 1:
         return cls(*values[:len(cls._fields_)])
     return cls(ctypes.sizeof(cls), *values[:len(cls._fields_) - 1])

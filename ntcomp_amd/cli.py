@@ -1,4 +1,4 @@
-"""ntcomp command line: `python -m ntcomp_amd build | encode | decode`.
+"""ntcomp command line: `python -m ntcomp_amd build | encode | decode | verify | info`.
 
 Mirrors the reference CLI (src/cli.rs:27-93, src/main.rs:91-211) with the hot path on
 the GPU: FASTX ingest in C++ (needletail parse + normalize(true) restated), encode /
@@ -231,6 +231,74 @@ def _check_p_args(args):
     return None if not pairs else "nocheck" if args.mate_check == "off" else "ids"
 
 
+def parse_reads(spec):
+    """--reads A-B, 1-based and inclusive as decode prints seq.N; also A, A- and -B.  Returns
+    (a, b) with b None for "to the last read"; ValueError for anything else."""
+    s = spec
+    a, sep, b = s.partition("-")
+    if not s or (sep and "-" in b) or not all(x == "" or (x.isascii() and x.isdigit()) for x in (a, b)):
+        raise ValueError(f"--reads {spec}: want A-B, A, A- or -B (1-based, inclusive)")
+    if not sep:
+        lo, hi = a, a
+    else:
+        lo, hi = a or "1", b or None
+    if (not a and not b) or int(lo) < 1 or (hi is not None and int(hi) < int(lo)):
+        raise ValueError(f"--reads {spec}: want 1 <= A <= B")
+    return int(lo), None if hi is None else int(hi)
+
+
+def parse_shard(spec):
+    """--shard I/N with 1 <= I <= N; ValueError otherwise."""
+    i, sep, n = spec.partition("/")
+    if not sep or not (i.isascii() and i.isdigit() and n.isascii() and n.isdigit()) or not 1 <= int(i) <= int(n):
+        raise ValueError(f"--shard {spec}: want I/N with 1 <= I <= N")
+    return int(i), int(n)
+
+
+def _check_r_args(args, command):
+    """--reads and --shard, from the arguments alone (before anything is loaded): the parsed
+    (a, b) or (i, n), or None."""
+    reads, shard = getattr(args, "reads", None), getattr(args, "shard", None)
+    if reads is not None and shard is not None:
+        _bad_args(f"{command}: --reads and --shard exclude each other")
+    try:
+        if reads is not None:
+            a, b = parse_reads(reads)
+            if getattr(args, "mate_out", None) is not None and (a % 2 == 0 or (b is not None and b % 2 == 1)):
+                _bad_args(f"{command}: --reads {reads} with --mate-out: whole pairs start at an odd read and end at an even one")
+            return ("reads", a, b)
+        if shard is not None:
+            return ("shard",) + parse_shard(shard)
+    except ValueError as e:
+        _bad_args(f"{command}: {e}")
+    return None
+
+
+def _place_range(args, command, asked):
+    """The asked --reads / --shard against the archive's block headers (host only): (first,
+    count) from 0 for decode_file, or None for an empty shard.  Status 2 for a range the
+    archive does not hold."""
+    import ntcomp_amd as nt
+    try:
+        info = nt.archive_info(args.input_path)
+    except nt.NtcError:
+        raise SystemExit(f"ntcomp: {command}: cannot read {args.input_path}")
+    total = info["n_reads"]
+    if asked[0] == "reads":
+        a, b = asked[1], asked[2] if asked[2] is not None else total
+        if a > total or b > total:
+            _bad_args(f"{command}: --reads {args.reads}: the archive holds {total} reads")
+        if getattr(args, "mate_out", None) is not None and b % 2:
+            _bad_args(f"{command}: --reads {args.reads} with --mate-out: the range ends inside a pair")
+        return a - 1, b - a + 1
+    lo, hi = nt.shard_blocks(asked[1], asked[2], info["n_blocks"])
+    first = sum(blk["reads"] for blk in info["blocks"][:lo])
+    count = sum(blk["reads"] for blk in info["blocks"][lo:hi])
+    if count and getattr(args, "mate_out", None) is not None and first % 2:
+        _bad_args(f"{command}: --shard {args.shard} with --mate-out: the slice starts inside a pair")
+    return (first, count) if count else None
+
+
 def _component_names(mask):
     return ",".join(n for c, n in enumerate(("seq", "sym", "qual", "name")) if mask >> c & 1) or "-"
 
@@ -331,8 +399,18 @@ def cmd_decode(args, verify=False):
     the --digest-file and no text copied off the device or written; one line on stdout."""
     command = "verify" if verify else "decode"
     _check_d_args(args, command, (args.exceptions, args.quality_file, args.name_file, args.input_path))
+    asked = _check_r_args(args, command)
     import ntcomp_amd as nt
     st = _Stats(args.stats)
+    r_args = {}
+    if asked is not None:  # placed from the block headers, before any GPU is opened
+        placed = _place_range(args, command, asked)
+        if placed is None:  # an empty slice: nothing to write
+            if verify:
+                print(f"verify: OK: 0 blocks of the archive's, 0 reads (--shard {args.shard} is empty)", flush=True)
+            st.report(command=command, reads=0, blocks=0)
+            return
+        r_args = dict(reads=placed)
     index = st.wrap("index_load", nt.Index.load)(args.index_prefix)
     ctxs = _open_gpus(index, _devices(args), st, args.contexts_per_gpu, decode_only=True)
     log("Verifying encoded data..." if verify else "Decoding encoded data...")
@@ -349,7 +427,7 @@ def cmd_decode(args, verify=False):
         res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, -1 if verify else out.fileno(),
                                                   threads=args.threads, blocks_per_batch=args.blocks_per_batch,
                                                   nx_path=args.exceptions, q_path=args.quality_file,
-                                                  n_path=args.name_file, d_path=args.digest_file, **p_args)
+                                                  n_path=args.name_file, d_path=args.digest_file, **p_args, **r_args)
     except nt.NtcError as e:
         bad = getattr(e, "bad_read", -1)
         raise SystemExit(f"ntcomp {command}: {e}" + (f" (read {bad + 1})" if e.code == 12 and bad is not None and bad >= 0
@@ -368,14 +446,39 @@ def cmd_decode(args, verify=False):
     if verify:
         d = res["d"]
         checked = sum(1 << c for c, k in enumerate(("blocks_seq", "blocks_sym", "blocks_qual", "blocks_name")) if d[k])
-        print(f"verify: OK: {d['sections']} blocks, {res['reads']} reads, checked {_component_names(checked)}, "
+        of = f" of {res['r']['blocks_total']}" if "r" in res else ""
+        print(f"verify: OK: {d['sections']}{of} blocks, {res['reads']} reads, checked {_component_names(checked)}, "
               f"not checkable {_component_names(d['not_checkable'])}", flush=True)
     st.report(command=command, gpus=len(ctxs), threads=res["threads"], reads=res["reads"], blocks=res["blocks"],
               pipeline_wall_s=round(res["wall_s"], 3),
               **({**{"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"},
                   "d_not_checkable": _component_names(res["d"]["not_checkable"])} if "d" in res else {}),
               **({"pairs": res["p"]["pairs"], "mate1_bytes": res["p"]["bytes1"], "mate2_bytes": res["p"]["bytes2"]}
-                 if "p" in res else {}))
+                 if "p" in res else {}),
+              **({"r_" + k: v for k, v in res["r"].items()} if "r" in res else {}))
+
+
+def cmd_info(args):
+    """`ntcomp info encoded.dat [--blocks]`: what the archive holds, from its block headers
+    alone (ntc_archive_info): no index, no GPU.  Status 1 when a block's headers are damaged."""
+    import ntcomp_amd as nt
+    try:
+        info = nt.archive_info(args.input_path)
+    except nt.NtcError:
+        raise SystemExit(f"ntcomp: info: cannot read {args.input_path}")
+    size = sum(b["bytes"] for b in info["blocks"])
+    bad = sum(b["bad"] for b in info["blocks"])
+    print(f"blocks {info['n_blocks']} reads {info['n_reads']} records {info['n_records']} bytes {size} "
+          f"trailing_bytes {info['tail_bytes']}" + (f" damaged_blocks {bad}" if bad else ""))
+    if args.blocks:
+        first = 1
+        for i, b in enumerate(info["blocks"]):
+            print(f"block {i} offset {b['offset']} bytes {b['bytes']} reads {b['reads']} records {b['records']} "
+                  + ("damaged" if b["bad"] else f"first_read {first}"))
+            first += b["reads"]
+    sys.stdout.flush()
+    if bad:
+        raise SystemExit(1)
 
 
 def main(argv=None):
@@ -474,6 +577,12 @@ def main(argv=None):
                         "block and the component")
     d.add_argument("--mate-out", metavar="R2.out",
                    help="the archive holds pairs: the mate-1 records go to stdout, the mate-2 records to R2.out")
+    r_help = ("only reads A-B of the archive, 1-based and inclusive as decode numbers them (seq.N); also A, A- and -B. "
+              "Only the blocks that hold them are read; the reads keep their numbers, names and qualities")
+    s_help = ("only the I-th of N contiguous slices of whole blocks; the N outputs concatenated in order are the full "
+              "decode (one process per GPU or node)")
+    d.add_argument("--reads", metavar="A-B", help=r_help)
+    d.add_argument("--shard", metavar="I/N", help=s_help)
     v = sub.add_parser("verify", help="Check encoded data against its digest file without writing the text")
     v.add_argument("input_path", help="File with encoded fastX data.")
     v.add_argument("-i", "--index", dest="index_prefix", required=True, help="Prefix for prebuilt <prefix>.sbwt and <prefix>.lcs")
@@ -488,6 +597,11 @@ def main(argv=None):
     v.add_argument("--quality-file", metavar="PATH", help="the side file of encode --qualities keep or bin8")
     v.add_argument("--name-file", metavar="PATH", help="the side file of encode --names keep or id")
     v.add_argument("--exceptions", metavar="PATH", help="the side file of encode --non-acgt keep")
+    v.add_argument("--reads", metavar="A-B", help=r_help + "; the touched blocks are checked whole")
+    v.add_argument("--shard", metavar="I/N", help=s_help)
+    n = sub.add_parser("info", help="What an encoded file holds, from its block headers (no index, no GPU)")
+    n.add_argument("input_path", help="File with encoded fastX data.")
+    n.add_argument("--blocks", action="store_true", help="one line per block")
     args = ap.parse_args(argv)
     if getattr(args, "threads", None) == 0:
         import ntcomp_amd as nt
@@ -500,6 +614,8 @@ def main(argv=None):
         cmd_decode(args)
     elif args.command == "verify":
         cmd_decode(args, verify=True)
+    elif args.command == "info":
+        cmd_info(args)
     else:
         ap.print_help()
     return 0

@@ -25,6 +25,7 @@
 #include "names_core.h"
 #include "digest_core.h"
 #include "pair_core.h"
+#include "window_core.h"
 #include "ntc_internal.h"
 
 using namespace ntc;
@@ -181,6 +182,10 @@ struct ntc_ctx {
     int paired = 0;
     bool pair_valid = false;
     uint64_t pair_first = 0;
+    // the text window of the next ntc_decode_fasta / _unpacked (ntc_decode_set_window): pending
+    // like the side data above, gone after that call whether it succeeds or fails
+    bool tw_has_pending = false;
+    uint64_t tw_first = 0, tw_count = 0;
     FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
@@ -2691,9 +2696,32 @@ uint64_t text_bytes(const ntc_ctx *ctx, uint64_t n_reads, uint64_t n_bases, uint
     return fasta_bytes(n_reads, n_bases, first_id) + q;
 }
 
-// walk + FASTA text of records already in HBM (d_recs), text D2H into out (need bytes)
+// The pending text window leaves the context with the call that takes it: a size query (keep)
+// alone leaves it for the call it sizes.
+struct TextWindow {
+    ntc_ctx *ctx;
+    uint64_t first = 0, count = 0;  // count 0: no window
+    bool kept = false;
+    explicit TextWindow(ntc_ctx *c) : ctx(c) {
+        if (c->tw_has_pending) first = c->tw_first, count = c->tw_count;
+    }
+    ~TextWindow() {
+        if (!kept) ctx->tw_has_pending = false;
+    }
+    void keep() { kept = true; }
+    // the request against the batch it met
+    int check(uint64_t n_reads) const {
+        if (!count || w_valid(first, count, n_reads, ctx->paired != 0)) return NTC_OK;
+        const bool inside = first < n_reads && count <= n_reads - first;  // (then it cuts a pair)
+        return set_err(ctx, NTC_ERR_INVALID_ARG, inside ? "paired: a window's first read and count must be even (whole pairs)"
+                                                        : "the window reaches past the batch's reads");
+    }
+};
+
+// walk + FASTA text of records already in HBM (d_recs), text D2H into out (need bytes; with a
+// window w only the window's bytes, which *out_len then reports)
 int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint64_t n_reads, uint64_t n_bases,
-                     uint64_t first_id, uint8_t *out, uint64_t need) {
+                     uint64_t first_id, uint8_t *out, uint64_t need, const TextWindow &w, uint64_t *out_len) {
     void *d_bases, *d_offs, *d_scan, *d_out;
     int rc;
     if ((rc = ensure(ctx, WS_FA_BASES, n_bases + 64, &d_bases))) return rc;
@@ -2717,7 +2745,9 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     const bool fastq = q_take_pending(ctx, qm, qp);  // (all pending lists leave the context here)
     const bool named = n_take_pending(ctx, nm, np);
     const bool digests = dg_take_pending(ctx, dm);
-    if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= n_reads)
+    const bool has_nx = nx_take_pending(ctx, nx, nx_sub);
+    if ((rc = w.check(n_reads))) return rc;  // (after the lists: a refused window leaves nothing pending either)
+    if (has_nx && nx.back().read >= n_reads)
         return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
     if (fastq) {
         uint64_t r = 0;
@@ -2774,14 +2804,19 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     uint64_t *sizes = (uint64_t *)d_scan, *out_offs = sizes + (n_reads + 1), *tmp = out_offs + (n_reads + 1);
     if (named)
         launch_named_text((const uint8_t *)d_bases, d_quals, (const uint64_t *)d_offs, d_names, d_name_off, n_reads,
-                          ctx->d_status, sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
+                          ctx->d_status, sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream, w.first, w.count);
     else if (fastq)
         launch_fastq_text((const uint8_t *)d_bases, d_quals, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status,
-                          sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
+                          sizes, out_offs, tmp, (uint8_t *)d_out, need, ctx->stream, w.first, w.count);
     else
         launch_fasta((const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, first_id, ctx->d_status, sizes,
-                     out_offs, tmp, (uint8_t *)d_out, need, ctx->stream);
+                     out_offs, tmp, (uint8_t *)d_out, need, ctx->stream, w.first, w.count);
     HIP_TRY(ctx, hipGetLastError());
+    if (w.count) {  // the window's bytes: the scan's total, 0 when the call failed on the device
+        ctx->h_box[13] = 0;  // (no kernel of an earlier call writes it: each ends synchronised)
+        launch_window_box(out_offs + n_reads, ctx->h_box, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     if (split) {
         PairSplitArgs p{};
         p.text = (const uint8_t *)d_out;
@@ -2799,7 +2834,13 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
         HIP_TRY(ctx, hipGetLastError());
         d_out = d_split;
     }
-    if (!ctx->discard_text) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t copy = need;
+    if (w.count) {  // the device knows the window's bytes: wait for them, copy only them
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const uint64_t got = ((volatile uint64_t *)ctx->h_box)[13];
+        *out_len = copy = std::min(need, got);
+    }
+    if (!ctx->discard_text && copy) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, copy, hipMemcpyDeviceToHost, ctx->stream));
     uint64_t nr = 0, nb = 0;
     rc = ntc_decode_status(ctx, &nr, &nb);  // synchronises
     if (digests) rc = dgd_verdict(ctx, rc);
@@ -2845,20 +2886,26 @@ int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
     ctx->pair_valid = false;
+    TextWindow w(ctx);
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->paired && (n_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, n_reads, n_bases, first_id);
     *out_len = need;
-    if (need > out_capacity && !ctx->discard_text)
+    if (need > out_capacity && !ctx->discard_text) {
+        w.keep();  // (a size query: the window waits for the call it sizes)
         return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+    }
     ctx->pair_valid = ctx->paired && !ctx->discard_text;  // (the parts stay empty unless the call succeeds)
     ctx->pair_first = 0;
-    if (n_recs == 0) return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
+    if (n_recs == 0) {
+        if (const int wrc = w.check(n_reads)) return wrc;
+        return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
+    }
     void *d_recs;
     int rc;
     if ((rc = ensure(ctx, WS_STAGE_RECS, n_recs * 8, &d_recs))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d_recs, recs, n_recs * 8, hipMemcpyHostToDevice, ctx->stream));
-    return decode_fasta_dev(ctx, (const uint64_t *)d_recs, n_recs, n_reads, n_bases, first_id, out, need);
+    return decode_fasta_dev(ctx, (const uint64_t *)d_recs, n_recs, n_reads, n_bases, first_id, out, need, w, out_len);
 }
 
 int ntc_unpack_streams(ntc_ctx *ctx, const uint8_t *payload, uint64_t payload_bytes, const ntc_block_meta *metas,
@@ -2988,18 +3035,37 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
     ctx->pair_valid = false;
+    TextWindow w(ctx);
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->paired && (ctx->unp_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, ctx->unp_reads, ctx->unp_bases, first_id);
     *out_len = need;  // (a size query: out_capacity 0)
     if (!ctx->discard_text) {
-        if (need > out_capacity) return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+        if (need > out_capacity) {
+            w.keep();  // (the window waits for the call the query sizes)
+            return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+        }
         if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     }
     ctx->pair_valid = ctx->paired && !ctx->discard_text;
     ctx->pair_first = 0;
-    if (ctx->unp_recs == 0) return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
-    return decode_fasta_dev(ctx, ctx->unp_d_recs, ctx->unp_recs, ctx->unp_reads, ctx->unp_bases, first_id, out, need);
+    if (ctx->unp_recs == 0) {
+        if (const int wrc = w.check(ctx->unp_reads)) return wrc;
+        return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
+    }
+    return decode_fasta_dev(ctx, ctx->unp_d_recs, ctx->unp_recs, ctx->unp_reads, ctx->unp_bases, first_id, out, need, w,
+                            out_len);
+}
+
+int ntc_decode_set_window(ntc_ctx *ctx, uint64_t first, uint64_t count) {
+    if (!ctx) return NTC_ERR_INVALID_ARG;
+    ctx->tw_has_pending = false;
+    // (the batch's reads are only known to the call that takes it: TextWindow::check)
+    if (count == 0 || first + count < first) return set_err(ctx, NTC_ERR_INVALID_ARG, "an empty window");
+    ctx->tw_first = first;
+    ctx->tw_count = count;
+    ctx->tw_has_pending = true;
+    return NTC_OK;
 }
 
 int ntc_decode_pair_split(ntc_ctx *ctx, uint64_t *first_bytes) {
@@ -3440,6 +3506,7 @@ struct NxHookFill {
         ntc::g_p_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "paired", mode); };
         ntc::g_p_hooks.encode_paired = ntc_encode_pack_fastq_paired;
         ntc::g_p_hooks.pair_split = ntc_decode_pair_split;
+        ntc::g_w_hooks.decode_set_window = ntc_decode_set_window;
         ntc::g_q_hooks.set_mode = [](ntc_ctx *ctx, int mode) { return ntc_ctx_set_option(ctx, "qualities", mode); };
         ntc::g_q_hooks.encode_qualities = ntc_encode_qualities;
         ntc::g_q_hooks.get_coder = [](ntc_ctx *ctx) {

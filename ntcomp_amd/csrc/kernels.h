@@ -199,7 +199,14 @@ void launch_unpack(const UnpackDev &d, hipStream_t s);
 uint64_t unpack_seg_words(uint64_t n_blocks, uint64_t max_recs);
 void launch_fasta(const uint8_t *d_bases, const uint64_t *d_offs, uint64_t n, uint64_t first_id,
                   const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs, uint64_t *tmp, uint8_t *out,
-                  uint64_t out_cap, hipStream_t s);
+                  uint64_t out_cap, hipStream_t s, uint64_t w_first = 0, uint64_t w_count = 0);
+// A window on the formatters (window.hip, window_core.h): w_count != 0 in launch_fasta,
+// launch_fastq_text and launch_named_text formats only reads [w_first, w_first + w_count) of
+// the n (a valid window, w_valid), packed at the head of out; out_offs[n] = their bytes.
+// launch_window_sizes zeroes the sizes outside the window (the formatters call it before their
+// scan); launch_window_box: box[13] = *total.  Without a window neither is launched.
+void launch_window_sizes(uint64_t *sizes, uint64_t n, uint64_t first, uint64_t count, hipStream_t s);
+void launch_window_box(const uint64_t *total, uint64_t *box, hipStream_t s);
 
 // plain FASTQ text of n_reads whole 4-line records -> normalised bases + read offsets
 // (fastq.hip).  tile_cnt: fastq_tiles(n_raw) words, tile_base: tiles + 1 (its last word =
@@ -403,7 +410,8 @@ void launch_quality_rans_decode(const QRDecArgs &a, hipStream_t s);
 // launch_fasta's FASTQ twin: "@seq.{first_id + r}\n{read r}\n+\n{qualities r}\n"
 void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t n,
                        uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,
-                       uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s);
+                       uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s, uint64_t w_first = 0,
+                       uint64_t w_count = 0);
 
 // Read names (names.hip, names_core.h).  Encode side, after launch_fastq_parse over the same
 // text: start / len / mid: n_reads + 1 words each, ps: two columns of n_reads bytes (pre,
@@ -456,7 +464,8 @@ void launch_names_expand(const NDecArgs &a, hipStream_t s);
 // "@{name r}\n{read r}\n+\n{qualities r}\n"
 void launch_named_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, const uint8_t *d_names,
                        const uint64_t *d_name_off, uint64_t n, const unsigned long long *d_status, uint64_t *sizes,
-                       uint64_t *out_offs, uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s);
+                       uint64_t *out_offs, uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s,
+                       uint64_t w_first = 0, uint64_t w_count = 0);
 
 // Per-block content digests (digest.hip, digest_core.h).  A table entry is the public
 // ntc_digest_meta: d[c] is the digest of component c (seq, sym, qual, name).

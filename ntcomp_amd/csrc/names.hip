@@ -20,6 +20,7 @@
 
 #include "kernels.h"
 #include "names_core.h"
+#include "window_core.h"
 
 namespace ntc {
 
@@ -260,6 +261,9 @@ __global__ __launch_bounds__(256) void k_named_sizes(const uint64_t *offs, const
     sizes[r] = *status != ~0ull ? 0 : fastq ? nlen + 2 * len + 6 : nlen + len + 3;
 }
 
+// W: the call has a window (window.hip zeroed the sizes outside it): reads without a record are
+// skipped.  W = false is the kernel as it was.
+template <bool W>
 __global__ __launch_bounds__(256) void k_named(const uint8_t *bases, const uint8_t *quals, const uint64_t *offs,
                                                const uint8_t *names, const uint64_t *name_off, uint64_t n,
                                                const uint64_t *out_offs, uint64_t out_cap, uint8_t *out) {
@@ -268,6 +272,7 @@ __global__ __launch_bounds__(256) void k_named(const uint8_t *bases, const uint8
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64);
     const uint64_t o0 = offs[0];
     for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); r < n; r += waves) {
+        if (W && w_skips(out_offs[r], out_offs[r + 1])) continue;
         const uint64_t b = offs[r] - o0, len = offs[r + 1] - offs[r];
         const uint64_t nb = name_off[r], nlen = name_off[r + 1] - nb;
         uint64_t o = out_offs[r];
@@ -320,14 +325,16 @@ void launch_names_expand(const NDecArgs &a, hipStream_t s) {
 
 void launch_named_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, const uint8_t *d_names,
                        const uint64_t *d_name_off, uint64_t n, const unsigned long long *d_status, uint64_t *sizes,
-                       uint64_t *out_offs, uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s) {
+                       uint64_t *out_offs, uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s, uint64_t w_first,
+                       uint64_t w_count) {
     if (!n) return;
     hipLaunchKernelGGL(k_named_sizes, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d_offs, d_name_off, n,
                        d_quals ? 1u : 0u, d_status, sizes);
+    if (w_count) launch_window_sizes(sizes, n, w_first, w_count, s);
     scan_excl_u64(sizes, n, out_offs, tmp, s);
     const uint64_t blocks = std::min<uint64_t>((n + 3) / 4, 65536);
-    hipLaunchKernelGGL(k_named, dim3((uint32_t)blocks), dim3(256), 0, s, d_bases, d_quals, d_offs, d_names, d_name_off,
-                       n, out_offs, out_cap, out);
+    hipLaunchKernelGGL(w_count ? k_named<true> : k_named<false>, dim3((uint32_t)blocks), dim3(256), 0, s, d_bases, d_quals,
+                       d_offs, d_names, d_name_off, n, out_offs, out_cap, out);
 }
 
 }  // namespace ntc

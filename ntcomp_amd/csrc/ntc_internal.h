@@ -173,6 +173,12 @@ struct PHooks {
     int (*pair_split)(::ntc_ctx *ctx, uint64_t *first_bytes);  // ntc_decode_pair_split
 };
 extern PHooks g_p_hooks;
+// ... and for a range of reads: with the table null, ntc_decode_file_ex5 answers
+// NTC_ERR_UNSUPPORTED to a range that does not start and end at block boundaries.
+struct WHooks {
+    int (*decode_set_window)(::ntc_ctx *ctx, uint64_t first, uint64_t count);  // ntc_decode_set_window
+};
+extern WHooks g_w_hooks;
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

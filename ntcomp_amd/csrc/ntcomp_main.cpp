@@ -82,14 +82,14 @@ bool takes_value(const std::string &o) {
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
                               "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
                               "--qualities", "--quality-file", "--quality-coder", "--names", "--name-file",
-                              "--digest-file", "--mate-file", "--mate-check", "--mate-out"};
+                              "--digest-file", "--mate-file", "--mate-check", "--mate-out", "--reads", "--shard"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
 }
 
 bool is_switch(const std::string &o) {
-    static const char *v[] = {"-d", "--dedup-batches", "--verbose", "--stats", "--host-parse", "--interleaved"};
+    static const char *v[] = {"-d", "--dedup-batches", "--verbose", "--stats", "--host-parse", "--interleaved", "--blocks"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -405,6 +405,110 @@ bool host_unpack_on() {
     return h && std::atoi(h) > 0;
 }
 
+// all of s is decimal digits (at least one, at most 18: no overflow)
+bool all_digits(const std::string &s) {
+    if (s.empty() || s.size() > 18) return false;
+    for (const char c : s)
+        if (c < '0' || c > '9') return false;
+    return true;
+}
+
+// --reads A-B, 1-based and inclusive as decode prints seq.N; also A, A- and -B.  *b = 0: to the
+// last read.  false: malformed.
+bool parse_reads(const std::string &spec, uint64_t *a, uint64_t *b) {
+    const size_t dash = spec.find('-');
+    const std::string lo = spec.substr(0, dash), hi = dash == std::string::npos ? lo : spec.substr(dash + 1);
+    if (lo.empty() && hi.empty()) return false;
+    if ((!lo.empty() && !all_digits(lo)) || (!hi.empty() && !all_digits(hi))) return false;
+    *a = lo.empty() ? 1 : std::strtoull(lo.c_str(), nullptr, 10);
+    *b = hi.empty() ? 0 : std::strtoull(hi.c_str(), nullptr, 10);
+    return *a >= 1 && (hi.empty() || *b >= *a);
+}
+
+// --shard I/N with 1 <= I <= N
+bool parse_shard(const std::string &spec, uint64_t *i, uint64_t *n) {
+    const size_t slash = spec.find('/');
+    if (slash == std::string::npos || !all_digits(spec.substr(0, slash)) || !all_digits(spec.substr(slash + 1))) return false;
+    *i = std::strtoull(spec.c_str(), nullptr, 10);
+    *n = std::strtoull(spec.c_str() + slash + 1, nullptr, 10);
+    return *i >= 1 && *i <= *n;
+}
+
+// what --reads / --shard ask, checked from the arguments alone, then placed against the block
+// headers (host only): reads [first, first + count) from 0
+struct RangeAsk {
+    bool reads = false, shard = false;
+    uint64_t a = 0, b = 0, i = 0, n = 0;
+    std::string spec;
+};
+RangeAsk range_args(const Args &a, const char *cmd) {
+    RangeAsk r;
+    if (a.flag("--reads") && a.flag("--shard")) bad_args(std::string(cmd) + ": --reads and --shard exclude each other");
+    if (a.flag("--reads")) {
+        r.reads = true;
+        r.spec = a.get("--reads", nullptr, "");
+        if (!parse_reads(r.spec, &r.a, &r.b))
+            bad_args(std::string(cmd) + ": --reads " + r.spec + ": want A-B, A, A- or -B (1-based, inclusive, 1 <= A <= B)");
+        if (a.flag("--mate-out") && (r.a % 2 == 0 || (r.b && r.b % 2 == 1)))
+            bad_args(std::string(cmd) + ": --reads " + r.spec + " with --mate-out: whole pairs start at an odd read and end at an even one");
+    }
+    if (a.flag("--shard")) {
+        r.shard = true;
+        r.spec = a.get("--shard", nullptr, "");
+        if (!parse_shard(r.spec, &r.i, &r.n)) bad_args(std::string(cmd) + ": --shard " + r.spec + ": want I/N with 1 <= I <= N");
+    }
+    return r;
+}
+// false: an empty slice
+bool place_range(const RangeAsk &r, const Args &a, const char *cmd, uint64_t *first, uint64_t *count) {
+    ntc_archive_block *blocks = nullptr;
+    uint64_t nb = 0, total = 0;
+    if (ntc_archive_info(a.pos[0].c_str(), &blocks, &nb, &total, nullptr, nullptr)) die(std::string(cmd) + ": cannot read " + a.pos[0]);
+    if (r.reads) {
+        ntc_buffer_free(blocks);
+        const uint64_t b = r.b ? r.b : total;
+        if (r.a > total || b > total)
+            bad_args(std::string(cmd) + ": --reads " + r.spec + ": the archive holds " + std::to_string(total) + " reads");
+        if (a.flag("--mate-out") && b % 2) bad_args(std::string(cmd) + ": --reads " + r.spec + " with --mate-out: the range ends inside a pair");
+        *first = r.a - 1;
+        *count = b - r.a + 1;
+        return true;
+    }
+    const uint64_t lo = (r.i - 1) * nb / r.n, hi = r.i * nb / r.n;
+    *first = *count = 0;
+    for (uint64_t k = 0; k < hi; k++) (k < lo ? *first : *count) += blocks[k].reads;
+    ntc_buffer_free(blocks);
+    if (*count && a.flag("--mate-out") && *first % 2)
+        bad_args(std::string(cmd) + ": --shard " + r.spec + " with --mate-out: the slice starts inside a pair");
+    return *count != 0;
+}
+
+// `ntcomp info encoded.dat [--blocks]`: what the archive holds, from its block headers alone;
+// no index, no GPU.  Status 1 when a block's headers are damaged.
+int cmd_info(const Args &a) {
+    if (a.pos.size() != 1) die("info: one input file");
+    ntc_archive_block *blocks = nullptr;
+    uint64_t nb = 0, reads = 0, recs = 0, tail = 0, bytes = 0, bad = 0;
+    if (ntc_archive_info(a.pos[0].c_str(), &blocks, &nb, &reads, &recs, &tail)) die("info: cannot read " + a.pos[0]);
+    for (uint64_t i = 0; i < nb; i++) bytes += blocks[i].bytes, bad += blocks[i].bad;
+    std::printf("blocks %llu reads %llu records %llu bytes %llu trailing_bytes %llu", (unsigned long long)nb,
+                (unsigned long long)reads, (unsigned long long)recs, (unsigned long long)bytes, (unsigned long long)tail);
+    if (bad) std::printf(" damaged_blocks %llu", (unsigned long long)bad);
+    std::printf("\n");
+    uint64_t first = 1;
+    for (uint64_t i = 0; a.flag("--blocks") && i < nb; i++) {
+        std::printf("block %llu offset %llu bytes %llu reads %llu records %llu ", (unsigned long long)i,
+                    (unsigned long long)blocks[i].offset, (unsigned long long)blocks[i].bytes,
+                    (unsigned long long)blocks[i].reads, (unsigned long long)blocks[i].records);
+        if (blocks[i].bad) std::printf("damaged\n");
+        else std::printf("first_read %llu\n", (unsigned long long)first);
+        first += blocks[i].reads;
+    }
+    ntc_buffer_free(blocks);
+    std::fflush(stdout);
+    return bad ? 1 : 0;
+}
+
 // verify: decode with out_fd -1 -- nothing is copied off the device or written; one line on stdout
 int cmd_decode(const Args &a, bool verify = false) {
     const auto t0 = Clock::now();
@@ -418,7 +522,14 @@ int cmd_decode(const Args &a, bool verify = false) {
     const std::string mate_out = a.get("--mate-out", nullptr, "");
     if (verify && a.flag("--mate-out")) bad_args("verify: writes no text: not with --mate-out");
     if (a.flag("--mate-out") && mate_out.empty()) bad_args("decode: --mate-out needs a path");
+    const RangeAsk ask = range_args(a, cmd);
     if (prefix.empty()) die(std::string(cmd) + ": -i/--index is required");
+    const bool ranged = ask.reads || ask.shard;
+    uint64_t r_first = 0, r_count = 0;
+    if (ranged && !place_range(ask, a, cmd, &r_first, &r_count)) {  // an empty slice: nothing to write
+        if (verify) std::printf("verify: OK: 0 blocks of the archive's, 0 reads (--shard %s is empty)\n", ask.spec.c_str());
+        return 0;
+    }
     ntc_index_host *ix = nullptr;
     if (ntc_index_load(prefix.c_str(), &ix)) die("cannot load index " + prefix);
     const double t_load = since(t0);
@@ -444,8 +555,12 @@ int cmd_decode(const Args &a, bool verify = false) {
     const ntc_file_opts4 fo4{(uint32_t)sizeof(ntc_file_opts4), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1, fo3.n_path, 0, -1,
                              d_path.empty() ? nullptr : d_path.c_str(), 2, nullptr, fd2};
     ntc_p_stats pst{};
+    const ntc_file_opts5 fo5{(uint32_t)sizeof(ntc_file_opts5), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1, fo3.n_path, 0, -1,
+                             fo4.d_path, fd2 >= 0 ? 2 : 0, nullptr, fd2, r_first, r_count};
+    ntc_r_stats rst{};
     std::fflush(stdout);
-    const int rc = fd2 >= 0 ? ntc_decode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &dst, &pst)
+    const int rc = ranged ? ntc_decode_file_ex5(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo5, &o, &st, &dst, &pst, &rst)
+                   : fd2 >= 0 ? ntc_decode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &dst, &pst)
                    : !d_path.empty() ? ntc_decode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo3, &o, &st, &dst)
                    : !n_path.empty() ? ntc_decode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st)
                    : !q_path.empty() ? ntc_decode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st)
@@ -460,13 +575,14 @@ int cmd_decode(const Args &a, bool verify = false) {
         if (rc == NTC_ERR_DIGEST && st.bad_read >= 0) m += " (read " + std::to_string(st.bad_read + 1) + ")";
         die(m);
     }
+    const std::string of = ranged ? " of " + std::to_string(rst.blocks_total) : "";
     if (verify)
-        std::printf("verify: OK: %llu blocks, %llu reads, checked %s, not checkable %s\n", (unsigned long long)dst.sections,
-                    (unsigned long long)st.reads,
+        std::printf("verify: OK: %llu%s blocks, %llu reads, checked %s, not checkable %s\n", (unsigned long long)dst.sections,
+                    of.c_str(), (unsigned long long)st.reads,
                     component_names((dst.blocks_seq ? 1u : 0) | (dst.blocks_sym ? 2u : 0) | (dst.blocks_qual ? 4u : 0) |
                                     (dst.blocks_name ? 8u : 0)).c_str(),
                     component_names(dst.not_checkable).c_str());
-    char djson[560] = "";
+    char djson[960] = "";
     if (fd2 >= 0)
         std::snprintf(djson, 240, "\"pairs\": %llu, \"mate1_bytes\": %llu, \"mate2_bytes\": %llu, ",
                       (unsigned long long)pst.pairs, (unsigned long long)pst.bytes1, (unsigned long long)pst.bytes2);
@@ -476,6 +592,13 @@ int cmd_decode(const Args &a, bool verify = false) {
                       (unsigned long long)dst.sections, (unsigned long long)dst.blocks_seq, (unsigned long long)dst.blocks_sym,
                       (unsigned long long)dst.blocks_qual, (unsigned long long)dst.blocks_name,
                       component_names(dst.not_checkable).c_str());
+    if (ranged)
+        std::snprintf(djson + std::strlen(djson), 400, "\"r_blocks_total\": %llu, \"r_reads_total\": %llu, \"r_first_block\": %llu, "
+                                            "\"r_blocks_read\": %llu, \"r_reads_written\": %llu, \"r_head_skipped\": %llu, "
+                                            "\"r_tail_skipped\": %llu, ",
+                      (unsigned long long)rst.blocks_total, (unsigned long long)rst.reads_total, (unsigned long long)rst.first_block,
+                      (unsigned long long)rst.blocks_read, (unsigned long long)rst.reads_written,
+                      (unsigned long long)rst.head_skipped, (unsigned long long)rst.tail_skipped);
     if (st.dropped_blocks)  // the reference's `while let Ok(..) = decode_block` just ends here (main.rs:202)
         std::fprintf(stderr, "warning: %s; %llu block(s) not decoded\n", st.error,
                      (unsigned long long)st.dropped_blocks);
@@ -594,9 +717,11 @@ void usage(FILE *f) {
                  "                     FILE > encoded.dat\n"
                  "                     [--mate-file R2 | --interleaved] [--mate-check ids|off]\n"
                  "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH]\n"
-                 "                     [--digest-file PATH] [--mate-out R2.out] FILE > out.fasta\n"
+                 "                     [--digest-file PATH] [--mate-out R2.out] [--reads A-B | --shard I/N]\n"
+                 "                     FILE > out.fasta\n"
                  "       ntcomp verify -i PREFIX --digest-file PATH [--exceptions PATH] [--quality-file PATH]\n"
-                 "                     [--name-file PATH] FILE\n\n"
+                 "                     [--name-file PATH] [--reads A-B | --shard I/N] FILE\n"
+                 "       ntcomp info [--blocks] FILE\n\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
                  "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
                  "                     the replaced symbols to the --exceptions file (lossless)\n"
@@ -623,7 +748,13 @@ void usage(FILE *f) {
                  "  --interleaved      encode: FILE already alternates the mates\n"
                  "  --mate-check ids|off  encode: compare the mates' ids (cut at the first blank, /1 and /2 stripped)\n"
                  "                     on the GPU (default), or not\n"
-                 "  --mate-out R2.out  decode: the archive holds pairs: mate-1 records to stdout, mate-2 records to R2.out\n");
+                 "  --mate-out R2.out  decode: the archive holds pairs: mate-1 records to stdout, mate-2 records to R2.out\n"
+                 "  --reads A-B        decode, verify: only reads A-B of the archive, 1-based and inclusive as decode\n"
+                 "                     numbers them (seq.N); also A, A- and -B.  Only the blocks that hold them are read;\n"
+                 "                     the reads keep their numbers, names and qualities\n"
+                 "  --shard I/N        decode, verify: only the I-th of N contiguous slices of whole blocks; the N outputs\n"
+                 "                     concatenated in order are the full decode (one process per GPU or node)\n"
+                 "  --blocks           info: one line per block\n");
 }
 
 }  // namespace
@@ -649,6 +780,7 @@ int main(int argc, char **argv) {
     }
     const Args a = parse(argc, argv, 2);
     if (cmd == "build") return cmd_build(a);
+    if (cmd == "info") return cmd_info(a);
     if (cmd == "encode" || cmd == "decode" || cmd == "verify") {
         const int rc = cmd == "encode" ? cmd_encode(a) : cmd_decode(a, cmd == "verify");
         // The output is complete and every device call has returned.  Free the contexts

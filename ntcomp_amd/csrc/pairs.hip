@@ -19,6 +19,7 @@
 
 #include "kernels.h"
 #include "pair_core.h"
+#include "window_core.h"
 
 namespace ntc {
 
@@ -146,6 +147,7 @@ __global__ __launch_bounds__(256) void k_ps_copy(PairSplitArgs a) {
     const uint64_t waves = (uint64_t)gridDim.x * 4;
     for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += waves) {
         const uint64_t b = a.out_offs[r], len = a.out_offs[r + 1] - b;
+        if (w_skips(b, b + len)) continue;  // a read outside the call's window has no record
         const uint8_t *src = a.text + b;
         uint8_t *dst = a.out + p_split_at(r, a.o1, a.o2, a.n_pairs);
         for (uint64_t i = lane; i < len; i += 64) dst[i] = src[i];

@@ -59,9 +59,9 @@
 namespace ntc {
 namespace pipe {
 
-// Everything the twelve entry points (ntc_{en,de}code_file, _nx, _ex, _ex2, _ex3, _ex4) can
-// say.  An entry point that lacks a field leaves it at its "none" value: mode 0, descriptor -1,
-// path null.
+// Everything the thirteen entry points (ntc_{en,de}code_file, _nx, _ex, _ex2, _ex3, _ex4 and
+// ntc_decode_file_ex5) can say.  An entry point that lacks a field leaves it at its "none"
+// value: mode 0, descriptor -1, path null.
 struct FileJob {
     ntc_ctx *const *ctxs;
     int n_ctx;
@@ -73,6 +73,7 @@ struct FileJob {
                       nullptr, -1};
     bool has_policy = false;   // false (ntc_encode_file): the contexts' policy as it is, no side file
     bool may_discard = false;  // decode _ex3 / _ex4: out_fd -1 runs everything but the text's copy and write
+    uint64_t read_first = 0, read_count = 0;  // decode _ex5: the range of reads, count 0 = the whole file
     FileJob(ntc_ctx *const *c, int n, const char *in, int out, const ntc_pipeline_opts *o)
         : ctxs(c), n_ctx(n), in_path(in), out_fd(out), opts(o) {}
     // the fields of ntc_file_opts, ntc_file_opts2 and ntc_file_opts3 (the same names in each)
@@ -101,6 +102,7 @@ struct FileStats {
     ntc_n_stats *n = nullptr;
     ntc_d_stats *d = nullptr;
     ntc_p_stats *p = nullptr;
+    ntc_r_stats *r = nullptr;
 };
 int encode_file(const FileJob &job, const FileStats &out);
 int decode_file(const FileJob &job, const FileStats &out);
@@ -182,6 +184,7 @@ QHooks g_q_hooks = {nullptr, nullptr, nullptr, nullptr};
 NHooks g_n_hooks = {nullptr, nullptr, nullptr};
 DHooks g_d_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 PHooks g_p_hooks = {nullptr, nullptr, nullptr};
+WHooks g_w_hooks = {nullptr};
 }
 
 namespace {
@@ -1440,6 +1443,7 @@ namespace {
 struct DBlock {
     uint64_t a, len;   // byte range of the block
     uint64_t n_recs;   // records (the flag stream's num_u64)
+    uint64_t n_reads;  // reads (stream 0's num_records)
     uint64_t pay;      // bytes of its four inflated streams (8 x encoded_size each)
     bool bad;          // a header that cannot describe its gzip stream: damaged, never sized
 };
@@ -1455,6 +1459,7 @@ struct DSlot {  // one batch in flight
     uint64_t batch = ~0ULL;  // batch held, ~0 = free
     uint64_t first_block = 0, n_blocks = 0;
     uint64_t n_recs = 0, n_reads = 0, n_bases = 0, text_len = 0;
+    uint64_t n_out = 0;      // reads in the text: n_reads, fewer where a range cuts the batch
     uint64_t first_len = 0;  // pairs: the bytes of the mate-1 part, at the head of text
     uint64_t first_id = 0;
     uint64_t finished = 0;   // blocks of this batch unzipped or found damaged
@@ -1545,7 +1550,7 @@ std::vector<DBlock> scan_extents(const uint8_t *data, uint64_t fsize) {
                                          (uint64_t)data[p + 3] << 24; };
     std::vector<DBlock> blocks;
     for (uint64_t pos = 32; pos < fsize;) {  // after the 32-byte file header (main.rs:196-198)
-        uint64_t p = pos, nrec = 0, pay = 0;
+        uint64_t p = pos, nrec = 0, nreads = 0, pay = 0;
         bool whole = true, bad = false;
         for (int s = 0; s < 4 && whole; s++) {
             if (p + 32 > fsize) {
@@ -1553,6 +1558,7 @@ std::vector<DBlock> scan_extents(const uint8_t *data, uint64_t fsize) {
                 break;
             }
             const uint64_t bs = le32(p), enc = le32(p + 12);
+            if (s == 0) nreads = le32(p + 4);
             if (s == 2) nrec = le32(p + 8);
             if (bs < 18 || p + 32 + bs > fsize || le32(p + 32 + bs - 4) != ((8 * enc) & 0xFFFFFFFFULL) ||
                 8 * enc > 1032 * bs || (s == 2 && nrec > 64 * enc))
@@ -1563,7 +1569,7 @@ std::vector<DBlock> scan_extents(const uint8_t *data, uint64_t fsize) {
         }
         if (!whole) break;
         // a bad block is sized as nothing; the unzip pool reports it damaged
-        blocks.push_back(bad ? DBlock{pos, p - pos, 0, 0, true} : DBlock{pos, p - pos, nrec, pay, false});
+        blocks.push_back(bad ? DBlock{pos, p - pos, 0, 0, 0, true} : DBlock{pos, p - pos, nrec, nreads, pay, false});
         pos = p;
     }
     return blocks;
@@ -1583,7 +1589,11 @@ struct Decoder {
     SideFile<ntc_digest_meta> df;  // the expected digests
     const uint8_t *data = nullptr;
     uint64_t fsize = 0;
-    std::vector<DBlock> blocks;
+    std::vector<DBlock> blocks;  // the blocks to decode: all of the file, or those a range touches
+    // a range of reads (ranged): blocks[0] is block blk_base of the file and of every side file;
+    // head_skip / tail_skip reads of the first / last batch stay out of the text
+    bool ranged = false;
+    uint64_t blk_base = 0, head_skip = 0, tail_skip = 0;
     uint64_t bpb = 0, b0n = 0, n_batches = 0;
     int NB = 0;
     bool gpu_unpack = true;
@@ -1627,6 +1637,7 @@ struct Decoder {
         sh.fail(rc, std::string("decode: ") + ntc_last_error(ctxs[c]));
         return false;
     }
+    std::string place_range(uint64_t first, uint64_t count, ntc_r_stats &R);
     bool ensure_pinned(void **p, uint64_t *cap, uint64_t need);
     void prepin_first_batches();
     void assign_ahead();
@@ -1640,6 +1651,71 @@ struct Decoder {
     void unzip_worker();
     void write_text();
 };
+
+// Reads [first, first + count) of the file (blocks = all of its blocks, the side files loaded):
+// keeps the blocks that hold them and sets the numbering's start and the reads to leave out at
+// both ends; R gets the placement.  Returns why not, or "": "range: ..." a request the archive
+// cannot serve (NTC_ERR_INVALID_ARG), "build: ..." a build without the window, anything else a
+// file that cannot be trusted for it (NTC_ERR_FORMAT).  Only metadata is read.
+std::string Decoder::place_range(uint64_t first, uint64_t count, ntc_r_stats &R) {
+    char buf[200];
+    uint64_t known = 0;  // reads of the blocks before the first bad one: only those have numbers
+    uint64_t first_bad = blocks.size();
+    for (uint64_t i = 0; i < blocks.size(); i++) {
+        if (blocks[i].bad) {
+            first_bad = i;
+            break;
+        }
+        known += blocks[i].n_reads;
+    }
+    if (first >= R.reads_total || count > R.reads_total - first) {
+        std::snprintf(buf, sizeof(buf), "range: reads %llu..%llu asked of an archive that holds %llu reads in %llu blocks",
+                      (unsigned long long)first, (unsigned long long)(first + count - 1), (unsigned long long)R.reads_total,
+                      (unsigned long long)blocks.size());
+        return buf;
+    }
+    if (pair_mode && ((first | count) & 1)) return "range: under pairs the first read and the count must be even (whole pairs)";
+    if (first + count > known) {
+        std::snprintf(buf, sizeof(buf), "damaged block %llu at or before the range: the reads after it have no numbers",
+                      (unsigned long long)first_bad);
+        return buf;
+    }
+    // every given side file describes exactly these blocks
+    const auto sections = [&](const char *what, bool loaded, uint64_t n, auto reads_of) -> std::string {
+        if (!loaded) return "";
+        if (n != blocks.size()) {
+            std::snprintf(buf, sizeof(buf), "%s: %llu sections for %llu blocks (the side file belongs to another encoding)", what,
+                          (unsigned long long)n, (unsigned long long)blocks.size());
+            return buf;
+        }
+        for (uint64_t i = 0; i < n; i++)
+            if (!blocks[i].bad && reads_of(i) != blocks[i].n_reads) {
+                std::snprintf(buf, sizeof(buf), "%s: section %llu holds %llu reads, block %llu's header says %llu", what,
+                              (unsigned long long)i, (unsigned long long)reads_of(i), (unsigned long long)i,
+                              (unsigned long long)blocks[i].n_reads);
+                return buf;
+            }
+        return "";
+    };
+    std::string why = sections("qualities", qf.loaded, qf.n, [&](uint64_t i) { return (uint64_t)qf.metas[i].n_reads; });
+    if (why.empty()) why = sections("names", nf.loaded, nf.n, [&](uint64_t i) { return (uint64_t)nf.metas[i].n_reads; });
+    if (why.empty()) why = sections("digests", df.loaded, df.n, [&](uint64_t i) { return (uint64_t)df.metas[i].n_reads; });
+    if (!why.empty()) return why;
+    uint64_t b0 = 0, before = 0;
+    while (before + blocks[b0].n_reads <= first) before += blocks[b0++].n_reads;
+    uint64_t b1 = b0, upto = before + blocks[b0].n_reads;  // reads of blocks [0, b1]
+    while (upto < first + count) upto += blocks[++b1].n_reads;
+    ranged = true;
+    blk_base = b0;
+    head_skip = first - before;
+    tail_skip = upto - (first + count);
+    if ((head_skip || tail_skip) && !ntc::g_w_hooks.decode_set_window) return "build: no text window in this build";
+    next_id = 1 + before;
+    blocks = std::vector<DBlock>(blocks.begin() + (std::ptrdiff_t)b0, blocks.begin() + (std::ptrdiff_t)b1 + 1);
+    R.head_skipped = head_skip;
+    R.tail_skipped = tail_skip;
+    return "";
+}
 
 // pinned buffers are sized per batch (grown in the claiming thread, outside the lock)
 bool Decoder::ensure_pinned(void **p, uint64_t *cap, uint64_t need) {
@@ -1793,7 +1869,7 @@ bool Decoder::decode_batch(int c, uint64_t b, DSlot &sl, uint64_t nb, std::vecto
     ntc_ctx *ctx = ctxs[c];
     const uint64_t q_per_base = qf.loaded ? 1 : 0, q_per_read = qf.loaded ? 3 : 0;  // FASTQ: "+\n", qualities, "\n" more
     const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
-                          digits_total(sl.first_id, sl.n_reads) + name_room(sl.first_block, nb) + 64;
+                          digits_total(sl.first_id, sl.n_reads) + name_room(blk_base + sl.first_block, nb) + 64;
     const auto tg = Clock::now();
     if (!discard && !ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
         sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
@@ -1801,26 +1877,50 @@ bool Decoder::decode_batch(int c, uint64_t b, DSlot &sl, uint64_t nb, std::vecto
     }
     if (const int rx = put_runs(ctx, sl.first_id - 1, sl.n_reads, nx_tmp)) return fail_ctx(rx, c);
     const char *what = "qualities: fewer sections than blocks, or a section that does not fit its block";
-    int rx = put_sections(qf, sl.first_block, nb, q_tmp,
+    int rx = put_sections(qf, blk_base + sl.first_block, nb, q_tmp,
                           [&](const ntc_qual_meta *m, uint64_t n, const uint8_t *p, uint64_t bytes) {
                               return ntc::g_q_hooks.decode_set_qualities(ctx, m, n, p, bytes);
                           });
     if (!rx) {
         what = "names: fewer sections than blocks, or a section that does not fit its block";
-        rx = put_sections(nf, sl.first_block, nb, n_tmp,
+        rx = put_sections(nf, blk_base + sl.first_block, nb, n_tmp,
                           [&](const ntc_name_meta *m, uint64_t n, const uint8_t *p, uint64_t bytes) {
                               return ntc::g_n_hooks.decode_set_names(ctx, m, n, p, bytes);
                           });
     }
     if (!rx && df.loaded) {  // the expected digests of the blocks
         what = "digests: fewer sections than blocks";
-        rx = sl.first_block + nb > df.n ? NTC_ERR_FORMAT : ntc::g_d_hooks.decode_set_digests(ctx, df.metas + sl.first_block, nb);
+        rx = blk_base + sl.first_block + nb > df.n
+                 ? NTC_ERR_FORMAT
+                 : ntc::g_d_hooks.decode_set_digests(ctx, df.metas + blk_base + sl.first_block, nb);
     }
     if (rx == NTC_ERR_FORMAT) {
         sh.fail(rx, what);
         return false;
     }
     if (rx) return fail_ctx(rx, c);
+    sl.n_out = sl.n_reads;
+    if (ranged) {
+        // strict: every touched block decoded, to the read count its header gave (the range was
+        // placed by those counts)
+        uint64_t by_header = 0;
+        for (uint64_t i = 0; i < sl.n_blocks; i++) by_header += blocks[sl.first_block + i].n_reads;
+        if (nb != sl.n_blocks || by_header != sl.n_reads) {
+            char why[160];
+            if (nb != sl.n_blocks)
+                std::snprintf(why, sizeof(why), "damaged block %llu inside the range", (unsigned long long)(blk_base + sl.first_block + nb));
+            else
+                std::snprintf(why, sizeof(why), "blocks %llu.. hold %llu reads, their headers say %llu: the range cannot be placed",
+                              (unsigned long long)(blk_base + sl.first_block), (unsigned long long)sl.n_reads,
+                              (unsigned long long)by_header);
+            sh.fail(NTC_ERR_FORMAT, why);
+            return false;
+        }
+        // the range's first and last batch: only its reads are formatted
+        const uint64_t w0 = b == 0 ? head_skip : 0, w1 = sl.n_reads - (b + 1 == n_batches ? tail_skip : 0);
+        sl.n_out = w1 - w0;
+        if (sl.n_out != sl.n_reads && (rx = ntc::g_w_hooks.decode_set_window(ctx, w0, w1 - w0))) return fail_ctx(rx, c);
+    }
     uint64_t len = 0;
     const uint64_t cap = discard ? 0 : sl.cap_text;
     const int rc = gpu_unpack ? ntc_decode_fasta_unpacked(ctx, sl.first_id, sl.text, cap, &len)
@@ -1829,7 +1929,7 @@ bool Decoder::decode_batch(int c, uint64_t b, DSlot &sl, uint64_t nb, std::vecto
     if (rc) {
         std::string msg = std::string("decode: ") + ntc_last_error(ctx);
         int64_t bad = -1;
-        digest_verdict(ctx, rc, sl.first_block, nb, sl.first_id - 1, msg, bad);
+        digest_verdict(ctx, rc, blk_base + sl.first_block, nb, sl.first_id - 1, msg, bad);
         sh.fail(rc, msg, bad);
         return false;
     }
@@ -1839,7 +1939,7 @@ bool Decoder::decode_batch(int c, uint64_t b, DSlot &sl, uint64_t nb, std::vecto
     {
         std::string unused;
         int64_t bad = -1;
-        digest_verdict(ctx, NTC_OK, sl.first_block, nb, sl.first_id - 1, unused, bad);
+        digest_verdict(ctx, NTC_OK, blk_base + sl.first_block, nb, sl.first_id - 1, unused, bad);
     }
     sl.first_len = first;
     sl.text_len = len;
@@ -2050,7 +2150,7 @@ void Decoder::write_text() {
             if (!write_out(slp->text, f) || !write_fd(out_fd2, slp->text + f, slp->text_len - f)) sh.fail(NTC_ERR_IO, "write failed");
             PS.bytes1 += f;
             PS.bytes2 += slp->text_len - f;
-            PS.pairs += slp->n_reads / 2;
+            PS.pairs += slp->n_out / 2;
         } else if (!discard && !write_out(slp->text, slp->text_len)) {
             sh.fail(NTC_ERR_IO, "write failed");
         }
@@ -2058,7 +2158,7 @@ void Decoder::write_text() {
         std::lock_guard<std::mutex> g(sh.mu);
         if (b == 0) S.first_batch_s = secs(t0, Clock::now());
         trace("written", b);
-        S.reads += slp->n_reads;
+        S.reads += slp->n_out;
         S.bases += slp->n_bases;
         S.bytes_out += slp->text_len;
         S.blocks += slp->bad_block >= 0 ? (uint64_t)slp->bad_block : slp->n_blocks;
@@ -2148,6 +2248,21 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
     }
     ::close(fd);
     D.blocks = scan_extents(D.data, fsize);
+    const uint64_t total_blocks = D.blocks.size();
+    const bool clean_end = D.blocks.empty() ? fsize <= 32 : D.blocks.back().a + D.blocks.back().len == fsize;
+    ntc_r_stats R{};
+    R.blocks_total = total_blocks;
+    for (const DBlock &db : D.blocks) R.reads_total += db.n_reads;
+    if (job.read_count) {  // a range: only the blocks that hold it are kept (or the call is refused here)
+        const std::string why = D.place_range(job.read_first, job.read_count, R);
+        if (!why.empty()) {
+            if (D.data) munmap((void *)D.data, fsize);
+            if (stats.r) *stats.r = R;  // (what the archive holds, for the caller's message)
+            const bool arg = why.compare(0, 6, "range:") == 0;
+            return refuse(arg ? NTC_ERR_INVALID_ARG : why.compare(0, 6, "build:") == 0 ? NTC_ERR_UNSUPPORTED : NTC_ERR_FORMAT,
+                          stats.pipe, why);
+        }
+    }
     const std::vector<DBlock> &blocks = D.blocks;
     // NTC_FIRST_BATCH_BLOCKS=n: batch 0 holds n blocks, the others blocks_per_batch.  A
     // one-block first batch (the writer -- the pipeline's bound -- starting sooner) measured
@@ -2184,26 +2299,27 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
     if (D.seekable) (void)lseek(out_fd, D.out_pos, SEEK_SET);
     int result = sh.error == -1 ? NTC_OK : sh.error;
     const int64_t stop_batch = D.stop_batch;
-    const bool clean_end = blocks.empty() ? fsize <= 32 : blocks.back().a + blocks.back().len == fsize;
     char damaged[120];
-    std::snprintf(damaged, sizeof(damaged), "damaged block %llu: the output ends before it", (unsigned long long)S.blocks);
+    std::snprintf(damaged, sizeof(damaged), "damaged block %llu: the output ends before it",
+                  (unsigned long long)(D.blk_base + S.blocks));
     const auto wrong = [&](bool cond, const char *why) {  // an ending that turns a clean run into NTC_ERR_FORMAT
         if (result != NTC_OK || !cond) return;
         result = NTC_ERR_FORMAT;
         sh.msg = why;
     };
     // every batch checked its own runs; one past the file's last read belongs to another encoding
-    wrong(stop_batch < 0 && D.nxf.n && D.nxf.metas[D.nxf.n - 1].read >= S.reads,
+    wrong(!D.ranged && stop_batch < 0 && D.nxf.n && D.nxf.metas[D.nxf.n - 1].read >= S.reads,
           "exceptions: a run past the last read (the side file belongs to another encoding)");
     // an input that ended cleanly used exactly all sections
-    wrong(stop_batch < 0 && clean_end && q_path && D.qf.n != blocks.size(),
+    wrong(stop_batch < 0 && clean_end && q_path && D.qf.n != total_blocks,
           "qualities: more sections than blocks (the side file belongs to another encoding)");
-    wrong(stop_batch < 0 && clean_end && n_path && D.nf.n != blocks.size(),
+    wrong(stop_batch < 0 && clean_end && n_path && D.nf.n != total_blocks,
           "names: more sections than blocks (the side file belongs to another encoding)");
     // under a digest file the lenient endings are errors: the file is known not to be whole
-    wrong(d_path && stop_batch >= 0, damaged);
-    wrong(d_path && !clean_end, "truncated input: the file ends inside a block");
-    wrong(d_path && D.df.n != blocks.size(),
+    // (a range is as strict about the blocks it touches; it never reaches a truncated tail)
+    wrong((d_path || D.ranged) && stop_batch >= 0, damaged);
+    wrong(d_path && !D.ranged && !clean_end, "truncated input: the file ends inside a block");
+    wrong(d_path && D.df.n != total_blocks,
           "digests: more sections than blocks (the input is truncated, or the side file belongs to another encoding)");
     S.dropped_blocks = blocks.size() - S.blocks;  // after a damaged block (or none)
     S.alloc_s += D.t_pin.load();
@@ -2216,6 +2332,10 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
     if (stats.d) *stats.d = D.DS;
     if (pair_mode && discard) D.PS.pairs = S.reads / 2;
     if (stats.p) *stats.p = D.PS;
+    R.first_block = D.blk_base;
+    R.blocks_read = S.blocks;
+    R.reads_written = S.reads;
+    if (stats.r) *stats.r = R;
     if (result != NTC_OK)
         std::snprintf(S.error, sizeof(S.error), "%s", sh.msg.c_str());
     else if (stop_batch >= 0)  // not an error for the reference either: its loop just ends
@@ -2276,6 +2396,61 @@ int ntc_decode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
     FileStats out{stats};
     out.d = d, out.p = p;
     return decode_file(job, out);
+}
+
+int ntc_decode_file_ex5(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts5 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p,
+                        ntc_r_stats *r) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts5)) return NTC_ERR_INVALID_ARG;
+    FileJob job(ctxs, n_ctx, in_path, out_fd, opts);
+    job.take_ex3(*fo);
+    job.fo.pair_mode = fo->pair_mode, job.fo.mate_path = fo->mate_path, job.fo.out_fd2 = fo->out_fd2;
+    job.may_discard = true;
+    job.read_first = fo->read_first, job.read_count = fo->read_count;
+    FileStats out{stats};
+    out.d = d, out.p = p, out.r = r;
+    return decode_file(job, out);
+}
+
+int ntc_archive_info(const char *path, ntc_archive_block **blocks, uint64_t *n_blocks, uint64_t *n_reads,
+                     uint64_t *n_records, uint64_t *tail_bytes) {
+    if (!path || !blocks) return NTC_ERR_INVALID_ARG;
+    *blocks = nullptr;
+    uint64_t nb = 0, reads = 0, recs = 0, tail = 0;
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return NTC_ERR_IO;
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
+        ::close(fd);
+        return NTC_ERR_IO;
+    }
+    const uint64_t fsize = (uint64_t)st.st_size;
+    if (fsize) {
+        const uint8_t *data = (const uint8_t *)mmap(nullptr, fsize, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (data == MAP_FAILED) {
+            ::close(fd);
+            return NTC_ERR_IO;
+        }
+        const std::vector<DBlock> found = scan_extents(data, fsize);  // (the headers and each stream's gzip trailer: nothing is inflated)
+        munmap((void *)data, fsize);
+        nb = found.size();
+        tail = fsize <= 32 ? 0 : fsize - (found.empty() ? 32 : found.back().a + found.back().len);
+        if (nb && !(*blocks = (ntc_archive_block *)std::calloc(nb, sizeof(ntc_archive_block)))) {
+            ::close(fd);
+            return NTC_ERR_IO;
+        }
+        for (uint64_t i = 0; i < nb; i++) {
+            (*blocks)[i] = ntc_archive_block{found[i].a, found[i].len, found[i].n_reads, found[i].n_recs, found[i].bad ? 1u : 0u, 0};
+            reads += found[i].n_reads;
+            recs += found[i].n_recs;
+        }
+    }
+    ::close(fd);
+    if (n_blocks) *n_blocks = nb;
+    if (n_reads) *n_reads = reads;
+    if (n_records) *n_records = recs;
+    if (tail_bytes) *tail_bytes = tail;
+    return NTC_OK;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "qrans_core.h"
 #include "quality_core.h"
+#include "window_core.h"
 
 namespace ntc {
 
@@ -181,6 +182,9 @@ __global__ __launch_bounds__(256) void k_fastq_sizes(const uint64_t *offs, uint6
     sizes[r] = *status != ~0ull ? 0 : 5 + ndigits(first_id + r) + 1 + 2 * (offs[r + 1] - offs[r]) + 4;
 }
 
+// W: the call has a window (window.hip zeroed the sizes outside it): reads without a record are
+// skipped.  W = false is the kernel as it was.
+template <bool W>
 __global__ __launch_bounds__(256) void k_fastq(const uint8_t *bases, const uint8_t *quals, const uint64_t *offs,
                                                uint64_t n, uint64_t first_id, const uint64_t *out_offs,
                                                uint64_t out_cap, uint8_t *out) {
@@ -189,6 +193,7 @@ __global__ __launch_bounds__(256) void k_fastq(const uint8_t *bases, const uint8
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64);
     const uint64_t o0 = offs[0];
     for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); r < n; r += waves) {
+        if (W && w_skips(out_offs[r], out_offs[r + 1])) continue;
         const uint64_t b = offs[r] - o0, len = offs[r + 1] - offs[r];
         uint64_t o = out_offs[r];
         const uint64_t id = first_id + r;
@@ -245,14 +250,15 @@ uint64_t quality_unpack_tiles(uint64_t max_quals) { return max_quals ? (max_qual
 
 void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t n,
                        uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,
-                       uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s) {
+                       uint64_t *tmp, uint8_t *out, uint64_t out_cap, hipStream_t s, uint64_t w_first, uint64_t w_count) {
     if (!n) return;
     hipLaunchKernelGGL(k_fastq_sizes, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d_offs, n, first_id,
                        d_status, sizes);
+    if (w_count) launch_window_sizes(sizes, n, w_first, w_count, s);
     scan_excl_u64(sizes, n, out_offs, tmp, s);
     const uint64_t blocks = std::min<uint64_t>((n + 3) / 4, 65536);
-    hipLaunchKernelGGL(k_fastq, dim3((uint32_t)blocks), dim3(256), 0, s, d_bases, d_quals, d_offs, n, first_id,
-                       out_offs, out_cap, out);
+    hipLaunchKernelGGL(w_count ? k_fastq<true> : k_fastq<false>, dim3((uint32_t)blocks), dim3(256), 0, s, d_bases, d_quals,
+                       d_offs, n, first_id, out_offs, out_cap, out);
 }
 
 }  // namespace ntc
