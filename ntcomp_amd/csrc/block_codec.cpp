@@ -598,6 +598,71 @@ int hand_out(const std::vector<uint8_t> &buf, uint8_t **out, uint64_t *out_len) 
     *out_len = buf.size();
     return NTC_OK;
 }
+
+// ---- what the side-file readers share (ntc_nx_read, ntc_q_read, ntc_n_read, ntc_d_read) ----
+// the whole file into buf
+int slurp(const char *path, std::vector<uint8_t> &buf) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return NTC_ERR_IO;
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+    const bool io_bad = std::ferror(f) != 0;
+    std::fclose(f);
+    return io_bad ? NTC_ERR_IO : NTC_OK;
+}
+// The 32-byte header of a side file: the tag, a version 1..max_version and three zero bytes;
+// bytes [8, zero_from) are the file's own fields, the rest must be zero.
+bool side_header(const std::vector<uint8_t> &buf, const char *tag, uint32_t max_version, size_t zero_from) {
+    if (buf.size() < 32 || std::memcmp(buf.data(), tag, 4) != 0) return false;
+    if (buf[4] < 1 || buf[4] > max_version || buf[5] || buf[6] || buf[7]) return false;
+    for (size_t i = zero_from; i < 32; i++)
+        if (buf[i]) return false;
+    return true;
+}
+// a vector handed to the caller as a malloc'd array (ntc_buffer_free); an empty one as null
+template <class T>
+int hand_out_array(const std::vector<T> &v, T **out) {
+    *out = nullptr;
+    if (v.empty()) return NTC_OK;
+    *out = (T *)std::malloc(v.size() * sizeof(T));
+    if (!*out) return NTC_ERR_CAPACITY;
+    std::memcpy(*out, v.data(), v.size() * sizeof(T));
+    return NTC_OK;
+}
+// the sections of a file and their payload, both or neither
+template <class Meta>
+int hand_out_sections(const std::vector<Meta> &all, const std::vector<uint8_t> &pay, Meta **metas, uint64_t *n_blocks,
+                      uint8_t **payload, uint64_t *payload_bytes) {
+    int rc = hand_out_array(all, metas);
+    if (rc) return rc;
+    if ((rc = hand_out_array(pay, payload))) {
+        std::free(*metas);
+        *metas = nullptr;
+        return rc;
+    }
+    *n_blocks = all.size();
+    *payload_bytes = pay.size();
+    return NTC_OK;
+}
+// work(i, scratch) for every member i < n, side by side on up to 16 threads (a file of whole
+// blocks holds ~10 MB each); false once one of them fails
+template <class Work>
+bool inflate_members(size_t n, const Work &work) {
+    std::atomic<size_t> next{0};
+    std::atomic<bool> bad{false};
+    const auto run = [&] {
+        std::vector<uint8_t> scratch;
+        for (size_t i; (i = next.fetch_add(1)) < n && !bad;)
+            if (!work(i, scratch)) bad = true;
+    };
+    const size_t T = std::min<size_t>(n, (size_t)std::max(1, std::min(16, ntc_host_threads())));
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < T; t++) pool.emplace_back(run);
+    run();
+    for (auto &t : pool) t.join();
+    return !bad;
+}
 }  // namespace
 
 extern "C" {
@@ -840,20 +905,9 @@ int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t 
     *runs = nullptr;
     *n_runs = 0;
     *sub = 0;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return NTC_ERR_IO;
     std::vector<uint8_t> buf;
-    uint8_t chunk[1 << 16];
-    size_t got;
-    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-    const bool io_bad = std::ferror(f) != 0;
-    std::fclose(f);
-    if (io_bad) return NTC_ERR_IO;
-    static const uint8_t magic[8] = {'N', 'T', 'C', 'X', 1, 0, 0, 0};
-    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
-    if (!ntc::nx_is_base(buf[8])) return NTC_ERR_FORMAT;
-    for (size_t i = 9; i < 32; i++)
-        if (buf[i]) return NTC_ERR_FORMAT;
+    if (const int rc = slurp(path, buf)) return rc;
+    if (!side_header(buf, "NTCX", 1, 9) || !ntc::nx_is_base(buf[8])) return NTC_ERR_FORMAT;
     std::vector<ntc_nx_run> all;
     size_t at = 32;
     while (at < buf.size()) {
@@ -876,11 +930,7 @@ int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t 
             if (r.read < p.read || (r.read == p.read && (uint64_t)r.pos < (uint64_t)p.pos + p.len)) return NTC_ERR_FORMAT;
         }
     }
-    if (!all.empty()) {
-        *runs = (ntc_nx_run *)std::malloc(all.size() * sizeof(ntc_nx_run));
-        if (!*runs) return NTC_ERR_CAPACITY;
-        std::memcpy(*runs, all.data(), all.size() * sizeof(ntc_nx_run));
-    }
+    if (const int rc = hand_out_array(all, runs)) return rc;
     *n_runs = all.size();
     *sub = buf[8];
     return NTC_OK;
@@ -956,22 +1006,11 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
     *n_blocks = 0;
     *payload = nullptr;
     *payload_bytes = 0;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return NTC_ERR_IO;
     std::vector<uint8_t> buf;
-    uint8_t chunk[1 << 16];
-    size_t got;
-    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-    const bool io_bad = std::ferror(f) != 0;
-    std::fclose(f);
-    if (io_bad) return NTC_ERR_IO;
-    static const uint8_t magic[8] = {'N', 'T', 'C', 'Q', 1, 0, 0, 0};
-    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 4) != 0) return NTC_ERR_FORMAT;
+    if (const int rc = slurp(path, buf)) return rc;
+    if (!side_header(buf, "NTCQ", 2, 10)) return NTC_ERR_FORMAT;
     const bool v2 = buf[4] == 2;  // version 2: coder 1, the bodies as they are
-    if (std::memcmp(buf.data() + 5, magic + 5, 3) != 0 || (!v2 && buf[4] != 1)) return NTC_ERR_FORMAT;
     if (buf[8] < 1 || buf[8] > 2 || buf[9] != (v2 ? 1 : 0)) return NTC_ERR_FORMAT;
-    for (size_t i = 10; i < 32; i++)
-        if (buf[i]) return NTC_ERR_FORMAT;
     // pass 1: the headers and alphabets, and where each member lies and inflates to
     std::vector<ntc_qual_meta> all;
     std::vector<uint64_t> gz_at, gz_len;
@@ -1017,60 +1056,28 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
         at += gz;
         all.push_back(m);
     }
-    // pass 2: the members inflate side by side (a file of whole blocks holds ~10 MB each)
+    // pass 2: the members inflate side by side
     std::vector<uint8_t> pay(pay_bytes);
-    std::atomic<size_t> next{0};
-    std::atomic<bool> bad{false};
-    const auto work = [&] {
-        std::vector<uint8_t> words;
-        for (size_t i; (i = next.fetch_add(1)) < all.size() && !bad;) {
-            const ntc_qual_meta &m = all[i];
-            if (!m.width) continue;
-            if (v2) {
-                std::memcpy(pay.data() + m.payload_off, buf.data() + gz_at[i], m.payload_bytes);
-                continue;
-            }
-            if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, words)) {
-                bad = true;
-                return;
-            }
-            const uint64_t bits = m.n_quals * m.width;  // padding bits of the last word
-            if (bits & 63) {
-                uint64_t last;
-                std::memcpy(&last, words.data() + m.payload_bytes - 8, 8);
-                if (last >> (bits & 63)) {
-                    bad = true;
-                    return;
-                }
-            }
-            std::memcpy(pay.data() + m.payload_off, words.data(), m.payload_bytes);
+    const bool ok = inflate_members(all.size(), [&](size_t i, std::vector<uint8_t> &words) {
+        const ntc_qual_meta &m = all[i];
+        if (!m.width) return true;
+        if (v2) {
+            std::memcpy(pay.data() + m.payload_off, buf.data() + gz_at[i], m.payload_bytes);
+            return true;
         }
-    };
-    {
-        const size_t T = std::min<size_t>(all.size(), (size_t)std::max(1, std::min(16, ntc_host_threads())));
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < T; t++) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-    }
-    if (bad) return NTC_ERR_FORMAT;
-    if (!all.empty()) {
-        *metas = (ntc_qual_meta *)std::malloc(all.size() * sizeof(ntc_qual_meta));
-        if (!*metas) return NTC_ERR_CAPACITY;
-        std::memcpy(*metas, all.data(), all.size() * sizeof(ntc_qual_meta));
-    }
-    if (!pay.empty()) {
-        *payload = (uint8_t *)std::malloc(pay.size());
-        if (!*payload) {
-            std::free(*metas);
-            *metas = nullptr;
-            return NTC_ERR_CAPACITY;
+        if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, words)) return false;
+        const uint64_t bits = m.n_quals * m.width;  // padding bits of the last word
+        if (bits & 63) {
+            uint64_t last;
+            std::memcpy(&last, words.data() + m.payload_bytes - 8, 8);
+            if (last >> (bits & 63)) return false;
         }
-        std::memcpy(*payload, pay.data(), pay.size());
-    }
+        std::memcpy(pay.data() + m.payload_off, words.data(), m.payload_bytes);
+        return true;
+    });
+    if (!ok) return NTC_ERR_FORMAT;
+    if (const int rc = hand_out_sections(all, pay, metas, n_blocks, payload, payload_bytes)) return rc;
     *mode = buf[8];
-    *n_blocks = all.size();
-    *payload_bytes = pay.size();
     return NTC_OK;
 }
 
@@ -1078,11 +1085,8 @@ int ntc_q_read(const char *path, int *mode, ntc_qual_meta **metas, uint64_t *n_b
 
 // ---- name side file "NTCN" (include/ntcomp_codec.h) -----------------------------------
 namespace {
-// the counts of a meta agree with one another (payload_off is the caller's)
-bool n_meta_ok(const ntc_name_meta &m) {
-    return !(m.n_reads >> 40) && m.mid_bytes <= m.name_bytes && m.name_bytes <= m.n_reads * ntc::kNMax &&
-           m.payload_bytes == ntc::n_payload_bytes(m.n_reads, m.mid_bytes);
-}
+// the counts of a meta agree with one another (names_core.h; payload_off is the caller's)
+bool n_meta_ok(const ntc_name_meta &m) { return ntc::n_meta_ok(m.n_reads, m.name_bytes, m.mid_bytes, m.payload_bytes); }
 // the payload of a section whose meta n_meta_ok took: every per-read rule, the sums, the padding
 bool n_section_ok(const ntc_name_meta &m, const uint8_t *p) {
     const uint64_t n = m.n_reads;
@@ -1146,20 +1150,9 @@ int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_b
     *n_blocks = 0;
     *payload = nullptr;
     *payload_bytes = 0;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return NTC_ERR_IO;
     std::vector<uint8_t> buf;
-    uint8_t chunk[1 << 16];
-    size_t got;
-    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-    const bool io_bad = std::ferror(f) != 0;
-    std::fclose(f);
-    if (io_bad) return NTC_ERR_IO;
-    static const uint8_t magic[8] = {'N', 'T', 'C', 'N', 1, 0, 0, 0};
-    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
-    if (buf[8] < 1 || buf[8] > 2) return NTC_ERR_FORMAT;
-    for (size_t i = 9; i < 32; i++)
-        if (buf[i]) return NTC_ERR_FORMAT;
+    if (const int rc = slurp(path, buf)) return rc;
+    if (!side_header(buf, "NTCN", 1, 9) || buf[8] < 1 || buf[8] > 2) return NTC_ERR_FORMAT;
     // pass 1: the section headers, and where each member lies and inflates to
     std::vector<ntc_name_meta> all;
     std::vector<uint64_t> gz_at, gz_len;
@@ -1188,44 +1181,15 @@ int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_b
     }
     // pass 2: the members inflate and are checked side by side
     std::vector<uint8_t> pay(pay_bytes);
-    std::atomic<size_t> next{0};
-    std::atomic<bool> bad{false};
-    const auto work = [&] {
-        std::vector<uint8_t> sec;
-        for (size_t i; (i = next.fetch_add(1)) < all.size() && !bad;) {
-            const ntc_name_meta &m = all[i];
-            if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, sec) || !n_section_ok(m, sec.data())) {
-                bad = true;
-                return;
-            }
-            if (m.payload_bytes) std::memcpy(pay.data() + m.payload_off, sec.data(), m.payload_bytes);
-        }
-    };
-    {
-        const size_t T = std::min<size_t>(all.size(), (size_t)std::max(1, std::min(16, ntc_host_threads())));
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < T; t++) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-    }
-    if (bad) return NTC_ERR_FORMAT;
-    if (!all.empty()) {
-        *metas = (ntc_name_meta *)std::malloc(all.size() * sizeof(ntc_name_meta));
-        if (!*metas) return NTC_ERR_CAPACITY;
-        std::memcpy(*metas, all.data(), all.size() * sizeof(ntc_name_meta));
-    }
-    if (!pay.empty()) {
-        *payload = (uint8_t *)std::malloc(pay.size());
-        if (!*payload) {
-            std::free(*metas);
-            *metas = nullptr;
-            return NTC_ERR_CAPACITY;
-        }
-        std::memcpy(*payload, pay.data(), pay.size());
-    }
+    const bool ok = inflate_members(all.size(), [&](size_t i, std::vector<uint8_t> &sec) {
+        const ntc_name_meta &m = all[i];
+        if (!gunzip_exact(buf.data() + gz_at[i], gz_len[i], m.payload_bytes, sec) || !n_section_ok(m, sec.data())) return false;
+        if (m.payload_bytes) std::memcpy(pay.data() + m.payload_off, sec.data(), m.payload_bytes);
+        return true;
+    });
+    if (!ok) return NTC_ERR_FORMAT;
+    if (const int rc = hand_out_sections(all, pay, metas, n_blocks, payload, payload_bytes)) return rc;
     *mode = buf[8];
-    *n_blocks = all.size();
-    *payload_bytes = pay.size();
     return NTC_OK;
 }
 
@@ -1234,13 +1198,10 @@ int ntc_n_read(const char *path, int *mode, ntc_name_meta **metas, uint64_t *n_b
 // ---- digest side file "NTCD" (include/ntcomp_codec.h) ---------------------------------
 namespace {
 static_assert(sizeof(ntc_digest_meta) == 56, "a section is the meta as it stands");
-// a meta on its own: known bits, seq among them, nothing set for an absent component
+// a meta on its own (digest_core.h): known bits, seq among them, nothing set for an absent component
 bool d_meta_ok(const ntc_digest_meta &m) {
-    if ((m.components & ~ntc::kDgAll) || !(m.components & ntc::kDgSeq) || m.reserved) return false;
     const uint64_t d[4] = {m.d_seq, m.d_sym, m.d_qual, m.d_name};
-    for (uint32_t c = 0; c < 4; c++)
-        if (!(m.components >> c & 1) && d[c]) return false;
-    return true;
+    return ntc::dg_meta_ok(m.components, m.reserved, d);
 }
 }  // namespace
 
@@ -1266,34 +1227,18 @@ int ntc_d_read(const char *path, uint32_t *components, uint32_t *k, uint64_t *n_
     *n_nodes = 0;
     *metas = nullptr;
     *n_blocks = 0;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return NTC_ERR_IO;
     std::vector<uint8_t> buf;
-    uint8_t chunk[1 << 16];
-    size_t got;
-    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-    const bool io_bad = std::ferror(f) != 0;
-    std::fclose(f);
-    if (io_bad) return NTC_ERR_IO;
-    static const uint8_t magic[8] = {'N', 'T', 'C', 'D', 1, 0, 0, 0};
-    if (buf.size() < 32 || std::memcmp(buf.data(), magic, 8) != 0) return NTC_ERR_FORMAT;
+    if (const int rc = slurp(path, buf)) return rc;
+    if (!side_header(buf, "NTCD", 1, 24) || buf[9] || buf[10] || buf[11]) return NTC_ERR_FORMAT;  // (k and n_nodes between)
     const uint32_t comp = buf[8];
     if ((comp & ~ntc::kDgAll) || !(comp & ntc::kDgSeq)) return NTC_ERR_FORMAT;
-    for (size_t i = 9; i < 12; i++)
-        if (buf[i]) return NTC_ERR_FORMAT;
-    for (size_t i = 24; i < 32; i++)
-        if (buf[i]) return NTC_ERR_FORMAT;
     if ((buf.size() - 32) % sizeof(ntc_digest_meta)) return NTC_ERR_FORMAT;
     const uint64_t n = (buf.size() - 32) / sizeof(ntc_digest_meta);
     std::vector<ntc_digest_meta> all(n);
     if (n) std::memcpy(all.data(), buf.data() + 32, n * sizeof(ntc_digest_meta));
     for (const ntc_digest_meta &m : all)
         if (!d_meta_ok(m) || (m.components & ~comp)) return NTC_ERR_FORMAT;
-    if (n) {
-        *metas = (ntc_digest_meta *)std::malloc(n * sizeof(ntc_digest_meta));
-        if (!*metas) return NTC_ERR_CAPACITY;
-        std::memcpy(*metas, all.data(), n * sizeof(ntc_digest_meta));
-    }
+    if (const int rc = hand_out_array(all, metas)) return rc;
     std::memcpy(k, buf.data() + 12, 4);
     std::memcpy(n_nodes, buf.data() + 16, 8);
     *components = comp;

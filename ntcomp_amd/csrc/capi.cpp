@@ -69,6 +69,92 @@ struct IndexMem {
     }
 };
 
+namespace {
+// Side data handed to the context for the next decode call (ntc_decode_set_*): section metas
+// and their payload words.  They leave the context with the call that takes them, which uses
+// them once, whether it succeeds or fails.
+template <class Meta>
+struct Pending {
+    std::vector<Meta> metas;
+    std::vector<uint64_t> payload;
+    bool has = false;
+    void clear() { *this = Pending(); }
+    bool take(Pending &to) {
+        to = has ? std::move(*this) : Pending();
+        clear();
+        return to.has;
+    }
+};
+
+// non-ACGT symbols (nonacgt.hip): the policy (0 error, 1 mask, 2 keep), the last encode
+// call's counts and runs, the runs waiting for the next decode call (pending.has: any run)
+struct NxState {
+    int policy = 0;
+    uint64_t runs = 0, bases = 0;
+    uint64_t cap = 0, cap_hint = 0;  // the run list of the call in flight; what an earlier call needed
+    void *d_runs = nullptr;
+    std::vector<ntc_nx_run> list;
+    Pending<ntc_nx_run> pending;
+    uint32_t pending_sub = 0;
+    std::vector<ntc_nx_run> pieces;  // the slices of the decode pass in flight (source of an async copy)
+    void begin() {  // a host-buffer encode call starts: nothing of the last one is left
+        runs = bases = 0;
+        list.clear();
+    }
+};
+
+// quality scores (quality.hip): the mode (0 drop, 1 keep, 2 bin8), the sections the last
+// ntc_encode_pack_fastq left in WS_Q_BLOCKS / WS_Q_PAYLOAD, the sections waiting for the
+// next FASTA decode call (which then writes FASTQ)
+struct QualState {
+    int mode = 0;
+    int coder = 0;  // option "quality_coder": 0 pack, 1 rans (qrans.hip); coder_last: of those sections
+    int coder_last = 0;
+    uint64_t blocks = 0, words = 0, reads = 0;
+    uint32_t block_reads = 0;
+    Pending<ntc_qual_meta> pending;
+    void begin() { blocks = words = reads = 0; }  // an encode call starts: the last call's sections are gone
+};
+
+// read names (names.hip): the mode (0 drop, 1 keep, 2 id), the sections the last
+// ntc_encode_pack_fastq left in WS_N_BLOCKS / WS_N_PAYLOAD, the sections waiting for the
+// next FASTA decode call (which then writes the names instead of seq.N)
+struct NameState {
+    int mode = 0;
+    uint64_t blocks = 0, bytes = 0;
+    const uint32_t *d_start = nullptr, *d_len = nullptr;  // the name spans of the names pass in flight
+    Pending<ntc_name_meta> pending;
+    void begin() { blocks = bytes = 0; }  // an encode call starts: the last call's sections are gone
+};
+
+// content digests (digest.hip): the option (0 off, 1 on), the table the last
+// ntc_encode_pack_* call left in WS_DG_TABLE, the expected digests waiting for the next
+// FASTA decode call, and what the last such call computed (WS_DGD_IN holds both on the device)
+struct DigestState {
+    int opt = 0;
+    uint64_t blocks = 0;
+    Pending<ntc_digest_meta> pending;  // (no payload)
+    std::vector<ntc_digest_meta> expected, computed;
+    uint32_t checkable = 0;  // the components that call could compute
+    void begin() { blocks = 0; }  // an encode call starts: the last call's digests are gone
+};
+
+// paired-end reads (pairs.hip): the option (0 off, 1 pairs with the mate check, 2 pairs
+// without it); whether the last text decode was split, and the bytes of its first part
+struct PairState {
+    int mode = 0;
+    bool valid = false;
+    uint64_t first = 0;
+};
+
+// the text window of the next ntc_decode_fasta / _unpacked (ntc_decode_set_window): pending
+// like the side data above, gone after that call whether it succeeds or fails
+struct WindowState {
+    bool has_pending = false;
+    uint64_t first = 0, count = 0;
+};
+}  // namespace
+
 struct ntc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -82,9 +168,8 @@ struct ntc_ctx {
     // workspace buffers (grown, never shrunk)
     DevBuf ws[WS_COUNT];
     unsigned long long *d_status = nullptr;
-    // status mailbox in pinned host memory: {status, count a, count b}, written by k_status_box
-    // at the end of a device call, so *_status() is one stream sync instead of D2H copies
-    // (16 words: 0-3 k_status_box, 4-5 non-ACGT, 6-7 qualities, 8-9 names, 10-12 pairs)
+    // status mailbox in pinned host memory (kernels.h BoxWord names its words), written by the
+    // last kernels of a device call, so *_status() is one stream sync instead of D2H copies
     uint64_t *h_box = nullptr;
     bool box_valid = false;
     // the records of the last ntc_unpack_streams (in WS_UNP_RECS) and their read / base counts
@@ -124,7 +209,7 @@ struct ntc_ctx {
     int path_link_opt = path_link_on() ? 1 : 0;  // path cover: unitigs linked across branches (default) or not
     int win_opt = -1;        // SCAN window words at the next upload: -1 auto (U >= 4), 0 off, 1 on
     int subst_opt = subst_on() ? -1 : 0;  // substitution words at the next upload: -1 auto (the build without
-                                          // joint runs, path positions in the table, U >= 4), 0 zeroed
+                                               // joint runs, path positions in the table, U >= 4), 0 zeroed
     int subst_built = 0;     // the index in use carries substitution words
     int decode_only_opt = 0;  // the next upload builds only what decode needs (walk table): no path
                               // cover, suffix table or SCAN words; encode calls then fail
@@ -135,58 +220,14 @@ struct ntc_ctx {
     int64_t upload_host_us = 0, upload_total_us = 0;  // last ntc_index_upload: host derive / total
     uint64_t max_pass_bases = 1ULL << 30;  // host-buffer calls split into device passes of at most this
     double last_pack_ms = 0;               // last ntc_pack_blocks_device: both packer kernels
-    // non-ACGT symbols (nonacgt.hip): the policy (0 error, 1 mask, 2 keep), the last encode
-    // call's counts and runs, the runs waiting for the next decode call
-    int nx_policy = 0;
-    uint64_t nx_runs = 0, nx_bases = 0;
-    uint64_t nx_cap = 0, nx_cap_hint = 0;  // the run list of the call in flight; what an earlier call needed
-    void *nx_d_runs = nullptr;
-    std::vector<ntc_nx_run> nx_list;
-    std::vector<ntc_nx_run> nx_pending;
-    std::vector<ntc_nx_run> nx_pieces;     // the slices of the decode pass in flight (source of an async copy)
-    uint32_t nx_pending_sub = 0;
-    bool nx_has_pending = false;
-    // quality scores (quality.hip): the mode (0 drop, 1 keep, 2 bin8), the sections the last
-    // ntc_encode_pack_fastq left in WS_Q_BLOCKS / WS_Q_PAYLOAD, the sections waiting for the
-    // next FASTA decode call (which then writes FASTQ)
-    int q_mode = 0;
-    int q_coder = 0;       // option "quality_coder": 0 pack, 1 rans (qrans.hip); q_coder_last: of those sections
-    int q_coder_last = 0;
-    uint64_t q_blocks = 0, q_words = 0, q_reads = 0;
-    uint32_t q_block_reads = 0;
-    std::vector<ntc_qual_meta> qd_metas;
-    std::vector<uint64_t> qd_payload;
-    bool qd_has_pending = false;
-    // read names (names.hip): the mode (0 drop, 1 keep, 2 id), the sections the last
-    // ntc_encode_pack_fastq left in WS_N_BLOCKS / WS_N_PAYLOAD, the sections waiting for the
-    // next FASTA decode call (which then writes the names instead of seq.N)
-    int n_mode = 0;
-    uint64_t n_blocks = 0, n_bytes = 0;
-    std::vector<ntc_name_meta> nd_metas;
-    std::vector<uint64_t> nd_payload;
-    uint64_t nd_name_bytes = 0;
-    bool nd_has_pending = false;
-    // content digests (digest.hip): the option (0 off, 1 on), the table the last
-    // ntc_encode_pack_* call left in WS_DG_TABLE, the expected digests waiting for the next
-    // FASTA decode call, and what the last such call computed (WS_DGD_IN holds both on the device)
-    int dg_opt = 0;
-    uint64_t dg_blocks = 0;
-    const uint32_t *n_d_start = nullptr, *n_d_len = nullptr;  // the name spans of the names pass in flight
-    std::vector<ntc_digest_meta> dd_metas;
-    bool dd_has_pending = false;
-    std::vector<ntc_digest_meta> dd_expected, dd_computed;
+    NxState nx;
+    QualState qual;
+    NameState names;
+    DigestState dig;
+    PairState pair;
+    WindowState win;
     int discard_text = 0;  // option "discard_text": a FASTA decode call formats its text and leaves it on the device
-    uint32_t dd_checkable = 0;  // the components that call could compute
-    // paired-end reads (pairs.hip): the option (0 off, 1 pairs with the mate check, 2 pairs
-    // without it); whether the last text decode was split, and the bytes of its first part
-    int paired = 0;
-    bool pair_valid = false;
-    uint64_t pair_first = 0;
-    // the text window of the next ntc_decode_fasta / _unpacked (ntc_decode_set_window): pending
-    // like the side data above, gone after that call whether it succeeds or fails
-    bool tw_has_pending = false;
-    uint64_t tw_first = 0, tw_count = 0;
-    FastqArgs fq_last{};                   // the last GPU FASTQ parse (run again when the run list was short)
+    FastqArgs fq_last{};              // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
 };
 
@@ -195,7 +236,6 @@ namespace {
 // work queue heads (kernels.hip WaveQueue: 8, 64 B apart), then the two pool counters
 // (kPoolCntE, kPoolCntR: words 64 and 72)
 constexpr uint64_t kCounterBytes = 8 * 64 + 2 * 64;
-
 
 #define HIP_TRY(ctx, expr)                                                                   \
     do {                                                                                     \
@@ -240,6 +280,16 @@ int ensure(ntc_ctx *ctx, int slot, uint64_t bytes, void **out) {
     }
     *out = b.p;
     return NTC_OK;
+}
+// a word of the status mailbox, after the stream sync that its writer's call ends with
+inline uint64_t box(const ntc_ctx *ctx, BoxWord w) { return ((volatile uint64_t *)ctx->h_box)[w]; }
+
+// an encode call starts, or failed: no side data of an earlier call is left to fetch
+inline void side_begin(ntc_ctx *ctx) {
+    ctx->nx.begin();
+    ctx->qual.begin();
+    ctx->names.begin();
+    ctx->dig.begin();
 }
 
 const char *status_name(int code) {
@@ -464,7 +514,7 @@ int read_status(ntc_ctx *ctx, int64_t *bad_index) {
         unsigned long long st = 0;
         if (ctx->box_valid) {  // the call's mailbox (k_status_box): one stream sync
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            st = ((volatile uint64_t *)ctx->h_box)[0];
+            st = box(ctx, kBoxStatus);
         } else {
             HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->d_status, 8, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -472,7 +522,7 @@ int read_status(ntc_ctx *ctx, int64_t *bad_index) {
         if (st == ~0ULL) {
             if (bad_index) *bad_index = -1;
             if (ctx->box_valid && ctx->last == kEncode && ctx->last_variant == 4)
-                learn_pool_rates(ctx, ((volatile uint64_t *)ctx->h_box)[2], ((volatile uint64_t *)ctx->h_box)[3]);
+                learn_pool_rates(ctx, box(ctx, kBoxB), box(ctx, kBoxC));
             return NTC_OK;
         }
         if (st == kStatusRegrow) {
@@ -497,19 +547,25 @@ int read_status(ntc_ctx *ctx, int64_t *bad_index) {
     }
 }
 
+// A decode-side pass may have set the call's status after the walk filled the mailbox: fill it
+// again (same counts), so the call's one sync still reads the final status.
+int rebox_decode(ntc_ctx *ctx) {
+    if (ctx->box_valid && ctx->last == kDecode)
+        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
+                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
 
 // ---- non-ACGT symbols (nonacgt.hip) ---------------------------------------------------
 // Before an encode of staged bases (the library's own, writable copy): flag, list the runs
-// (policy keep), substitute.  Asynchronous; the counts reach the host in mailbox words 4 and
-// 5 with the encode call's own status sync (nx_collect).  Policy 0 launches nothing.
-void nx_begin(ntc_ctx *ctx) {  // a host-buffer encode call starts: nothing of the last one is left
-    ctx->nx_runs = ctx->nx_bases = 0;
-    ctx->nx_list.clear();
-}
+// (policy keep), substitute.  Asynchronous; the counts reach the host in mailbox words
+// kBoxNxRuns and kBoxNxBases with the encode call's own status sync (nx_collect).  Policy 0
+// launches nothing.
 int nx_mask(ntc_ctx *ctx, uint8_t *d_bases, const uint64_t *d_offs, uint64_t n_reads, uint64_t total) {
-    ctx->nx_cap = 0;
-    if (ctx->nx_policy == 0) return NTC_OK;
-    ctx->h_box[4] = ctx->h_box[5] = 0;  // (the last call's kernels are done: every encode call ends synchronised)
+    ctx->nx.cap = 0;
+    if (ctx->nx.policy == 0) return NTC_OK;
+    ctx->h_box[kBoxNxRuns] = ctx->h_box[kBoxNxBases] = 0;  // (the last call's kernels are done: every encode call ends synchronised)
     if (n_reads == 0) return NTC_OK;
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     const uint32_t sub = nx_substitute(ctx->dix.absent);
@@ -537,14 +593,14 @@ int nx_mask(ntc_ctx *ctx, uint8_t *d_bases, const uint64_t *d_offs, uint64_t n_r
     a.cnt_s = (uint32_t *)(a.counts + 2);
     a.cnt_e = a.cnt_s + (W + 1);
     if ((rc = ensure(ctx, WS_SCANTMP, scan_tmp_words(std::max(W, n_reads) + 1) * 8, &tmp))) return rc;
-    if (ctx->nx_policy == 2) {
+    if (ctx->nx.policy == 2) {
         // room for a run per 16 bases, or what an earlier call needed; a call that finds
         // more is staged and run again with the exact room (nx_collect)
-        ctx->nx_cap = std::min<uint64_t>(std::max<uint64_t>(total / 16 + 4096, ctx->nx_cap_hint), total + 1);
-        if ((rc = ensure(ctx, WS_NX_RUNS, ctx->nx_cap * sizeof(ntc_nx_run), &p))) return rc;
-        ctx->nx_d_runs = p;
+        ctx->nx.cap = std::min<uint64_t>(std::max<uint64_t>(total / 16 + 4096, ctx->nx.cap_hint), total + 1);
+        if ((rc = ensure(ctx, WS_NX_RUNS, ctx->nx.cap * sizeof(ntc_nx_run), &p))) return rc;
+        ctx->nx.d_runs = p;
         a.runs = (NxRun *)p;
-        a.run_cap = ctx->nx_cap;
+        a.run_cap = ctx->nx.cap;
     }
     a.box = ctx->h_box;
     a.sub = sub;
@@ -559,21 +615,21 @@ int nx_mask(ntc_ctx *ctx, uint8_t *d_bases, const uint64_t *d_offs, uint64_t n_r
 // stages the bases afresh (they are masked by now) and runs the call again.
 int nx_collect(ntc_ctx *ctx, uint64_t read_base, bool *again) {
     *again = false;
-    if (ctx->nx_policy == 0) return NTC_OK;
-    const uint64_t n = ((volatile uint64_t *)ctx->h_box)[4], nb = ((volatile uint64_t *)ctx->h_box)[5];
-    if (ctx->nx_policy == 2 && n > ctx->nx_cap) {
-        ctx->nx_cap_hint = n + n / 4;
+    if (ctx->nx.policy == 0) return NTC_OK;
+    const uint64_t n = box(ctx, kBoxNxRuns), nb = box(ctx, kBoxNxBases);
+    if (ctx->nx.policy == 2 && n > ctx->nx.cap) {
+        ctx->nx.cap_hint = n + n / 4;
         *again = true;
         return NTC_OK;
     }
-    ctx->nx_runs += n;
-    ctx->nx_bases += nb;
-    if (ctx->nx_policy != 2 || n == 0) return NTC_OK;
-    const size_t at = ctx->nx_list.size();
-    ctx->nx_list.resize(at + n);
-    HIP_TRY(ctx, hipMemcpy(ctx->nx_list.data() + at, ctx->nx_d_runs, n * sizeof(ntc_nx_run), hipMemcpyDeviceToHost));
+    ctx->nx.runs += n;
+    ctx->nx.bases += nb;
+    if (ctx->nx.policy != 2 || n == 0) return NTC_OK;
+    const size_t at = ctx->nx.list.size();
+    ctx->nx.list.resize(at + n);
+    HIP_TRY(ctx, hipMemcpy(ctx->nx.list.data() + at, ctx->nx.d_runs, n * sizeof(ntc_nx_run), hipMemcpyDeviceToHost));
     if (read_base)
-        for (size_t i = at; i < at + n; i++) ctx->nx_list[i].read += read_base;
+        for (size_t i = at; i < at + n; i++) ctx->nx.list[i].read += read_base;
     return NTC_OK;
 }
 
@@ -587,7 +643,7 @@ int nx_patch(ntc_ctx *ctx, const std::vector<ntc_nx_run> &runs, uint32_t sub, ui
                                [](const ntc_nx_run &x, uint64_t v) { return x.read < v; });
     auto hi = std::lower_bound(lo, runs.end(), r0 + n_reads, [](const ntc_nx_run &x, uint64_t v) { return x.read < v; });
     if (lo == hi) return NTC_OK;
-    std::vector<ntc_nx_run> &pc = ctx->nx_pieces;
+    std::vector<ntc_nx_run> &pc = ctx->nx.pieces;
     pc.clear();
     pc.reserve((size_t)(hi - lo));
     for (auto it = lo; it != hi; ++it) {
@@ -618,41 +674,24 @@ int nx_patch(ntc_ctx *ctx, const std::vector<ntc_nx_run> &runs, uint32_t sub, ui
     a.status = ctx->d_status;
     launch_nx_patch(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    if (ctx->box_valid && ctx->last == kDecode)
-        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
-                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    return NTC_OK;
-}
-
-// the pending runs leave the context: the call that takes them uses them once
-bool nx_take_pending(ntc_ctx *ctx, std::vector<ntc_nx_run> &runs, uint32_t &sub) {
-    runs.clear();
-    if (!ctx->nx_has_pending) return false;
-    runs.swap(ctx->nx_pending);
-    sub = ctx->nx_pending_sub;
-    ctx->nx_has_pending = false;
-    return !runs.empty();
+    return rebox_decode(ctx);
 }
 
 // ---- quality scores (quality.hip) -------------------------------------------------------
 // After a GPU FASTQ parse (the text, its newline table and the read offsets are in HBM):
 // gather, alphabets, pack.  Asynchronous: the pass has a status word of its own (d_status is
 // preset again by the encode that follows), which reaches the host with the payload's size
-// in mailbox words 6 and 7 at the encode call's own status sync (q_collect).  Mode 0 returns
-// before anything is launched.
-void q_begin(ntc_ctx *ctx) {  // an encode call starts: the last call's sections are gone
-    ctx->q_blocks = ctx->q_words = ctx->q_reads = 0;
-}
+// in mailbox words kBoxQualStatus and kBoxQualWords at the encode call's own status sync
+// (q_collect).  Mode 0 returns before anything is launched.
 int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t total, uint32_t block_reads) {
-    if (ctx->q_mode == 0 || n_reads == 0) return NTC_OK;
+    if (ctx->qual.mode == 0 || n_reads == 0) return NTC_OK;
     const uint64_t nb = (n_reads + block_reads - 1) / block_reads;
     void *quals, *blk, *pay;
     int rc;
     if ((rc = ensure(ctx, WS_Q_QUALS, total + 64, &quals))) return rc;
     // the status word, the presence maps (16 B per block), the blocks and their totals
     if ((rc = ensure(ctx, WS_Q_BLOCKS, 64 + nb * 16 + (nb + 1) * sizeof(QBlock), &blk))) return rc;
-    const bool rans = ctx->q_coder == 1;
+    const bool rans = ctx->qual.coder == 1;
     if ((rc = ensure(ctx, WS_Q_PAYLOAD, rans ? qr_payload_bytes_max(total, nb) : q_payload_words_max(total, nb) * 8, &pay)))
         return rc;
     const FastqArgs &f = ctx->fq_last;
@@ -665,16 +704,16 @@ int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t tota
     a.n_reads = n_reads;
     a.n_blocks = nb;
     a.block_reads = block_reads;
-    a.mode = (uint32_t)ctx->q_mode;
+    a.mode = (uint32_t)ctx->qual.mode;
     a.quals = (uint8_t *)quals;
     a.status = (unsigned long long *)blk;
     a.pres = (uint32_t *)((uint8_t *)blk + 64);
     a.blocks = (QBlock *)((uint8_t *)blk + 64 + nb * 16);
     a.payload = (uint64_t *)pay;
     a.box = ctx->h_box;
-    ctx->h_box[6] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
-    ctx->h_box[7] = 0;
-    ctx->q_coder_last = ctx->q_coder;
+    ctx->h_box[kBoxQualStatus] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
+    ctx->h_box[kBoxQualWords] = 0;
+    ctx->qual.coder_last = ctx->qual.coder;
     if (!rans) {
         launch_quality_pack(a, total, ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
@@ -703,8 +742,8 @@ int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t tota
 }
 // After the encode call's sync: the quality pass's verdict.  A read it refused fails the call.
 int q_collect(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads, int64_t *bad_read) {
-    if (ctx->q_mode == 0 || n_reads == 0) return NTC_OK;
-    const uint64_t st = ((volatile uint64_t *)ctx->h_box)[6];
+    if (ctx->qual.mode == 0 || n_reads == 0) return NTC_OK;
+    const uint64_t st = box(ctx, kBoxQualStatus);
     if (st != ~0ull) {
         if (bad_read) *bad_read = (int64_t)(st >> 8);
         char buf[160];
@@ -712,26 +751,15 @@ int q_collect(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads, int64_t *bad
                                         "byte lies outside '!'..'~'", (long long)(st >> 8));
         return set_err(ctx, (int)(st & 0xFF), buf);
     }
-    ctx->q_blocks = (n_reads + block_reads - 1) / block_reads;
-    ctx->q_words = ((volatile uint64_t *)ctx->h_box)[7];
-    ctx->q_reads = n_reads;
-    ctx->q_block_reads = block_reads;
+    ctx->qual.blocks = (n_reads + block_reads - 1) / block_reads;
+    ctx->qual.words = box(ctx, kBoxQualWords);
+    ctx->qual.reads = n_reads;
+    ctx->qual.block_reads = block_reads;
     return NTC_OK;
 }
 int q_unsupported(ntc_ctx *ctx, const char *call) {
     return set_err(ctx, NTC_ERR_UNSUPPORTED, std::string(call) + " takes bases without quality lines: qualities keep / "
                                              "bin8 need ntc_encode_pack_fastq");
-}
-
-// the pending sections leave the context: the call that takes them uses them once
-bool q_take_pending(ntc_ctx *ctx, std::vector<ntc_qual_meta> &metas, std::vector<uint64_t> &payload) {
-    metas.clear();
-    payload.clear();
-    if (!ctx->qd_has_pending) return false;
-    metas.swap(ctx->qd_metas);
-    payload.swap(ctx->qd_payload);
-    ctx->qd_has_pending = false;
-    return true;
 }
 
 // Decode side, coder 1 (ntc_decode_set_qualities checked every body with qr_body_ok): the
@@ -790,12 +818,8 @@ int q_rans_decode(ntc_ctx *ctx, const std::vector<ntc_qual_meta> &metas, const s
     a.status = ctx->d_status;
     launch_quality_rans_decode(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    if (ctx->box_valid && ctx->last == kDecode)
-        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
-                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
     *d_quals = (uint8_t *)quals;
-    return NTC_OK;
+    return rebox_decode(ctx);
 }
 
 // Decode side: the sections over the decoded reads' offsets -> quality bytes (WS_QD_QUALS);
@@ -840,24 +864,17 @@ int q_unpack(ntc_ctx *ctx, const std::vector<ntc_qual_meta> &metas, const std::v
     a.status = ctx->d_status;
     launch_quality_unpack(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    if (ctx->box_valid && ctx->last == kDecode)
-        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
-                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
     *d_quals = (uint8_t *)quals;
-    return NTC_OK;
+    return rebox_decode(ctx);
 }
 
 // ---- read names (names.hip) -------------------------------------------------------------
 // After a GPU FASTQ parse, beside the quality pass: measure, offsets, emit.  Asynchronous,
 // with a status word of its own; the status and the payload's size reach the host in mailbox
-// words 8 and 9 at the encode call's own status sync (n_collect).  Mode 0 returns before
-// anything is launched.
-void n_begin(ntc_ctx *ctx) {  // an encode call starts: the last call's sections are gone
-    ctx->n_blocks = ctx->n_bytes = 0;
-}
+// words kBoxNameStatus and kBoxNameBytes at the encode call's own status sync (n_collect).
+// Mode 0 returns before anything is launched.
 int n_pack(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads) {
-    if (ctx->n_mode == 0 || n_reads == 0) return NTC_OK;
+    if (ctx->names.mode == 0 || n_reads == 0) return NTC_OK;
     const uint64_t nb = (n_reads + block_reads - 1) / block_reads;
     const FastqArgs &f = ctx->fq_last;
     void *cols, *blk, *pay;
@@ -875,7 +892,7 @@ int n_pack(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads) {
     a.n_reads = n_reads;
     a.n_blocks = nb;
     a.block_reads = block_reads;
-    a.mode = (uint32_t)ctx->n_mode;
+    a.mode = (uint32_t)ctx->names.mode;
     a.len_off = (uint64_t *)cols;
     a.mid_off = a.len_off + n1;
     a.start = (uint32_t *)(a.mid_off + n1);
@@ -887,43 +904,31 @@ int n_pack(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads) {
     a.blocks = (NBlock *)((uint8_t *)blk + 64);
     a.payload = (uint8_t *)pay;
     a.box = ctx->h_box;
-    ctx->h_box[8] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
-    ctx->h_box[9] = 0;
-    ctx->n_d_start = a.start;
-    ctx->n_d_len = a.len;
+    ctx->h_box[kBoxNameStatus] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
+    ctx->h_box[kBoxNameBytes] = 0;
+    ctx->names.d_start = a.start;
+    ctx->names.d_len = a.len;
     launch_names_pack(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     return NTC_OK;
 }
 // After the encode call's sync: the names pass's verdict.  A name too long fails the call.
 int n_collect(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads, int64_t *bad_read) {
-    if (ctx->n_mode == 0 || n_reads == 0) return NTC_OK;
-    const uint64_t st = ((volatile uint64_t *)ctx->h_box)[8];
+    if (ctx->names.mode == 0 || n_reads == 0) return NTC_OK;
+    const uint64_t st = box(ctx, kBoxNameStatus);
     if (st != ~0ull) {
         if (bad_read) *bad_read = (int64_t)(st >> 8);
         char buf[160];
         std::snprintf(buf, sizeof(buf), "name of read %lld: longer than %u bytes", (long long)(st >> 8), kNMax);
         return set_err(ctx, (int)(st & 0xFF), buf);
     }
-    ctx->n_blocks = (n_reads + block_reads - 1) / block_reads;
-    ctx->n_bytes = ((volatile uint64_t *)ctx->h_box)[9];
+    ctx->names.blocks = (n_reads + block_reads - 1) / block_reads;
+    ctx->names.bytes = box(ctx, kBoxNameBytes);
     return NTC_OK;
 }
 int n_unsupported(ntc_ctx *ctx, const char *call) {
     return set_err(ctx, NTC_ERR_UNSUPPORTED, std::string(call) + " takes bases without header lines: names keep / id "
                                              "need ntc_encode_pack_fastq");
-}
-
-// the pending sections leave the context: the call that takes them uses them once
-bool n_take_pending(ntc_ctx *ctx, std::vector<ntc_name_meta> &metas, std::vector<uint64_t> &payload) {
-    metas.clear();
-    payload.clear();
-    if (!ctx->nd_has_pending) return false;
-    metas.swap(ctx->nd_metas);
-    payload.swap(ctx->nd_payload);
-    ctx->nd_has_pending = false;
-    ctx->nd_name_bytes = 0;
-    return true;
 }
 
 // Decode side: the sections -> the names of the decoded reads, read by read (WS_ND_NAMES) and
@@ -969,13 +974,9 @@ int n_expand(ntc_ctx *ctx, const std::vector<ntc_name_meta> &metas, const std::v
     a.status = ctx->d_status;
     launch_names_expand(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    if (ctx->box_valid && ctx->last == kDecode)
-        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
-                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
     *d_names = (uint8_t *)names;
     *d_name_off = a.name_off;
-    return NTC_OK;
+    return rebox_decode(ctx);
 }
 
 // ---- content digests (digest.hip) ---------------------------------------------------------
@@ -984,14 +985,11 @@ int n_expand(ntc_ctx *ctx, const std::vector<ntc_name_meta> &metas, const std::v
 // anyway.  Asynchronous, on the call's stream; option 0 launches nothing.
 static_assert(sizeof(DigestMetaDev) == sizeof(ntc_digest_meta) && sizeof(ntc_digest_meta) == 56,
               "the device table is the public meta");
-void dg_begin(ntc_ctx *ctx) {  // an encode call starts: the last call's digests are gone
-    ctx->dg_blocks = 0;
-}
 // the components a call under the context's options yields (0: digests are off)
 uint32_t dg_components(const ntc_ctx *ctx, bool fastq) {
-    if (!ctx->dg_opt) return 0;
-    return kDgSeq | (ctx->nx_policy == 2 ? kDgSym : 0) | (fastq && ctx->q_mode ? kDgQual : 0) |
-           (fastq && ctx->n_mode ? kDgName : 0);
+    if (!ctx->dig.opt) return 0;
+    return kDgSeq | (ctx->nx.policy == 2 ? kDgSym : 0) | (fastq && ctx->qual.mode ? kDgQual : 0) |
+           (fastq && ctx->names.mode ? kDgName : 0);
 }
 // the table of the call: reads and bases per block, the digests zeroed but those in keep
 int dg_init(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint32_t block_reads, uint32_t components,
@@ -1022,14 +1020,6 @@ int dg_add(ntc_ctx *ctx, uint32_t c, const void *buf, uint64_t buf_bytes, const 
     return NTC_OK;
 }
 
-// Decode side: the expected digests leave the context with the call that takes them
-bool dg_take_pending(ntc_ctx *ctx, std::vector<ntc_digest_meta> &metas) {
-    metas.clear();
-    if (!ctx->dd_has_pending) return false;
-    metas.swap(ctx->dd_metas);
-    ctx->dd_has_pending = false;
-    return true;
-}
 // The decode call in flight: expected and computed tables and the blocks' first reads on the
 // device (WS_DGD_IN); the runs of sections of one size, each of which is one launch_digest
 struct DgDecode {
@@ -1049,10 +1039,10 @@ int dgd_begin(ntc_ctx *ctx, const std::vector<ntc_digest_meta> &exp, DgDecode &d
         d.groups.emplace_back(b, e);
         b = e;
     }
-    ctx->dd_expected = exp;
-    ctx->dd_checkable = 0;
-    ctx->dd_computed.assign(nb, ntc_digest_meta{});
-    for (uint64_t b = 0; b < nb; b++) ctx->dd_computed[b].n_reads = exp[b].n_reads;
+    ctx->dig.expected = exp;
+    ctx->dig.checkable = 0;
+    ctx->dig.computed.assign(nb, ntc_digest_meta{});
+    for (uint64_t b = 0; b < nb; b++) ctx->dig.computed[b].n_reads = exp[b].n_reads;
     void *in;
     int rc;
     const uint64_t tb = nb * sizeof(DigestMetaDev);
@@ -1061,7 +1051,7 @@ int dgd_begin(ntc_ctx *ctx, const std::vector<ntc_digest_meta> &exp, DgDecode &d
     d.computed = d.expected + nb;
     d.r0 = (uint64_t *)(d.computed + nb);
     HIP_TRY(ctx, hipMemcpy(d.expected, exp.data(), tb, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d.computed, ctx->dd_computed.data(), tb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d.computed, ctx->dig.computed.data(), tb, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(d.r0, d.first.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
     return NTC_OK;
 }
@@ -1075,7 +1065,7 @@ int dgd_add(ntc_ctx *ctx, DgDecode &d, uint32_t c, const void *buf, uint64_t buf
         a.offs = offs + d.first[g.first];
         a.origin = offs;
         a.n_reads = d.first[g.second] - d.first[g.first];
-        a.block_reads = (uint32_t)ctx->dd_expected[g.first].n_reads;
+        a.block_reads = (uint32_t)ctx->dig.expected[g.first].n_reads;
         a.out = d.computed[g.first].d + c;
         a.out_stride = sizeof(DigestMetaDev) / 8;
         a.status = ctx->d_status;
@@ -1091,20 +1081,17 @@ int dgd_compare(ntc_ctx *ctx, DgDecode &d, uint64_t n_reads, const uint64_t *d_o
     a.expected = d.expected;
     a.computed = d.computed;
     a.r0 = d.r0;
-    a.n_blocks = ctx->dd_expected.size();
+    a.n_blocks = ctx->dig.expected.size();
     a.n_reads = n_reads;
     a.offs = d_offs;
     a.checkable = d.checkable;
     a.status = ctx->d_status;
     launch_digest_compare(a, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    if (ctx->box_valid && ctx->last == kDecode)
-        launch_status_box(ctx->d_status, ctx->last_out_offs + ctx->last_n,
-                          ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, nullptr, ctx->h_box, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dd_computed.data(), d.computed, a.n_blocks * sizeof(DigestMetaDev),
+    if (const int rc = rebox_decode(ctx)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dig.computed.data(), d.computed, a.n_blocks * sizeof(DigestMetaDev),
                                 hipMemcpyDeviceToHost, ctx->stream));
-    ctx->dd_checkable = d.checkable;
+    ctx->dig.checkable = d.checkable;
     return NTC_OK;
 }
 // After the call's synchronisation: which components were checked, and for NTC_ERR_DIGEST the
@@ -1112,9 +1099,9 @@ int dgd_compare(ntc_ctx *ctx, DgDecode &d, uint64_t n_reads, const uint64_t *d_o
 int dgd_verdict(ntc_ctx *ctx, int rc) {
     static const char *const names[4] = {"seq", "sym", "qual", "name"};
     std::string msg;
-    for (size_t b = 0; b < ctx->dd_expected.size(); b++) {
-        ntc_digest_meta &e = ctx->dd_expected[b], &g = ctx->dd_computed[b];
-        const uint32_t check = e.components & ctx->dd_checkable;
+    for (size_t b = 0; b < ctx->dig.expected.size(); b++) {
+        ntc_digest_meta &e = ctx->dig.expected[b], &g = ctx->dig.computed[b];
+        const uint32_t check = e.components & ctx->dig.checkable;
         g.components = check;
         g.reserved = 0;
         const uint64_t ed[4] = {e.d_seq, e.d_sym, e.d_qual, e.d_name}, gd[4] = {g.d_seq, g.d_sym, g.d_qual, g.d_name};
@@ -1296,7 +1283,7 @@ int ntc_ctx_create(int device, ntc_ctx **out) {
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void **)&ctx->d_status, 64) != hipSuccess ||
-        hipHostMalloc((void **)&ctx->h_box, 128, hipHostMallocDefault) != hipSuccess) {
+        hipHostMalloc((void **)&ctx->h_box, kBoxWords * 8, hipHostMallocDefault) != hipSuccess) {
         delete ctx;
         return NTC_ERR_HIP;
     }
@@ -1448,63 +1435,91 @@ int ntc_index_upload(ntc_ctx *ctx, const ntc_index_view *v) {
 }  // extern "C"
 
 namespace {
-int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
-    const HostIndex &hx = prep.hx;
-    const Derived &dv = prep.dv;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t_start = std::chrono::steady_clock::now();
-    auto us_since = [&] {
-        return prep.host_us + (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(
-                                  std::chrono::steady_clock::now() - t_start).count();
-    };
-    ctx->upload_host_us = prep.host_us;
-    // NTC_UPLOAD_TRACE=1: seconds since the start of the device half at each stage (stderr)
-    static const bool trace = std::getenv("NTC_UPLOAD_TRACE") != nullptr;
-    auto mark = [&](const char *what, bool sync) {
-        if (!trace) return;
-        if (sync) (void)hipStreamSynchronize(ctx->stream);
-        std::fprintf(stderr, "[upload] %-28s %.4f s\n", what,
-                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
-    };
-    // free a previous index
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->index_mem = std::make_shared<IndexMem>(ctx->device);  // the previous one goes with its last holder
-    ctx->has_index = false;
-    ctx->index_bytes = 0;
-    const uint64_t n = hx.n;
-    auto dalloc = [&](uint64_t bytes, void **p) -> int {
+// ---- the device half of an upload -----------------------------------------------------------
+// One upload in flight: what its stages (up_*, below in the order they run) hand to one another.
+struct Upload {
+    ntc_ctx *ctx;
+    const HostIndex &hx;
+    const Derived &dv;
+    const uint64_t n;  // nodes
+    const int64_t host_us;
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    // the raw arrays of the index, and the walk build's inputs and buffers (freed after the path cover)
+    void *d_lines = nullptr, *d_lcs = nullptr, *d_uniq = nullptr, *d_walk = nullptr;
+    void *d_walk_a = nullptr, *d_walk_b = nullptr, *d_pred = nullptr, *d_code = nullptr;
+    // the path cover: has_paths says that it was built and fits 31 bits
+    void *d_pstream = nullptr, *d_colex_at = nullptr, *d_pos = nullptr, *d_puniq = nullptr;
+    bool has_paths = false;
+    uint64_t tlen = 0, n_paths = 0;
+    // the suffix table: levels 1..U, its presence bits, those of the filter level (F != 0)
+    uint32_t U = 0;
+    void *d_tab = nullptr, *d_bits = nullptr, *d_fbits = nullptr;
+
+    Upload(ntc_ctx *c, const ntc_index_prep &p) : ctx(c), hx(p.hx), dv(p.dv), n(p.hx.n), host_us(p.host_us) {}
+    // memory of the index itself: freed with the last context that holds it
+    int dalloc(uint64_t bytes, void **p) {
         HIP_TRY(ctx, hipMalloc(p, bytes));
         ctx->index_mem->ptrs.push_back(*p);
         ctx->index_bytes += bytes;
         return NTC_OK;
-    };
-    void *d_lines, *d_lcs, *d_uniq, *d_walk, *d_walk_a, *d_walk_b, *d_pred, *d_code;
+    }
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
+    // NTC_UPLOAD_TRACE=1: seconds since the start of the device half at each stage (stderr)
+    void mark(const char *what, bool sync) const {
+        static const bool trace = std::getenv("NTC_UPLOAD_TRACE") != nullptr;
+        if (!trace) return;
+        if (sync) (void)hipStreamSynchronize(ctx->stream);
+        std::fprintf(stderr, "[upload] %-28s %.4f s\n", what, seconds());
+    }
+};
+
+int up_free_previous(Upload &u) {
+    ntc_ctx *ctx = u.ctx;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->index_mem = std::make_shared<IndexMem>(ctx->device);  // the previous one goes with its last holder
+    ctx->has_index = false;
+    ctx->index_bytes = 0;
+    return NTC_OK;
+}
+
+int up_raw_arrays(Upload &u) {
+    ntc_ctx *ctx = u.ctx;
+    const uint64_t n = u.n;
     int rc;
-    if ((rc = dalloc(dv.rank.size() * sizeof(uint2), &d_lines))) return rc;
-    if ((rc = dalloc(n + 256, &d_lcs))) return rc;
-    if ((rc = dalloc(dv.uniq.size() * 4, &d_uniq))) return rc;
-    if ((rc = dalloc(n * sizeof(WalkEntry), &d_walk))) return rc;
-    HIP_TRY(ctx, hipMalloc(&d_walk_a, n * sizeof(WalkStep)));
-    HIP_TRY(ctx, hipMalloc(&d_walk_b, n * sizeof(WalkStep)));
-    HIP_TRY(ctx, hipMalloc(&d_pred, n * 4));
-    HIP_TRY(ctx, hipMalloc(&d_code, n + 64));
-    HIP_TRY(ctx, hipMemcpy(d_lines, dv.rank.data(), dv.rank.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemset(d_lcs, 0, n + 256));
-    HIP_TRY(ctx, hipMemcpy(d_lcs, hx.lcs.data(), n, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_uniq, dv.uniq.data(), dv.uniq.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_pred, dv.pred.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_code, dv.code.data(), n, hipMemcpyHostToDevice));
-    mark("allocations + H2D", false);
-    launch_walk_build((const uint32_t *)d_pred, (const uint8_t *)d_code, n, (WalkStep *)d_walk_a,
-                      (WalkStep *)d_walk_b, (WalkEntry *)d_walk, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    mark("walk table", true);
-    // path cover, built on the device (kernels.hip "path cover"; derived.cpp build_paths is
-    // the same cover on the host, for emulation)
-    void *d_pstream = nullptr, *d_colex_at = nullptr, *d_pos = nullptr, *d_puniq = nullptr;
-    bool has_paths = false;
-    uint64_t tlen = 0, n_paths = 0;
-    const bool dec_only = ctx->decode_only_opt != 0;
+    if ((rc = u.dalloc(u.dv.rank.size() * sizeof(uint2), &u.d_lines))) return rc;
+    if ((rc = u.dalloc(n + 256, &u.d_lcs))) return rc;
+    if ((rc = u.dalloc(u.dv.uniq.size() * 4, &u.d_uniq))) return rc;
+    if ((rc = u.dalloc(n * sizeof(WalkEntry), &u.d_walk))) return rc;
+    HIP_TRY(ctx, hipMalloc(&u.d_walk_a, n * sizeof(WalkStep)));
+    HIP_TRY(ctx, hipMalloc(&u.d_walk_b, n * sizeof(WalkStep)));
+    HIP_TRY(ctx, hipMalloc(&u.d_pred, n * 4));
+    HIP_TRY(ctx, hipMalloc(&u.d_code, n + 64));
+    HIP_TRY(ctx, hipMemcpy(u.d_lines, u.dv.rank.data(), u.dv.rank.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset(u.d_lcs, 0, n + 256));
+    HIP_TRY(ctx, hipMemcpy(u.d_lcs, u.hx.lcs.data(), n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(u.d_uniq, u.dv.uniq.data(), u.dv.uniq.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(u.d_pred, u.dv.pred.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(u.d_code, u.dv.code.data(), n, hipMemcpyHostToDevice));
+    u.mark("allocations + H2D", false);
+    return NTC_OK;
+}
+
+int up_walk_table(Upload &u) {
+    launch_walk_build((const uint32_t *)u.d_pred, (const uint8_t *)u.d_code, u.n, (WalkStep *)u.d_walk_a,
+                      (WalkStep *)u.d_walk_b, (WalkEntry *)u.d_walk, u.ctx->stream);
+    HIP_TRY(u.ctx, hipGetLastError());
+    u.mark("walk table", true);
+    return NTC_OK;
+}
+
+// path cover, built on the device (kernels.hip "path cover"; derived.cpp build_paths is the
+// same cover on the host, for emulation); a decode-only upload has none
+int up_path_cover(Upload &u, bool dec_only) {
+    ntc_ctx *ctx = u.ctx;
+    const HostIndex &hx = u.hx;
+    const Derived &dv = u.dv;
+    const uint64_t n = u.n;
+    int rc;
     ctx->index_decode_only = false;
     if (!dec_only && n < (1ULL << 31)) {
         const std::vector<uint8_t> dummy = dummy_nodes(hx, dv);
@@ -1531,9 +1546,9 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
             return rc;
         }
         HIP_TRY(ctx, hipMemcpy(d_dummy, dbits.data(), dbits.size() * 4, hipMemcpyHostToDevice));
-        PathArgs pa{(const uint2 *)d_lines, dv.rwords, (uint32_t)n, hx.k, (const uint8_t *)d_lcs,
-                    (const uint32_t *)d_dummy, (const uint32_t *)d_pred, (const uint8_t *)d_code,
-                    (const uint32_t *)d_uniq};
+        PathArgs pa{(const uint2 *)u.d_lines, dv.rwords, (uint32_t)n, hx.k, (const uint8_t *)u.d_lcs,
+                    (const uint32_t *)d_dummy, (const uint32_t *)u.d_pred, (const uint8_t *)u.d_code,
+                    (const uint32_t *)u.d_uniq};
         uint32_t *prv = (uint32_t *)d_prv, *cnt = (uint32_t *)d_cnt;
         HIP_TRY(ctx, hipMemsetAsync(prv, 0xFF, n * 4, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 16, ctx->stream));
@@ -1562,94 +1577,91 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
         launch_path_lengths(pa, st, prv, (uint32_t *)d_len, (uint32_t *)d_vals, cnt + 1, ctx->stream);
         scan_excl_u32((const uint32_t *)d_vals, n, (uint64_t *)d_base, (uint64_t *)d_stmp, ctx->stream);
         uint32_t np32 = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&tlen, (uint64_t *)d_base + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&u.tlen, (uint64_t *)d_base + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(&np32, cnt + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipGetLastError());
-        n_paths = np32;
+        u.n_paths = np32;
+        const uint64_t tlen = u.tlen;
         if (tlen + 64 < (1ULL << 31)) {
             // sizes as derived.cpp build_paths: groups read up to k + 64 characters past a node
             const uint64_t n_groups = (tlen + hx.k) / 32 + 8, n_colex = tlen + 8, n_puniq = tlen / 64 + 4;
-            if ((rc = dalloc(n_puniq * 8, &d_puniq)) || (rc = dalloc(n_groups * 16, &d_pstream)) ||
-                (rc = dalloc(n_colex * 4 + 64, &d_colex_at)) || (rc = dalloc(n * 4, &d_pos))) {
+            if ((rc = u.dalloc(n_puniq * 8, &u.d_puniq)) || (rc = u.dalloc(n_groups * 16, &u.d_pstream)) ||
+                (rc = u.dalloc(n_colex * 4 + 64, &u.d_colex_at)) || (rc = u.dalloc(n * 4, &u.d_pos))) {
                 free_tmp();
                 return rc;
             }
-            HIP_TRY(ctx, hipMemsetAsync(d_puniq, 0, n_puniq * 8, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(d_pstream, 0, n_groups * 16, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(d_colex_at, 0xFF, n_colex * 4 + 64, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(d_pos, 0xFF, n * 4, ctx->stream));
-            launch_path_place(pa, st, prv, (const uint64_t *)d_base, (uint32_t *)d_colex_at, (uint32_t *)d_pos,
-                              (uint4 *)d_pstream, (uint64_t *)d_puniq, ctx->stream);
+            HIP_TRY(ctx, hipMemsetAsync(u.d_puniq, 0, n_puniq * 8, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(u.d_pstream, 0, n_groups * 16, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(u.d_colex_at, 0xFF, n_colex * 4 + 64, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(u.d_pos, 0xFF, n * 4, ctx->stream));
+            launch_path_place(pa, st, prv, (const uint64_t *)d_base, (uint32_t *)u.d_colex_at, (uint32_t *)u.d_pos,
+                              (uint4 *)u.d_pstream, (uint64_t *)u.d_puniq, ctx->stream);
             if (hx.k >= kForkBlockMinK)
-                launch_path_forks(pa, st, (const uint32_t *)d_len, (const uint64_t *)d_base, (const uint32_t *)d_pos,
-                                  (const uint4 *)d_pstream, (uint32_t *)d_colex_at, ctx->stream);
+                launch_path_forks(pa, st, (const uint32_t *)d_len, (const uint64_t *)d_base, (const uint32_t *)u.d_pos,
+                                  (const uint4 *)u.d_pstream, (uint32_t *)u.d_colex_at, ctx->stream);
             HIP_TRY(ctx, hipGetLastError());
-            has_paths = true;
+            u.has_paths = true;
         }
         free_tmp();
     }
-    mark("path cover", true);
+    u.mark("path cover", true);
+    // the walk build's inputs served the cover too: both are done with them
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(d_walk_a));
-    HIP_TRY(ctx, hipFree(d_walk_b));
-    HIP_TRY(ctx, hipFree(d_pred));
-    HIP_TRY(ctx, hipFree(d_code));
+    HIP_TRY(ctx, hipFree(u.d_walk_a));
+    HIP_TRY(ctx, hipFree(u.d_walk_b));
+    HIP_TRY(ctx, hipFree(u.d_pred));
+    HIP_TRY(ctx, hipFree(u.d_code));
+    return NTC_OK;
+}
+
+// the context's DevIndex so far, and the choice between the two k_ms4 builds
+int up_joint_choice(Upload &u) {
+    ntc_ctx *ctx = u.ctx;
+    const bool has_paths = u.has_paths;
     DevIndex &d = ctx->dix;
-    d.rank = (const uint2 *)d_lines;
-    d.lcs = (const uint8_t *)d_lcs;
-    d.uniq = (const uint32_t *)d_uniq;
-    d.walk = (const WalkEntry *)d_walk;
-    d.rwords = dv.rwords;
-    d.n = (uint32_t)n;
-    d.k = hx.k;
-    d.t_jump = dv.t_jump;
-    for (int c = 0; c < 5; c++) d.C[c] = dv.C[c];
+    d = DevIndex{};  // (what the stages after this one do not build stays null / 0)
+    d.rank = (const uint2 *)u.d_lines;
+    d.lcs = (const uint8_t *)u.d_lcs;
+    d.uniq = (const uint32_t *)u.d_uniq;
+    d.walk = (const WalkEntry *)u.d_walk;
+    d.rwords = u.dv.rwords;
+    d.n = (uint32_t)u.n;
+    d.k = u.hx.k;
+    d.t_jump = u.dv.t_jump;
+    for (int c = 0; c < 5; c++) d.C[c] = u.dv.C[c];
     d.has_paths = has_paths ? 1u : 0u;
-    d.path_len = has_paths ? (uint32_t)tlen : 0u;
-    d.pstream = (const uint4 *)d_pstream;
-    d.colex_at = (const uint32_t *)d_colex_at;
-    d.pos_of_node = (const uint32_t *)d_pos;
-    d.puniq = (const uint64_t *)d_puniq;
-    d.forks = has_paths && hx.k >= kForkBlockMinK ? 1u : 0u;
-    d.absent = dv.absent;
+    d.path_len = has_paths ? (uint32_t)u.tlen : 0u;
+    d.pstream = (const uint4 *)u.d_pstream;
+    d.colex_at = (const uint32_t *)u.d_colex_at;
+    d.pos_of_node = (const uint32_t *)u.d_pos;
+    d.puniq = (const uint64_t *)u.d_puniq;
+    d.forks = has_paths && u.hx.k >= kForkBlockMinK ? 1u : 0u;
+    d.absent = u.dv.absent;
     // Joint path runs pay off when MS intervals above U hold several nodes for long stretches:
     // genome collections, whose shared regions split the path cover into short unitigs (S91:
     // 1.19 M paths over 70 M nodes).  A cover of long paths (one genome, C91: 2 paths) keeps
     // the lighter k_ms4 build.
-    d.joint = has_paths && (ctx->joint_opt == 1 || (ctx->joint_opt < 0 && (uint64_t)n_paths * kJointAutoNodesPerPath > n))
+    d.joint = has_paths && (ctx->joint_opt == 1 || (ctx->joint_opt < 0 && u.n_paths * kJointAutoNodesPerPath > u.n))
                   ? 1u : 0u;
-    if (dec_only) {  // decode reads the walk table alone: no suffix table, SCAN words or rank chunks
-        d.rank2 = nullptr;
-        d.tab = nullptr;
-        d.tab_bits = nullptr;
-        d.filt_bits = nullptr;
-        d.filt_f = 0;
-        d.pair_w = nullptr;
-        d.win_w = nullptr;
-        d.tab_u = 0;
-        d.tab_pos = 0;
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->n_paths = 0;
-        ctx->path_text_len = 0;
-        ctx->index_decode_only = true;
-        ctx->subst_built = 0;
-        ctx->has_index = true;
-        mark("done (decode only)", false);
-        ctx->upload_total_us = us_since();
-        return NTC_OK;
-    }
-    d.rank2 = nullptr;
-    if (ctx->ext2_opt) {  // two-character rank lines (8 B per node)
+    return NTC_OK;
+}
+
+// suffix table, levels 1..U, built on the device from the rank lines (and before it, under the
+// A/B option ext2, the two-character rank lines: 8 B per node)
+int up_suffix_table(Upload &u) {
+    ntc_ctx *ctx = u.ctx;
+    DevIndex &d = ctx->dix;
+    const uint64_t n = u.n;
+    int rc;
+    if (ctx->ext2_opt) {
         void *d_r2;
-        if ((rc = dalloc(rank2_blocks(n) * 4 * sizeof(Rank2Chunk), &d_r2))) return rc;
+        if ((rc = u.dalloc(rank2_blocks(n) * 4 * sizeof(Rank2Chunk), &d_r2))) return rc;
         launch_rank2(d, (Rank2Chunk *)d_r2, ctx->stream);
         d.rank2 = (const Rank2Chunk *)d_r2;
     }
-    // suffix table, levels 1..U, built on the device from the rank lines
-    uint32_t U = ctx->tab_u_opt ? std::min<uint32_t>(ctx->tab_u_opt, std::min<uint32_t>(hx.k, kTabMaxU))
-                                : default_tab_u(n, hx.k, hx.lcs.data());
+    uint32_t U = ctx->tab_u_opt ? std::min<uint32_t>(ctx->tab_u_opt, std::min<uint32_t>(u.hx.k, kTabMaxU))
+                                : default_tab_u(n, u.hx.k, u.hx.lcs.data());
     ctx->tab_u_fallback = 0;
     if (!ctx->tab_u_opt && U > 14) {
         // the density rule's deeper table (U = 15: 11.5 GB against 2.9 GB) only where it fits
@@ -1661,30 +1673,37 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
             ctx->tab_u_fallback = 1;
         }
     }
-    void *d_tab, *d_bits, *d_fbits = nullptr;
-    if (hipMalloc(&d_tab, tab_base(U + 1) * sizeof(uint2)) != hipSuccess) {
+    if (hipMalloc(&u.d_tab, tab_base(U + 1) * sizeof(uint2)) != hipSuccess) {
         (void)hipGetLastError();
         if (ctx->tab_u_opt || U <= 14) return set_err(ctx, NTC_ERR_HIP, "suffix table allocation failed");
         U = 14;  // allocation failed at the deeper level: fall back (results never depend on U)
         ctx->tab_u_fallback = 1;
-        if ((rc = dalloc(tab_base(U + 1) * sizeof(uint2), &d_tab))) return rc;
+        if ((rc = u.dalloc(tab_base(U + 1) * sizeof(uint2), &u.d_tab))) return rc;
     } else {
-        ctx->index_mem->ptrs.push_back(d_tab);
+        ctx->index_mem->ptrs.push_back(u.d_tab);
         ctx->index_bytes += tab_base(U + 1) * sizeof(uint2);
     }
     const uint32_t F = filter_level(U);
-    if ((rc = dalloc(tab_bits_words(U) * 4, &d_bits))) return rc;
-    if (F && (rc = dalloc(tab_bits_words(F) * 4, &d_fbits))) return rc;
-    d.tab = (const uint2 *)d_tab;
-    d.tab_bits = (const uint32_t *)d_bits;
-    d.filt_bits = (const uint32_t *)d_fbits;
+    if ((rc = u.dalloc(tab_bits_words(U) * 4, &u.d_bits))) return rc;
+    if (F && (rc = u.dalloc(tab_bits_words(F) * 4, &u.d_fbits))) return rc;
+    d.tab = (const uint2 *)u.d_tab;
+    d.tab_bits = (const uint32_t *)u.d_bits;
+    d.filt_bits = (const uint32_t *)u.d_fbits;
     d.filt_f = F;
-    d.tab_u = U;
-    d.tab_pos = (has_paths && U >= dv.t_jump && n < (1ULL << 31)) ? 1u : 0u;
-    mark("suffix table allocation", false);
-    launch_tab_build(d, U, (uint2 *)d_tab, (uint32_t *)d_bits, F, (uint32_t *)d_fbits, ctx->stream);
-    mark("suffix table", true);
-    d.win_w = nullptr;
+    d.tab_u = u.U = U;
+    d.tab_pos = (u.has_paths && U >= u.dv.t_jump && n < (1ULL << 31)) ? 1u : 0u;
+    u.mark("suffix table allocation", false);
+    launch_tab_build(d, U, (uint2 *)u.d_tab, (uint32_t *)u.d_bits, F, (uint32_t *)u.d_fbits, ctx->stream);
+    u.mark("suffix table", true);
+    return NTC_OK;
+}
+
+// what a SCAN reads: window words, the pre-filter's verdict, pair words
+int up_scan_words(Upload &u) {
+    ntc_ctx *ctx = u.ctx;
+    DevIndex &d = ctx->dix;
+    const uint32_t U = u.U, F = d.filt_f;
+    int rc;
     // SCAN window words (a (U-3)-mer keyed 32-byte entry answers four positions): two lines
     // answer the eight positions of a SCAN unit.  k_ms4 is bound by its lane loads in the
     // CU's vector memory path (TA/TD 93-96 % busy at C91, TCP stalled on pending L2 data), and
@@ -1693,8 +1712,8 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
     const bool win_on = U >= 4 && ctx->win_opt != 0;
     if (win_on) {
         void *d_win;
-        if ((rc = dalloc(win_words_count(U) * 32, &d_win))) return rc;
-        launch_win_words((const uint32_t *)d_bits, U, (uint32_t *)d_win, ctx->stream);
+        if ((rc = u.dalloc(win_words_count(U) * 32, &d_win))) return rc;
+        launch_win_words((const uint32_t *)u.d_bits, U, (uint32_t *)d_win, ctx->stream);
         d.win_w = (const uint32_t *)d_win;
     }
     ctx->filter_density_ppm = -1;
@@ -1703,7 +1722,7 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
         // and passes most positions, so it costs more lines than it saves: auto mode drops it
         // above kFiltMaxDensityPpm (every SCAN then goes straight to the exact pair words).
         std::vector<uint32_t> fb(tab_bits_words(F));
-        HIP_TRY(ctx, hipMemcpyAsync(fb.data(), d_fbits, fb.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(fb.data(), u.d_fbits, fb.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         uint64_t ones = 0;
         for (uint32_t x : fb) ones += (uint64_t)__builtin_popcount(x);
@@ -1713,31 +1732,208 @@ int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
                         (ctx->filter_opt < 0 && !win_on && ctx->filter_density_ppm <= kFiltMaxDensityPpm);
         if (!on) d.filt_f = 0;
     }
-    d.pair_w = nullptr;
     if (ctx->pair_bytes_opt) {
         void *d_pair;
-        if ((rc = dalloc((pair_words_count(U) + 1) / 2 * 4, &d_pair))) return rc;
-        launch_pair_words((const uint2 *)d_tab + tab_base(U), U, (uint16_t *)d_pair, ctx->stream);
+        if ((rc = u.dalloc((pair_words_count(U) + 1) / 2 * 4, &d_pair))) return rc;
+        launch_pair_words((const uint2 *)u.d_tab + tab_base(U), U, (uint16_t *)d_pair, ctx->stream);
         d.pair_w = (const uint16_t *)d_pair;
     }
-    // substitution words (encode_core.h subst_clean), the fourth word of each path-stream
-    // group: k_ms4 without joint runs skips the SCAN after a run break at a set bit
+    return NTC_OK;
+}
+
+// substitution words (encode_core.h subst_clean), the fourth word of each path-stream group:
+// k_ms4 without joint runs skips the SCAN after a run break at a set bit
+int up_subst_words(Upload &u) {
+    ntc_ctx *ctx = u.ctx;
+    const DevIndex &d = ctx->dix;
     ctx->subst_built = 0;
-    if (has_paths) {
-        mark("SCAN words", true);
-        const bool on = ctx->subst_opt != 0 && !d.joint && d.tab_pos && U >= 4;
-        launch_subst_words(d, (uint4 *)d_pstream, pstream_groups(tlen, hx.k), on, ctx->stream);
+    if (u.has_paths) {
+        u.mark("SCAN words", true);
+        const bool on = ctx->subst_opt != 0 && !d.joint && d.tab_pos && u.U >= 4;
+        launch_subst_words(d, (uint4 *)u.d_pstream, pstream_groups(u.tlen, u.hx.k), on, ctx->stream);
         ctx->subst_built = on ? 1 : 0;
-        mark("substitution words", true);
+        u.mark("substitution words", true);
     }
+    return NTC_OK;
+}
+
+int up_finish(Upload &u, bool dec_only) {
+    ntc_ctx *ctx = u.ctx;
+    // (decode reads the walk table alone: no suffix table, SCAN words or rank chunks)
+    if (dec_only) ctx->subst_built = 0;
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->n_paths = n_paths;
-    ctx->path_text_len = tlen;
+    ctx->n_paths = u.n_paths;  // (a decode-only upload built no cover: both are 0)
+    ctx->path_text_len = u.tlen;
+    ctx->index_decode_only = dec_only;
     ctx->has_index = true;
-    mark("done", false);
-    ctx->upload_total_us = us_since();
+    u.mark(dec_only ? "done (decode only)" : "done", false);
+    ctx->upload_total_us = u.host_us + (int64_t)(u.seconds() * 1e6);
     return NTC_OK;
+}
+
+int upload_prepared(ntc_ctx *ctx, const ntc_index_prep &prep) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Upload u(ctx, prep);
+    ctx->upload_host_us = prep.host_us;
+    const bool dec_only = ctx->decode_only_opt != 0;
+    int rc;
+    if ((rc = up_free_previous(u)) || (rc = up_raw_arrays(u)) || (rc = up_walk_table(u)) ||
+        (rc = up_path_cover(u, dec_only)) || (rc = up_joint_choice(u)))
+        return rc;
+    if (!dec_only && ((rc = up_suffix_table(u)) || (rc = up_scan_words(u)) || (rc = up_subst_words(u)))) return rc;
+    return up_finish(u, dec_only);
+}
+}  // namespace
+
+// ---- context options ----------------------------------------------------------------------
+// One table drives ntc_ctx_set_option and ntc_ctx_get_option.  A row with a setter accepts the
+// values lo..hi that its rule allows and answers msg to any other; a row without one is
+// read-only (to set_option it is an unknown option), one without a getter write-only.
+namespace {
+enum OptRule { kInRange, kEndsOnly, kMultipleOf4 };
+struct Option {
+    const char *key;
+    int64_t lo, hi;
+    OptRule rule;
+    const char *msg;
+    int (*set)(ntc_ctx *, int64_t);
+    int (*get)(const ntc_ctx *, int64_t *);
+};
+constexpr int64_t kNoMax = INT64_MAX;
+
+// an action: copies of `value` bytes each way, now
+int warm_dma(ntc_ctx *ctx, int64_t value) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, (size_t)value, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(ctx, NTC_ERR_HIP, "warm_dma: pinned allocation failed");
+    }
+    int rc = ensure(ctx, WS_STAGE_BASES, (uint64_t)value, &d);
+    if (rc == NTC_OK) {
+        if (hipMemcpyAsync(h, d, (size_t)value, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(d, h, (size_t)value, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = set_err(ctx, NTC_ERR_HIP, "warm_dma: copy failed");
+        }
+    }
+    (void)hipHostFree(h);
+    return rc;
+}
+// test hook: overflow pools per read (entries, records)
+int set_pool_per_read(ntc_ctx *ctx, int64_t value) {
+    ctx->epool_per_read = ctx->rpool_per_read = (double)value;
+    ctx->epool_per_base = ctx->rpool_per_base = 0.0;
+    return NTC_OK;
+}
+// test hook: derived.h subst_word_hash of the device words
+int get_subst_hash(const ntc_ctx *ctx, int64_t *value) {
+    if (!ctx->has_index || !ctx->dix.has_paths) return NTC_ERR_NO_INDEX;
+    std::vector<uint4> ps(pstream_groups(ctx->path_text_len, ctx->dix.k));
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(ps.data(), ctx->dix.pstream, ps.size() * 16, hipMemcpyDeviceToHost) != hipSuccess)
+        return NTC_ERR_HIP;
+    *value = (int64_t)subst_word_hash(ps.data(), ps.size());
+    return NTC_OK;
+}
+// test hook: derived.h path_cover_hash of the device cover
+int get_path_hash(const ntc_ctx *ctx, int64_t *value) {
+    if (!ctx->has_index || !ctx->dix.has_paths) return NTC_ERR_NO_INDEX;
+    const uint64_t n = ctx->dix.n, k = ctx->dix.k, tlen = ctx->path_text_len;
+    std::vector<uint4> ps((tlen + k) / 32 + 8);
+    std::vector<uint32_t> ca(tlen + 8), pn(n);
+    std::vector<uint64_t> pu(tlen / 64 + 4);
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(ps.data(), ctx->dix.pstream, ps.size() * 16, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(ca.data(), ctx->dix.colex_at, ca.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(pn.data(), ctx->dix.pos_of_node, pn.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(pu.data(), ctx->dix.puniq, pu.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return NTC_ERR_HIP;
+    *value = (int64_t)path_cover_hash(ps.data(), ca.data(), pn.data(), pu.data(), n, (uint32_t)k, tlen);
+    return NTC_OK;
+}
+// test hooks dev_*: device address of a derived array, 0 = not built
+int get_dev_addr(const ntc_ctx *ctx, const void *p, int64_t *value) {
+    if (!ctx->has_index) return NTC_ERR_NO_INDEX;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return NTC_ERR_HIP;
+    *value = (int64_t)(uintptr_t)p;
+    return NTC_OK;
+}
+// device workspace held now (all slots)
+int get_workspace_bytes(const ntc_ctx *ctx, int64_t *value) {
+    uint64_t t = 0;
+    for (const auto &b : ctx->ws) t += b.bytes;
+    *value = (int64_t)t;
+    return NTC_OK;
+}
+
+#define OPT_SET(member) [](ntc_ctx *c, int64_t v) { c->member = (decltype(c->member))v; return (int)NTC_OK; }
+#define OPT_GET(expr) [](const ntc_ctx *c, int64_t *v) { *v = (int64_t)(expr); return (int)NTC_OK; }
+// a plain option: get returns what set stored
+#define OPT_VALUE(member) OPT_SET(member), OPT_GET(c->member)
+// an option of the next ntc_index_upload: get returns what the index in use was built with
+#define OPT_UPLOAD(member, built) OPT_SET(member), OPT_GET(c->has_index ? (int64_t)(built) : (int64_t)c->member)
+#define OPT_READ(key, expr) {key, 0, 0, kInRange, nullptr, nullptr, OPT_GET(expr)}
+#define OPT_DEV(f) {"dev_" #f, 0, 0, kInRange, nullptr, nullptr, \
+                    [](const ntc_ctx *c, int64_t *v) { return get_dev_addr(c, c->dix.f, v); }}
+
+const Option kOptions[] = {
+    {"encode_variant", 1, 4, kEndsOnly, "encode_variant must be 4 (default) or 1 (A/B baseline)", OPT_VALUE(encode_variant)},
+    {"tab_u", 0, kTabMaxU, kInRange, "tab_u must be 0 (default) or 1..15", OPT_UPLOAD(tab_u_opt, c->dix.tab_u)},
+    {"pair_bytes", 0, 1, kInRange, "pair_bytes must be 0 or 1", OPT_UPLOAD(pair_bytes_opt, c->dix.pair_w != nullptr)},
+    {"filter", -1, 1, kInRange, "filter must be -1 (auto), 0 or 1", OPT_UPLOAD(filter_opt, c->dix.filt_f != 0)},
+    {"joint", -1, 1, kInRange, "joint must be -1 (auto), 0 or 1", OPT_UPLOAD(joint_opt, c->dix.joint)},
+    {"path_link", 0, 1, kInRange, "path_link must be 0 or 1", OPT_VALUE(path_link_opt)},
+    {"win", -1, 1, kInRange, "win must be -1 (auto), 0 or 1", OPT_UPLOAD(win_opt, c->dix.win_w != nullptr)},
+    {"subst", -1, 0, kInRange, "subst must be -1 (auto) or 0", OPT_UPLOAD(subst_opt, c->subst_built)},
+    {"decode_only", 0, 1, kInRange, "decode_only must be 0 or 1", OPT_UPLOAD(decode_only_opt, c->index_decode_only)},
+    {"ext2", 0, 1, kInRange, "ext2 must be 0 or 1", OPT_UPLOAD(ext2_opt, c->dix.rank2 != nullptr)},
+    {"warm_dma", 1, 1ll << 30, kInRange, "warm_dma: 1 .. 2^30 bytes", warm_dma, nullptr},
+    // device workspace ~40 B per base of a pass
+    {"max_pass_bases", 1, kNoMax, kInRange, "max_pass_bases must be >= 1", OPT_VALUE(max_pass_bases)},
+    // secondary entry slots per read: get returns what 0 (auto) stands for
+    {"ent_slots", 0, 1024, kMultipleOf4, "ent_slots must be 0 (auto) or a multiple of 4 up to 1024", OPT_SET(ent_slots_opt),
+     OPT_GET(ent_slots(c))},
+    {"pool_per_read", 0, kNoMax, kInRange, "pool_per_read must be >= 0", set_pool_per_read, nullptr},
+    // the side data of FASTQ and FASTA text (ntcomp_codec.h, ntcomp_gpu.h)
+    {"qualities", 0, 2, kInRange, "qualities must be 0 (drop), 1 (keep) or 2 (bin8)", OPT_VALUE(qual.mode)},
+    {"quality_coder", 0, 1, kInRange, "quality_coder must be 0 (pack) or 1 (rans)", OPT_VALUE(qual.coder)},
+    {"names", 0, 2, kInRange, "names must be 0 (drop), 1 (keep) or 2 (id)", OPT_VALUE(names.mode)},
+    {"discard_text", 0, 1, kInRange, "discard_text must be 0 or 1", OPT_VALUE(discard_text)},
+    {"paired", 0, 2, kInRange, "paired must be 0 (off), 1 (ids) or 2 (no check)", OPT_VALUE(pair.mode)},
+    {"digests", 0, 1, kInRange, "digests must be 0 or 1", OPT_VALUE(dig.opt)},
+    {"non_acgt", 0, 2, kInRange, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)", OPT_VALUE(nx.policy)},
+    // what the last upload and the last calls left
+    {"subst_hash", 0, 0, kInRange, nullptr, nullptr, get_subst_hash},
+    {"path_hash", 0, 0, kInRange, nullptr, nullptr, get_path_hash},
+    {"workspace_bytes", 0, 0, kInRange, nullptr, nullptr, get_workspace_bytes},
+    OPT_DEV(walk), OPT_DEV(rank2), OPT_DEV(tab), OPT_DEV(tab_bits),
+    OPT_DEV(filt_bits),  // allocated also when filt_f = 0
+    OPT_DEV(pair_w), OPT_DEV(win_w),
+    OPT_READ("filter_density_ppm", c->filter_density_ppm),
+    OPT_READ("n_paths", c->n_paths),
+    OPT_READ("path_text_len", c->path_text_len),
+    OPT_READ("upload_host_us", c->upload_host_us),
+    OPT_READ("upload_total_us", c->upload_total_us),
+    OPT_READ("tab_u_fallback", c->tab_u_fallback),
+    OPT_READ("pack_us", c->last_pack_ms * 1000.0),
+    OPT_READ("spill_reruns", c->spill_reruns),
+    OPT_READ("nx_sub", c->has_index ? nx_substitute(c->dix.absent) : 0),
+    OPT_READ("nx_runs", c->nx.runs),
+    OPT_READ("nx_bases", c->nx.bases),
+    OPT_READ("unpack_rice_not_simple", c->unp_path[0]),
+    OPT_READ("unpack_rice_serial", c->unp_path[1]),
+    OPT_READ("unpack_rice_through", c->unp_path[2]),
+    OPT_READ("pool_entries", c->last4.pcap),  // last call's pools
+    OPT_READ("pool_records", c->last4.rcap),
+};
+
+const Option *find_option(const char *key) {
+    for (const Option &o : kOptions)
+        if (std::strcmp(key, o.key) == 0) return &o;
+    return nullptr;
 }
 }  // namespace
 
@@ -1745,215 +1941,18 @@ extern "C" {
 
 int ntc_ctx_set_option(ntc_ctx *ctx, const char *key, int64_t value) {
     if (!ctx || !key) return NTC_ERR_INVALID_ARG;
-    if (std::strcmp(key, "tab_u") == 0) {  // applies to the next ntc_index_upload
-        if (value < 0 || value > (int64_t)kTabMaxU)
-            return set_err(ctx, NTC_ERR_INVALID_ARG, "tab_u must be 0 (default) or 1..15");
-        ctx->tab_u_opt = (uint32_t)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "pair_bytes") == 0) {  // applies to the next ntc_index_upload
-        if (value != 0 && value != 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "pair_bytes must be 0 or 1");
-        ctx->pair_bytes_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "filter") == 0) {  // applies to the next ntc_index_upload
-        if (value < -1 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "filter must be -1 (auto), 0 or 1");
-        ctx->filter_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "joint") == 0) {  // applies to the next ntc_index_upload
-        if (value < -1 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "joint must be -1 (auto), 0 or 1");
-        ctx->joint_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "path_link") == 0) {  // applies to the next ntc_index_upload
-        if (value != 0 && value != 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "path_link must be 0 or 1");
-        ctx->path_link_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "win") == 0) {  // applies to the next ntc_index_upload
-        if (value < -1 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "win must be -1 (auto), 0 or 1");
-        ctx->win_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "subst") == 0) {  // applies to the next ntc_index_upload
-        if (value < -1 || value > 0) return set_err(ctx, NTC_ERR_INVALID_ARG, "subst must be -1 (auto) or 0");
-        ctx->subst_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "decode_only") == 0) {  // applies to the next ntc_index_upload
-        if (value != 0 && value != 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "decode_only must be 0 or 1");
-        ctx->decode_only_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "warm_dma") == 0) {  // an action: copies of `value` bytes each way, now
-        if (value < 1 || value > (1ll << 30)) return set_err(ctx, NTC_ERR_INVALID_ARG, "warm_dma: 1 .. 2^30 bytes");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        void *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, (size_t)value, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(ctx, NTC_ERR_HIP, "warm_dma: pinned allocation failed");
-        }
-        int rc = ensure(ctx, WS_STAGE_BASES, (uint64_t)value, &d);
-        if (rc == NTC_OK) {
-            if (hipMemcpyAsync(h, d, (size_t)value, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(d, h, (size_t)value, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess) {
-                (void)hipGetLastError();
-                rc = set_err(ctx, NTC_ERR_HIP, "warm_dma: copy failed");
-            }
-        }
-        (void)hipHostFree(h);
-        return rc;
-    }
-    if (std::strcmp(key, "ext2") == 0) {  // applies to the next ntc_index_upload
-        if (value != 0 && value != 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "ext2 must be 0 or 1");
-        ctx->ext2_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "max_pass_bases") == 0) {  // device workspace ~40 B per base of a pass
-        if (value < 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "max_pass_bases must be >= 1");
-        ctx->max_pass_bases = (uint64_t)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "ent_slots") == 0) {  // secondary entry slots per read (0: auto)
-        if (value < 0 || value > 1024 || (value & 3))
-            return set_err(ctx, NTC_ERR_INVALID_ARG, "ent_slots must be 0 (auto) or a multiple of 4 up to 1024");
-        ctx->ent_slots_opt = (uint32_t)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "pool_per_read") == 0) {  // test hook: overflow pools per read (entries, records)
-        if (value < 0) return set_err(ctx, NTC_ERR_INVALID_ARG, "pool_per_read must be >= 0");
-        ctx->epool_per_read = ctx->rpool_per_read = (double)value;
-        ctx->epool_per_base = ctx->rpool_per_base = 0.0;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "qualities") == 0) {  // FASTQ quality scores: 0 drop, 1 keep, 2 bin8 (ntcomp_codec.h)
-        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "qualities must be 0 (drop), 1 (keep) or 2 (bin8)");
-        ctx->q_mode = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "quality_coder") == 0) {  // the quality sections' coder: 0 pack, 1 rans (ntcomp_codec.h)
-        if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "quality_coder must be 0 (pack) or 1 (rans)");
-        ctx->q_coder = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "names") == 0) {  // FASTQ read names: 0 drop, 1 keep, 2 id (ntcomp_codec.h)
-        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "names must be 0 (drop), 1 (keep) or 2 (id)");
-        ctx->n_mode = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "discard_text") == 0) {  // ntc_decode_fasta*: no copy of the text to the host (ntcomp_codec.h)
-        if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "discard_text must be 0 or 1");
-        ctx->discard_text = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "paired") == 0) {  // paired-end reads: 0 off, 1 pairs + mate check, 2 pairs (ntcomp_codec.h)
-        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "paired must be 0 (off), 1 (ids) or 2 (no check)");
-        ctx->paired = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "digests") == 0) {  // per-block content digests: 0 off, 1 on (ntcomp_codec.h)
-        if (value < 0 || value > 1) return set_err(ctx, NTC_ERR_INVALID_ARG, "digests must be 0 or 1");
-        ctx->dg_opt = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "non_acgt") == 0) {  // N and IUPAC symbols: 0 error, 1 mask, 2 keep (ntcomp_gpu.h)
-        if (value < 0 || value > 2) return set_err(ctx, NTC_ERR_INVALID_ARG, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)");
-        ctx->nx_policy = (int)value;
-        return NTC_OK;
-    }
-    if (std::strcmp(key, "encode_variant") == 0) {
-        if (value != 1 && value != 4)
-            return set_err(ctx, NTC_ERR_INVALID_ARG, "encode_variant must be 4 (default) or 1 (A/B baseline)");
-        ctx->encode_variant = (int)value;
-        return NTC_OK;
-    }
-    return set_err(ctx, NTC_ERR_INVALID_ARG, std::string("unknown option ") + key);
+    const Option *o = find_option(key);
+    if (!o || !o->set) return set_err(ctx, NTC_ERR_INVALID_ARG, std::string("unknown option ") + key);
+    if (value < o->lo || value > o->hi || (o->rule == kEndsOnly && value != o->lo && value != o->hi) ||
+        (o->rule == kMultipleOf4 && (value & 3)))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, o->msg);
+    return o->set(ctx, value);
 }
 
 int ntc_ctx_get_option(const ntc_ctx *ctx, const char *key, int64_t *value) {
     if (!ctx || !key || !value) return NTC_ERR_INVALID_ARG;
-    if (std::strcmp(key, "encode_variant") == 0) *value = ctx->encode_variant;
-    else if (std::strcmp(key, "tab_u") == 0) *value = ctx->has_index ? ctx->dix.tab_u : ctx->tab_u_opt;
-    else if (std::strcmp(key, "pair_bytes") == 0) *value = ctx->has_index ? (ctx->dix.pair_w != nullptr) : ctx->pair_bytes_opt;
-    else if (std::strcmp(key, "ext2") == 0) *value = ctx->has_index ? (ctx->dix.rank2 != nullptr) : ctx->ext2_opt;
-    else if (std::strcmp(key, "decode_only") == 0) *value = ctx->has_index ? ctx->index_decode_only : ctx->decode_only_opt;
-    else if (std::strcmp(key, "filter") == 0) *value = ctx->has_index ? (ctx->dix.filt_f != 0) : ctx->filter_opt;
-    else if (std::strcmp(key, "joint") == 0) *value = ctx->has_index ? (int64_t)ctx->dix.joint : ctx->joint_opt;
-    else if (std::strcmp(key, "win") == 0) *value = ctx->has_index ? (ctx->dix.win_w != nullptr) : ctx->win_opt;
-    else if (std::strcmp(key, "path_link") == 0) *value = ctx->path_link_opt;
-    else if (std::strcmp(key, "subst") == 0) *value = ctx->has_index ? ctx->subst_built : ctx->subst_opt;
-    else if (std::strcmp(key, "subst_hash") == 0) {  // test hook: derived.h subst_word_hash of the device words
-        if (!ctx->has_index || !ctx->dix.has_paths) return NTC_ERR_NO_INDEX;
-        std::vector<uint4> ps(pstream_groups(ctx->path_text_len, ctx->dix.k));
-        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-            hipMemcpy(ps.data(), ctx->dix.pstream, ps.size() * 16, hipMemcpyDeviceToHost) != hipSuccess)
-            return NTC_ERR_HIP;
-        *value = (int64_t)subst_word_hash(ps.data(), ps.size());
-    }
-    else if (std::strcmp(key, "filter_density_ppm") == 0) *value = ctx->filter_density_ppm;
-    else if (std::strcmp(key, "n_paths") == 0) *value = (int64_t)ctx->n_paths;
-    else if (std::strcmp(key, "path_text_len") == 0) *value = (int64_t)ctx->path_text_len;
-    else if (std::strcmp(key, "path_hash") == 0) {  // test hook: derived.h path_cover_hash of the device cover
-        if (!ctx->has_index || !ctx->dix.has_paths) return NTC_ERR_NO_INDEX;
-        const uint64_t n = ctx->dix.n, k = ctx->dix.k, tlen = ctx->path_text_len;
-        std::vector<uint4> ps((tlen + k) / 32 + 8);
-        std::vector<uint32_t> ca(tlen + 8), pn(n);
-        std::vector<uint64_t> pu(tlen / 64 + 4);
-        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-            hipMemcpy(ps.data(), ctx->dix.pstream, ps.size() * 16, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(ca.data(), ctx->dix.colex_at, ca.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(pn.data(), ctx->dix.pos_of_node, pn.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(pu.data(), ctx->dix.puniq, pu.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return NTC_ERR_HIP;
-        *value = (int64_t)path_cover_hash(ps.data(), ca.data(), pn.data(), pu.data(), n, (uint32_t)k, tlen);
-    }
-    else if (std::strncmp(key, "dev_", 4) == 0) {  // test hooks: device address of a derived array, 0 = not built
-        const DevIndex &d = ctx->dix;
-        const void *p;
-        if (std::strcmp(key, "dev_walk") == 0) p = d.walk;
-        else if (std::strcmp(key, "dev_rank2") == 0) p = d.rank2;
-        else if (std::strcmp(key, "dev_tab") == 0) p = d.tab;
-        else if (std::strcmp(key, "dev_tab_bits") == 0) p = d.tab_bits;
-        else if (std::strcmp(key, "dev_filt_bits") == 0) p = d.filt_bits;  // allocated also when filt_f = 0
-        else if (std::strcmp(key, "dev_pair_w") == 0) p = d.pair_w;
-        else if (std::strcmp(key, "dev_win_w") == 0) p = d.win_w;
-        else return NTC_ERR_INVALID_ARG;
-        if (!ctx->has_index) return NTC_ERR_NO_INDEX;
-        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-            return NTC_ERR_HIP;
-        *value = (int64_t)(uintptr_t)p;
-    }
-    else if (std::strcmp(key, "upload_host_us") == 0) *value = ctx->upload_host_us;
-    else if (std::strcmp(key, "max_pass_bases") == 0) *value = (int64_t)ctx->max_pass_bases;
-    else if (std::strcmp(key, "upload_total_us") == 0) *value = ctx->upload_total_us;
-    else if (std::strcmp(key, "tab_u_fallback") == 0) *value = ctx->tab_u_fallback;
-    else if (std::strcmp(key, "pack_us") == 0) *value = (int64_t)(ctx->last_pack_ms * 1000.0);
-    else if (std::strcmp(key, "ent_slots") == 0) *value = ent_slots(ctx);
-    else if (std::strcmp(key, "spill_reruns") == 0) *value = (int64_t)ctx->spill_reruns;
-    else if (std::strcmp(key, "non_acgt") == 0) *value = ctx->nx_policy;
-    else if (std::strcmp(key, "qualities") == 0) *value = ctx->q_mode;
-    else if (std::strcmp(key, "quality_coder") == 0) *value = ctx->q_coder;
-    else if (std::strcmp(key, "names") == 0) *value = ctx->n_mode;
-    else if (std::strcmp(key, "digests") == 0) *value = ctx->dg_opt;
-    else if (std::strcmp(key, "discard_text") == 0) *value = ctx->discard_text;
-    else if (std::strcmp(key, "paired") == 0) *value = ctx->paired;
-    else if (std::strcmp(key, "nx_sub") == 0) *value = ctx->has_index ? (int64_t)nx_substitute(ctx->dix.absent) : 0;
-    else if (std::strcmp(key, "nx_runs") == 0) *value = (int64_t)ctx->nx_runs;
-    else if (std::strcmp(key, "nx_bases") == 0) *value = (int64_t)ctx->nx_bases;
-    else if (std::strcmp(key, "unpack_rice_not_simple") == 0) *value = (int64_t)ctx->unp_path[0];
-    else if (std::strcmp(key, "unpack_rice_serial") == 0) *value = (int64_t)ctx->unp_path[1];
-    else if (std::strcmp(key, "unpack_rice_through") == 0) *value = (int64_t)ctx->unp_path[2];
-    else if (std::strcmp(key, "pool_entries") == 0) *value = (int64_t)ctx->last4.pcap;  // last call's pools
-    else if (std::strcmp(key, "pool_records") == 0) *value = (int64_t)ctx->last4.rcap;
-    else if (std::strcmp(key, "workspace_bytes") == 0) {  // device workspace held now (all slots)
-        uint64_t t = 0;
-        for (const auto &b : ctx->ws) t += b.bytes;
-        *value = (int64_t)t;
-    }
-    else return NTC_ERR_INVALID_ARG;
-    return NTC_OK;
+    const Option *o = find_option(key);
+    return o && o->get ? o->get(ctx, value) : NTC_ERR_INVALID_ARG;
 }
 
 int ntc_index_info(const ntc_ctx *ctx, uint64_t *n_nodes, uint32_t *k, uint64_t *device_bytes) {
@@ -1971,9 +1970,9 @@ int ntc_encode_batch_device(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t
     if (!ctx || (!d_read_offsets && n_reads) || !d_rec_offsets_out)
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_batch_device");
-    if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_batch_device");
-    if (ctx->nx_policy != 0)
+    if (ctx->qual.mode != 0) return q_unsupported(ctx, "ntc_encode_batch_device");
+    if (ctx->names.mode != 0) return n_unsupported(ctx, "ntc_encode_batch_device");
+    if (ctx->nx.policy != 0)
         return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need the host-buffer encode calls "
                                                  "(the caller's device buffer is const)");
     if (ctx->encode_variant == 4) {
@@ -2023,7 +2022,7 @@ int ntc_encode_status(ntc_ctx *ctx, int64_t *bad_read, uint64_t *n_records) {
     if (rc) return rc;
     if (n_records) {
         if (ctx->last != kEncode || !ctx->last_out_offs) return set_err(ctx, NTC_ERR_INVALID_ARG, "no encode call");
-        if (ctx->box_valid) *n_records = ((volatile uint64_t *)ctx->h_box)[1];
+        if (ctx->box_valid) *n_records = box(ctx, kBoxA);
         else HIP_TRY(ctx, hipMemcpy(n_records, ctx->last_out_offs + ctx->last_n, 8, hipMemcpyDeviceToHost));
     }
     return NTC_OK;
@@ -2080,10 +2079,10 @@ int ntc_encode_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_of
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
-    if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_batch");
-    if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_batch");
-    nx_begin(ctx);
-    if (ctx->encode_variant != 4 && ctx->nx_policy != 0)
+    if (ctx->qual.mode != 0) return q_unsupported(ctx, "ntc_encode_batch");
+    if (ctx->names.mode != 0) return n_unsupported(ctx, "ntc_encode_batch");
+    ctx->nx.begin();
+    if (ctx->encode_variant != 4 && ctx->nx.policy != 0)
         return set_err(ctx, NTC_ERR_UNSUPPORTED, "non_acgt mask / keep need encode_variant 4");
     if (ctx->encode_variant != 4)
         return encode_batch_v1(ctx, bases, read_offsets, n_reads, rec_out, rec_capacity, rec_offsets_out, bad_read);
@@ -2199,8 +2198,8 @@ int ntc_decode_status(ntc_ctx *ctx, uint64_t *n_reads, uint64_t *n_bases) {
     if (ctx->last != kDecode) return set_err(ctx, NTC_ERR_INVALID_ARG, "no decode call");
     uint64_t nr = 0, nb = 0;
     if (ctx->box_valid) {
-        nr = ((volatile uint64_t *)ctx->h_box)[1];
-        nb = ((volatile uint64_t *)ctx->h_box)[2];
+        nr = box(ctx, kBoxA);
+        nb = box(ctx, kBoxB);
     } else {
         HIP_TRY(ctx, hipMemcpy(&nr, ctx->last_out_offs + ctx->last_n, 8, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(&nb, ctx->last_out_offs + (ctx->last_n + 1) + ctx->last_n, 8, hipMemcpyDeviceToHost));
@@ -2227,10 +2226,11 @@ int ntc_decode_batch(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint8_
     if (n_recs && !((recs[0] >> 56) & 1)) return set_err(ctx, NTC_ERR_FORMAT, "records do not start a read");
     if (nbases > bases_capacity || nreads + 1 > offsets_capacity || !read_offsets_out || (nbases && !bases_out))
         return set_err(ctx, NTC_ERR_CAPACITY, "decode output buffers too small");
-    std::vector<ntc_nx_run> nx;  // pending exception runs: each pass patches its own reads'
-    uint32_t nx_sub = 0;
-    if (nx_take_pending(ctx, nx, nx_sub) && nx.back().read >= nreads)
-        return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
+    Pending<ntc_nx_run> nxp;  // pending exception runs: each pass patches its own reads'
+    const bool has_nx = ctx->nx.pending.take(nxp);
+    const std::vector<ntc_nx_run> &nx = nxp.metas;
+    const uint32_t nx_sub = ctx->nx.pending_sub;
+    if (has_nx && nx.back().read >= nreads) return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
     // passes of whole reads (a pass ends before a `first` record), at most max_pass_bases
     // output bases each unless one read alone is larger
     uint64_t a0 = 0, reads_done = 0, bases_done = 0;
@@ -2327,7 +2327,7 @@ int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_o
     // malformed unary runs: size the device buffer for that and let the packer check
     const uint64_t n_blocks = (n_reads + block_reads - 1) / block_reads;
     uint64_t nrec = 0;  // the status box of the encode call holds it (k_emit4 wrote offsets from 0)
-    if (ctx->box_valid) nrec = ((volatile uint64_t *)ctx->h_box)[1];
+    if (ctx->box_valid) nrec = box(ctx, kBoxA);
     else HIP_TRY(ctx, hipMemcpy(&nrec, d_roffs + n_reads, 8, hipMemcpyDeviceToHost));
     const uint64_t ends[2] = {0, nrec};
     uint64_t cap = nrec * 10 + n_blocks * 64 + 64, used = 0;
@@ -2347,7 +2347,7 @@ int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_o
     }
     *payload = h;
     *payload_bytes = used;
-    if (dg) ctx->dg_blocks = n_blocks;
+    if (dg) ctx->dig.blocks = n_blocks;
     return NTC_OK;
 }
 }  // namespace
@@ -2365,9 +2365,9 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
-    if (ctx->q_mode != 0) return q_unsupported(ctx, "ntc_encode_pack_batch");
-    if (ctx->n_mode != 0) return n_unsupported(ctx, "ntc_encode_pack_batch");
-    dg_begin(ctx);
+    if (ctx->qual.mode != 0) return q_unsupported(ctx, "ntc_encode_pack_batch");
+    if (ctx->names.mode != 0) return n_unsupported(ctx, "ntc_encode_pack_batch");
+    ctx->dig.begin();
     for (uint64_t r = 0; r < n_reads; r++)
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
@@ -2381,7 +2381,7 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     if ((rc = ensure(ctx, WS_STAGE_OFFS, (n_reads + 1) * 8 * 2, &d_offs))) return rc;
     if (total) HIP_TRY(ctx, hipMemcpyAsync(d_bases, bases + o0, total, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_offs, offs.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    nx_begin(ctx);
+    ctx->nx.begin();
     const auto restage = [&]() -> int {
         if (total) HIP_TRY(ctx, hipMemcpyAsync(d_bases, bases + o0, total, hipMemcpyHostToDevice, ctx->stream));
         return NTC_OK;
@@ -2483,7 +2483,7 @@ int fastq_stage(ntc_ctx *ctx, const uint8_t *fastq, uint64_t bytes, uint64_t n_r
         if ((rc = ensure(ctx, WS_PAIR_ST, 64, &p))) return rc;
         pst = (unsigned long long *)p;
         HIP_TRY(ctx, hipMemsetAsync(pst, 0xFF, 16, ctx->stream));
-        ctx->h_box[10] = ctx->h_box[11] = ~0ull;  // (no kernel of an earlier call writes them: each ends synchronised)
+        ctx->h_box[kBoxWeave] = ctx->h_box[kBoxMateCheck] = ~0ull;  // (no kernel of an earlier call writes them: each ends synchronised)
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0xFF, 8, ctx->stream));
     if (pair) {
@@ -2510,30 +2510,30 @@ int fastq_stage(ntc_ctx *ctx, const uint8_t *fastq, uint64_t bytes, uint64_t n_r
     launch_status_box(ctx->d_status, a.offs + n_reads, nullptr, nullptr, ctx->h_box, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (pst && ((volatile uint64_t *)ctx->h_box)[10] != ~0ULL) {  // (the parse then saw a text nobody wrote)
-        const uint64_t w = ((volatile uint64_t *)ctx->h_box)[10];
+    if (pst && box(ctx, kBoxWeave) != ~0ULL) {  // (the parse then saw a text nobody wrote)
+        const uint64_t w = box(ctx, kBoxWeave);
         if (bad_read) *bad_read = (int64_t)(w >> 8);
         char buf[160];
         std::snprintf(buf, sizeof(buf), "mate texts hold different record counts: read %lld has no whole record",
                       (long long)(w >> 8));
         return set_err(ctx, (int)(w & 0xFF), buf);
     }
-    const uint64_t st = ((volatile uint64_t *)ctx->h_box)[0];
+    const uint64_t st = box(ctx, kBoxStatus);
     if (st != ~0ULL) {
         if (bad_read) *bad_read = (int64_t)(st >> 8);
         char buf[160];
         std::snprintf(buf, sizeof(buf), "malformed FASTQ record at index %lld", (long long)(st >> 8));
         return set_err(ctx, (int)(st & 0xFF), buf);
     }
-    if (pst && ((volatile uint64_t *)ctx->h_box)[11] != ~0ULL) {
-        const uint64_t c = ((volatile uint64_t *)ctx->h_box)[11];
+    if (pst && box(ctx, kBoxMateCheck) != ~0ULL) {
+        const uint64_t c = box(ctx, kBoxMateCheck);
         if (bad_read) *bad_read = (int64_t)(c >> 8);
         char buf[160];
         std::snprintf(buf, sizeof(buf), "the names of the mates disagree at pair %lld (reads %lld and %lld)",
                       (long long)(c >> 9), (long long)(c >> 8), (long long)(c >> 8) + 1);
         return set_err(ctx, (int)(c & 0xFF), buf);
     }
-    *total = ((volatile uint64_t *)ctx->h_box)[1];
+    *total = box(ctx, kBoxA);
     return NTC_OK;
 }
 }  // namespace
@@ -2571,24 +2571,16 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
-    if (ctx->paired && ((n_reads & 1) || (block_reads & 1)))
+    if (ctx->pair.mode && ((n_reads & 1) || (block_reads & 1)))
         return set_err(ctx, NTC_ERR_INVALID_ARG, "paired: n_reads and block_reads must be even");
     void *d_bases, *d_offs;
     uint64_t total = 0;
     int rc = fastq_stage(ctx, fastq, fastq_bytes, n_reads, &d_bases, &d_offs, &total, bad_read, pair,
-                         ctx->paired == kPairIds);
-    if (rc && ctx->paired) {  // a failed call leaves no sections
-        nx_begin(ctx);
-        q_begin(ctx);
-        n_begin(ctx);
-        dg_begin(ctx);
-    }
+                         ctx->pair.mode == kPairIds);
+    if (rc && ctx->pair.mode) side_begin(ctx);  // a failed call leaves no sections
     if (rc) return rc;
     if (n_bases) *n_bases = total;
-    nx_begin(ctx);
-    q_begin(ctx);
-    n_begin(ctx);
-    dg_begin(ctx);
+    side_begin(ctx);
     if (n_reads == 0) return NTC_OK;
     // the digest table of the call (option "digests" 0: nothing runs here or below)
     const uint32_t dg = dg_components(ctx, true);
@@ -2600,7 +2592,7 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
         return rc;
     // and the names are front-coded from it (mode 0: nothing runs)
     if ((rc = n_pack(ctx, n_reads, block_reads))) return rc;
-    if ((dg & kDgName) && (rc = dg_add(ctx, 3, ctx->fq_last.raw, ctx->fq_last.n_raw, nullptr, ctx->n_d_start, ctx->n_d_len,
+    if ((dg & kDgName) && (rc = dg_add(ctx, 3, ctx->fq_last.raw, ctx->fq_last.n_raw, nullptr, ctx->names.d_start, ctx->names.d_len,
                                       n_reads, block_reads)))
         return rc;
     const auto restage = [&]() -> int {  // the text is still in HBM: parse it again (it parsed clean once)
@@ -2612,7 +2604,7 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
     };
     rc = encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads, meta,
                             payload, payload_bytes, bad_read, restage, dg);
-    if (ctx->q_mode == 0 && ctx->n_mode == 0) return rc;
+    if (ctx->qual.mode == 0 && ctx->names.mode == 0) return rc;
     // a read the quality or the names pass refused fails the call, whatever the encode said of it
     if (rc) (void)hipStreamSynchronize(ctx->stream);  // (an encode that failed early may not have synchronised)
     int64_t q_bad = -1, n_bad = -1;
@@ -2620,9 +2612,9 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
     const int nrc = n_collect(ctx, n_reads, block_reads, &n_bad);
     const int src = qrc ? qrc : nrc;
     if (rc || src) {  // a failed call leaves no sections
-        q_begin(ctx);
-        n_begin(ctx);
-        dg_begin(ctx);
+        ctx->qual.begin();
+        ctx->names.begin();
+        ctx->dig.begin();
     }
     if (src && bad_read) *bad_read = qrc ? q_bad : n_bad;
     if (src && !rc) {
@@ -2655,11 +2647,8 @@ int ntc_encode_pack_fastq_paired(ntc_ctx *ctx, const uint8_t *fastq1, uint64_t b
     *payload = nullptr;
     *payload_bytes = 0;
     if (n_bases) *n_bases = 0;
-    if (!ctx->paired) return set_err(ctx, NTC_ERR_INVALID_ARG, "ntc_encode_pack_fastq_paired needs the option paired 1 or 2");
-    nx_begin(ctx);  // a failed call leaves no sections
-    q_begin(ctx);
-    n_begin(ctx);
-    dg_begin(ctx);
+    if (!ctx->pair.mode) return set_err(ctx, NTC_ERR_INVALID_ARG, "ntc_encode_pack_fastq_paired needs the option paired 1 or 2");
+    side_begin(ctx);  // a failed call leaves no sections
     // (the weave may add a newline to each text)
     if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32) || bytes1 + bytes2 + 2 >= (1ull << 32))
         return set_err(ctx, NTC_ERR_CAPACITY, "mate texts of 4 GiB or more together: split the batch");
@@ -2690,10 +2679,12 @@ uint64_t fasta_bytes(uint64_t n_reads, uint64_t n_bases, uint64_t first_id) {
 // the text a decode call writes: FASTQ when quality sections are pending ("\n+\n" and the
 // qualities more per read)
 uint64_t text_bytes(const ntc_ctx *ctx, uint64_t n_reads, uint64_t n_bases, uint64_t first_id) {
-    const uint64_t q = ctx->qd_has_pending ? n_bases + 3 * n_reads : 0;
+    const uint64_t q = ctx->qual.pending.has ? n_bases + 3 * n_reads : 0;
     // with names pending: ">" or "@", the name, '\n', the read, '\n' (and no seq.N)
-    if (ctx->nd_has_pending) return ctx->nd_name_bytes + n_bases + 3 * n_reads + q;
-    return fasta_bytes(n_reads, n_bases, first_id) + q;
+    if (!ctx->names.pending.has) return fasta_bytes(n_reads, n_bases, first_id) + q;
+    uint64_t name_bytes = 0;
+    for (const ntc_name_meta &m : ctx->names.pending.metas) name_bytes += m.name_bytes;
+    return name_bytes + n_bases + 3 * n_reads + q;
 }
 
 // The pending text window leaves the context with the call that takes it: a size query (keep)
@@ -2703,20 +2694,33 @@ struct TextWindow {
     uint64_t first = 0, count = 0;  // count 0: no window
     bool kept = false;
     explicit TextWindow(ntc_ctx *c) : ctx(c) {
-        if (c->tw_has_pending) first = c->tw_first, count = c->tw_count;
+        if (c->win.has_pending) first = c->win.first, count = c->win.count;
     }
     ~TextWindow() {
-        if (!kept) ctx->tw_has_pending = false;
+        if (!kept) ctx->win.has_pending = false;
     }
     void keep() { kept = true; }
     // the request against the batch it met
     int check(uint64_t n_reads) const {
-        if (!count || w_valid(first, count, n_reads, ctx->paired != 0)) return NTC_OK;
+        if (!count || w_valid(first, count, n_reads, ctx->pair.mode != 0)) return NTC_OK;
         const bool inside = first < n_reads && count <= n_reads - first;  // (then it cuts a pair)
         return set_err(ctx, NTC_ERR_INVALID_ARG, inside ? "paired: a window's first read and count must be even (whole pairs)"
                                                         : "the window reaches past the batch's reads");
     }
 };
+
+// the sections of a side stream taken for this call cover exactly the reads it decodes
+template <class Meta>
+int sections_cover(ntc_ctx *ctx, const std::vector<Meta> &metas, uint64_t n_reads, const char *noun) {
+    uint64_t r = 0;
+    for (const Meta &m : metas) {
+        if (m.n_reads > n_reads - r)
+            return set_err(ctx, NTC_ERR_FORMAT, std::string(noun) + " sections for more reads than decoded");
+        r += m.n_reads;
+    }
+    if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, std::string(noun) + " sections for fewer reads than decoded");
+    return NTC_OK;
+}
 
 // walk + FASTA text of records already in HBM (d_recs), text D2H into out (need bytes; with a
 // window w only the window's bytes, which *out_len then reports)
@@ -2729,52 +2733,30 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if ((rc = ensure(ctx, WS_FA_SCAN, (2 * (n_reads + 1) + scan_tmp_words(n_reads + 1)) * 8, &d_scan))) return rc;
     if ((rc = ensure(ctx, WS_STAGE_BASES, need + 64, &d_out))) return rc;
     // pairs: the formatted text is split into its two parts on the device before the copy
-    const bool split = ctx->paired && !ctx->discard_text && n_reads;
+    const bool split = ctx->pair.mode && !ctx->discard_text && n_reads;
     void *d_pscan = nullptr, *d_split = nullptr;
     if (split) {
         if ((rc = ensure(ctx, WS_PAIR_SCAN, 4 * (n_reads / 2 + 1) * 8, &d_pscan))) return rc;
         if ((rc = ensure(ctx, WS_PAIR_OUT, need + 64, &d_split))) return rc;
     }
-    std::vector<ntc_nx_run> nx;
-    uint32_t nx_sub = 0;
-    std::vector<ntc_qual_meta> qm;
-    std::vector<uint64_t> qp;
-    std::vector<ntc_name_meta> nm;
-    std::vector<uint64_t> np;
-    std::vector<ntc_digest_meta> dm;
-    const bool fastq = q_take_pending(ctx, qm, qp);  // (all pending lists leave the context here)
-    const bool named = n_take_pending(ctx, nm, np);
-    const bool digests = dg_take_pending(ctx, dm);
-    const bool has_nx = nx_take_pending(ctx, nx, nx_sub);
+    Pending<ntc_nx_run> nxp;
+    Pending<ntc_qual_meta> qs;
+    Pending<ntc_name_meta> ns;
+    Pending<ntc_digest_meta> ds;
+    const bool fastq = ctx->qual.pending.take(qs);  // (all pending lists leave the context here)
+    const bool named = ctx->names.pending.take(ns);
+    const bool digests = ctx->dig.pending.take(ds);
+    const bool has_nx = ctx->nx.pending.take(nxp);
+    const std::vector<ntc_nx_run> &nx = nxp.metas;
+    const uint32_t nx_sub = ctx->nx.pending_sub;
     if ((rc = w.check(n_reads))) return rc;  // (after the lists: a refused window leaves nothing pending either)
     if (has_nx && nx.back().read >= n_reads)
         return set_err(ctx, NTC_ERR_FORMAT, "exception run past the last read");
-    if (fastq) {
-        uint64_t r = 0;
-        for (const ntc_qual_meta &m : qm) {
-            if (m.n_reads > n_reads - r) return set_err(ctx, NTC_ERR_FORMAT, "quality sections for more reads than decoded");
-            r += m.n_reads;
-        }
-        if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "quality sections for fewer reads than decoded");
-    }
-    if (named) {
-        uint64_t r = 0;
-        for (const ntc_name_meta &m : nm) {
-            if (m.n_reads > n_reads - r) return set_err(ctx, NTC_ERR_FORMAT, "name sections for more reads than decoded");
-            r += m.n_reads;
-        }
-        if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "name sections for fewer reads than decoded");
-    }
+    if (fastq && (rc = sections_cover(ctx, qs.metas, n_reads, "quality"))) return rc;
+    if (named && (rc = sections_cover(ctx, ns.metas, n_reads, "name"))) return rc;
     DgDecode dg;
-    if (digests) {
-        uint64_t r = 0;
-        for (const ntc_digest_meta &m : dm) {
-            if (m.n_reads > n_reads - r) return set_err(ctx, NTC_ERR_FORMAT, "digest sections for more reads than decoded");
-            r += m.n_reads;
-        }
-        if (r != n_reads) return set_err(ctx, NTC_ERR_FORMAT, "digest sections for fewer reads than decoded");
-        if ((rc = dgd_begin(ctx, dm, dg))) return rc;
-    }
+    if (digests && (rc = sections_cover(ctx, ds.metas, n_reads, "digest"))) return rc;
+    if (digests && (rc = dgd_begin(ctx, ds.metas, dg))) return rc;
     if ((rc = ntc_decode_batch_device(ctx, d_recs, n_recs, (uint8_t *)d_bases, n_bases + 64, (uint64_t *)d_offs,
                                       n_reads + 2)))
         return rc;
@@ -2787,16 +2769,16 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if (digests && !nx.empty() && (rc = dgd_add(ctx, dg, 1, d_bases, n_bases, (const uint64_t *)d_offs))) return rc;
     // and the qualities are unpacked by the decoded reads' offsets, after the patch
     uint8_t *d_quals = nullptr;
-    if (fastq && (rc = q_unpack(ctx, qm, qp, n_reads, n_bases, (const uint64_t *)d_offs, &d_quals))) return rc;
+    if (fastq && (rc = q_unpack(ctx, qs.metas, qs.payload, n_reads, n_bases, (const uint64_t *)d_offs, &d_quals))) return rc;
     // and the names are expanded, each section on its own
     uint8_t *d_names = nullptr;
     uint64_t *d_name_off = nullptr;
-    if (named && (rc = n_expand(ctx, nm, np, n_reads, &d_names, &d_name_off))) return rc;
+    if (named && (rc = n_expand(ctx, ns.metas, ns.payload, n_reads, &d_names, &d_name_off))) return rc;
     // the other two components over what was just expanded, then the verdict on the device:
     // a block that differs sets the status, and the formatters below write nothing
     if (digests) {
         uint64_t name_bytes = 0;
-        for (const ntc_name_meta &m : nm) name_bytes += m.name_bytes;
+        for (const ntc_name_meta &m : ns.metas) name_bytes += m.name_bytes;
         if (fastq && (rc = dgd_add(ctx, dg, 2, d_quals, n_bases, (const uint64_t *)d_offs))) return rc;
         if (named && (rc = dgd_add(ctx, dg, 3, d_names, name_bytes, d_name_off))) return rc;
         if ((rc = dgd_compare(ctx, dg, n_reads, (const uint64_t *)d_offs))) return rc;
@@ -2813,7 +2795,7 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
                      out_offs, tmp, (uint8_t *)d_out, need, ctx->stream, w.first, w.count);
     HIP_TRY(ctx, hipGetLastError());
     if (w.count) {  // the window's bytes: the scan's total, 0 when the call failed on the device
-        ctx->h_box[13] = 0;  // (no kernel of an earlier call writes it: each ends synchronised)
+        ctx->h_box[kBoxWindow] = 0;  // (no kernel of an earlier call writes it: each ends synchronised)
         launch_window_box(out_offs + n_reads, ctx->h_box, ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -2837,7 +2819,7 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     uint64_t copy = need;
     if (w.count) {  // the device knows the window's bytes: wait for them, copy only them
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const uint64_t got = ((volatile uint64_t *)ctx->h_box)[13];
+        const uint64_t got = box(ctx, kBoxWindow);
         *out_len = copy = std::min(need, got);
     }
     if (!ctx->discard_text && copy) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, copy, hipMemcpyDeviceToHost, ctx->stream));
@@ -2847,7 +2829,7 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if (rc) return rc;
     if (nr != n_reads || nb != n_bases)
         return set_err(ctx, NTC_ERR_FORMAT, "records hold other read / base counts than given");
-    if (split) ctx->pair_first = ((volatile uint64_t *)ctx->h_box)[12];
+    if (split) ctx->pair.first = box(ctx, kBoxPairFirst);
     return NTC_OK;
 }
 }  // namespace
@@ -2885,18 +2867,18 @@ int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
-    ctx->pair_valid = false;
+    ctx->pair.valid = false;
     TextWindow w(ctx);
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
-    if (ctx->paired && (n_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
+    if (ctx->pair.mode && (n_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, n_reads, n_bases, first_id);
     *out_len = need;
     if (need > out_capacity && !ctx->discard_text) {
         w.keep();  // (a size query: the window waits for the call it sizes)
         return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
     }
-    ctx->pair_valid = ctx->paired && !ctx->discard_text;  // (the parts stay empty unless the call succeeds)
-    ctx->pair_first = 0;
+    ctx->pair.valid = ctx->pair.mode && !ctx->discard_text;  // (the parts stay empty unless the call succeeds)
+    ctx->pair.first = 0;
     if (n_recs == 0) {
         if (const int wrc = w.check(n_reads)) return wrc;
         return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
@@ -3034,10 +3016,10 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     if (!ctx || !out_len) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
-    ctx->pair_valid = false;
+    ctx->pair.valid = false;
     TextWindow w(ctx);
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
-    if (ctx->paired && (ctx->unp_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
+    if (ctx->pair.mode && (ctx->unp_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, ctx->unp_reads, ctx->unp_bases, first_id);
     *out_len = need;  // (a size query: out_capacity 0)
     if (!ctx->discard_text) {
@@ -3047,8 +3029,8 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
         }
         if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     }
-    ctx->pair_valid = ctx->paired && !ctx->discard_text;
-    ctx->pair_first = 0;
+    ctx->pair.valid = ctx->pair.mode && !ctx->discard_text;
+    ctx->pair.first = 0;
     if (ctx->unp_recs == 0) {
         if (const int wrc = w.check(ctx->unp_reads)) return wrc;
         return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
@@ -3059,41 +3041,41 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
 
 int ntc_decode_set_window(ntc_ctx *ctx, uint64_t first, uint64_t count) {
     if (!ctx) return NTC_ERR_INVALID_ARG;
-    ctx->tw_has_pending = false;
+    ctx->win.has_pending = false;
     // (the batch's reads are only known to the call that takes it: TextWindow::check)
     if (count == 0 || first + count < first) return set_err(ctx, NTC_ERR_INVALID_ARG, "an empty window");
-    ctx->tw_first = first;
-    ctx->tw_count = count;
-    ctx->tw_has_pending = true;
+    ctx->win.first = first;
+    ctx->win.count = count;
+    ctx->win.has_pending = true;
     return NTC_OK;
 }
 
 int ntc_decode_pair_split(ntc_ctx *ctx, uint64_t *first_bytes) {
     if (!ctx || !first_bytes) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     *first_bytes = 0;
-    if (!ctx->pair_valid) return set_err(ctx, NTC_ERR_INVALID_ARG, "the last text decode of this context was not a paired one");
-    *first_bytes = ctx->pair_first;
+    if (!ctx->pair.valid) return set_err(ctx, NTC_ERR_INVALID_ARG, "the last text decode of this context was not a paired one");
+    *first_bytes = ctx->pair.first;
     return NTC_OK;
 }
 
 int ntc_encode_exceptions(ntc_ctx *ctx, ntc_nx_run *out, uint64_t capacity, uint64_t *n_runs) {
     if (!ctx || !n_runs || (capacity && !out)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    *n_runs = ctx->nx_list.size();
-    if (ctx->nx_list.size() > capacity) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the exception runs");
-    if (!ctx->nx_list.empty()) std::memcpy(out, ctx->nx_list.data(), ctx->nx_list.size() * sizeof(ntc_nx_run));
+    *n_runs = ctx->nx.list.size();
+    if (ctx->nx.list.size() > capacity) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the exception runs");
+    if (!ctx->nx.list.empty()) std::memcpy(out, ctx->nx.list.data(), ctx->nx.list.size() * sizeof(ntc_nx_run));
     return NTC_OK;
 }
 
 int ntc_decode_set_exceptions(ntc_ctx *ctx, const ntc_nx_run *runs, uint64_t n_runs, uint32_t sub) {
     if (!ctx || (n_runs && !runs)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    ctx->nx_pending.assign(runs, runs + n_runs);
+    std::vector<ntc_nx_run> &p = ctx->nx.pending.metas;
+    p.assign(runs, runs + n_runs);
     // each decode pass finds its runs by read: keep them in (read, pos) order (the canonical
     // lists already are)
     const auto less = [](const ntc_nx_run &a, const ntc_nx_run &b) { return a.read != b.read ? a.read < b.read : a.pos < b.pos; };
-    if (!std::is_sorted(ctx->nx_pending.begin(), ctx->nx_pending.end(), less))
-        std::stable_sort(ctx->nx_pending.begin(), ctx->nx_pending.end(), less);
-    ctx->nx_pending_sub = sub;
-    ctx->nx_has_pending = n_runs != 0;
+    if (!std::is_sorted(p.begin(), p.end(), less)) std::stable_sort(p.begin(), p.end(), less);
+    ctx->nx.pending_sub = sub;
+    ctx->nx.pending.has = n_runs != 0;
     return NTC_OK;
 }
 
@@ -3101,26 +3083,26 @@ int ntc_encode_qualities(ntc_ctx *ctx, ntc_qual_meta *metas, uint64_t meta_cap, 
                          uint64_t *n_blocks, uint64_t *payload_bytes) {
     if (!ctx || !n_blocks || !payload_bytes || (meta_cap && !metas) || (payload_cap && !payload))
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    *n_blocks = ctx->q_blocks;
-    *payload_bytes = ctx->q_words * 8;
-    if (ctx->q_blocks > meta_cap || ctx->q_words * 8 > payload_cap)
+    *n_blocks = ctx->qual.blocks;
+    *payload_bytes = ctx->qual.words * 8;
+    if (ctx->qual.blocks > meta_cap || ctx->qual.words * 8 > payload_cap)
         return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the quality sections");
-    if (ctx->q_blocks == 0) return NTC_OK;
+    if (ctx->qual.blocks == 0) return NTC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t nb = ctx->q_blocks;
+    const uint64_t nb = ctx->qual.blocks;
     std::vector<QBlock> blk(nb);
     HIP_TRY(ctx, hipMemcpy(blk.data(), (const uint8_t *)ctx->ws[WS_Q_BLOCKS].p + 64 + nb * 16, nb * sizeof(QBlock),
                            hipMemcpyDeviceToHost));
-    if (ctx->q_words)
-        HIP_TRY(ctx, hipMemcpy(payload, ctx->ws[WS_Q_PAYLOAD].p, ctx->q_words * 8, hipMemcpyDeviceToHost));
+    if (ctx->qual.words)
+        HIP_TRY(ctx, hipMemcpy(payload, ctx->ws[WS_Q_PAYLOAD].p, ctx->qual.words * 8, hipMemcpyDeviceToHost));
     for (uint64_t b = 0; b < nb; b++) {
         ntc_qual_meta &m = metas[b];
         std::memset(&m, 0, sizeof(m));
-        m.n_reads = std::min<uint64_t>(ctx->q_block_reads, ctx->q_reads - b * ctx->q_block_reads);
+        m.n_reads = std::min<uint64_t>(ctx->qual.block_reads, ctx->qual.reads - b * ctx->qual.block_reads);
         m.n_quals = blk[b].n_quals;
         m.payload_off = blk[b].word_off * 8;
-        m.payload_bytes = ctx->q_coder_last == 1 ? blk[b].body_bytes : blk[b].n_words * 8;
-        m.reserved[0] = (uint8_t)ctx->q_coder_last;
+        m.payload_bytes = ctx->qual.coder_last == 1 ? blk[b].body_bytes : blk[b].n_words * 8;
+        m.reserved[0] = (uint8_t)ctx->qual.coder_last;
         m.width = (uint8_t)blk[b].w;
         m.n_syms = (uint8_t)blk[b].n_syms;
         std::memcpy(m.alphabet, blk[b].alphabet, blk[b].n_syms);
@@ -3131,9 +3113,7 @@ int ntc_encode_qualities(ntc_ctx *ctx, ntc_qual_meta *metas, uint64_t meta_cap, 
 int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t n_blocks, const uint8_t *payload,
                              uint64_t payload_bytes) {
     if (!ctx || (n_blocks && !metas) || (payload_bytes && !payload)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    ctx->qd_metas.clear();
-    ctx->qd_payload.clear();
-    ctx->qd_has_pending = false;
+    ctx->qual.pending.clear();
     if (n_blocks == 0) return NTC_OK;
     const uint32_t coder = metas[0].reserved[0];  // 0 pack, 1 rans: one coder for all sections
     if (coder > 1) return set_err(ctx, NTC_ERR_FORMAT, "quality sections of an unknown coder");
@@ -3154,10 +3134,10 @@ int ntc_decode_set_qualities(ntc_ctx *ctx, const ntc_qual_meta *metas, uint64_t 
             m.payload_off > payload_bytes || m.payload_bytes > payload_bytes - m.payload_off)
             return set_err(ctx, NTC_ERR_FORMAT, "quality section " + std::to_string(b) + ": payload size or place");
     }
-    ctx->qd_metas.assign(metas, metas + n_blocks);
-    ctx->qd_payload.assign((payload_bytes + 7) / 8, 0);
-    if (payload_bytes) std::memcpy(ctx->qd_payload.data(), payload, payload_bytes);
-    ctx->qd_has_pending = true;
+    ctx->qual.pending.metas.assign(metas, metas + n_blocks);
+    ctx->qual.pending.payload.assign((payload_bytes + 7) / 8, 0);
+    if (payload_bytes) std::memcpy(ctx->qual.pending.payload.data(), payload, payload_bytes);
+    ctx->qual.pending.has = true;
     return NTC_OK;
 }
 
@@ -3165,80 +3145,70 @@ int ntc_encode_names(ntc_ctx *ctx, ntc_name_meta *metas, uint64_t meta_cap, uint
                      uint64_t *n_blocks, uint64_t *payload_bytes) {
     if (!ctx || !n_blocks || !payload_bytes || (meta_cap && !metas) || (payload_cap && !payload))
         return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    *n_blocks = ctx->n_blocks;
-    *payload_bytes = ctx->n_bytes;
-    if (ctx->n_blocks > meta_cap || ctx->n_bytes > payload_cap)
+    *n_blocks = ctx->names.blocks;
+    *payload_bytes = ctx->names.bytes;
+    if (ctx->names.blocks > meta_cap || ctx->names.bytes > payload_cap)
         return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the name sections");
-    if (ctx->n_blocks == 0) return NTC_OK;
+    if (ctx->names.blocks == 0) return NTC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     static_assert(sizeof(NBlock) == sizeof(ntc_name_meta), "the device table is the public meta");
-    HIP_TRY(ctx, hipMemcpy(metas, (const uint8_t *)ctx->ws[WS_N_BLOCKS].p + 64, ctx->n_blocks * sizeof(NBlock),
+    HIP_TRY(ctx, hipMemcpy(metas, (const uint8_t *)ctx->ws[WS_N_BLOCKS].p + 64, ctx->names.blocks * sizeof(NBlock),
                            hipMemcpyDeviceToHost));
-    if (ctx->n_bytes) HIP_TRY(ctx, hipMemcpy(payload, ctx->ws[WS_N_PAYLOAD].p, ctx->n_bytes, hipMemcpyDeviceToHost));
+    if (ctx->names.bytes) HIP_TRY(ctx, hipMemcpy(payload, ctx->ws[WS_N_PAYLOAD].p, ctx->names.bytes, hipMemcpyDeviceToHost));
     return NTC_OK;
 }
 
 int ntc_decode_set_names(ntc_ctx *ctx, const ntc_name_meta *metas, uint64_t n_blocks, const uint8_t *payload,
                          uint64_t payload_bytes) {
     if (!ctx || (n_blocks && !metas) || (payload_bytes && !payload)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    ctx->nd_metas.clear();
-    ctx->nd_payload.clear();
-    ctx->nd_has_pending = false;
-    ctx->nd_name_bytes = 0;
+    ctx->names.pending.clear();
     if (n_blocks == 0) return NTC_OK;
     if (payload_bytes & 7) return set_err(ctx, NTC_ERR_FORMAT, "name payload is not a multiple of 8 bytes");
-    uint64_t name_bytes = 0;
     for (uint64_t b = 0; b < n_blocks; b++) {
         const ntc_name_meta &m = metas[b];
-        if (m.n_reads >> 40 || m.mid_bytes >> 48 || m.mid_bytes > m.name_bytes || m.name_bytes > m.n_reads * kNMax ||
-            m.payload_bytes != n_payload_bytes(m.n_reads, m.mid_bytes))
+        if (m.mid_bytes >> 48 || !n_meta_ok(m.n_reads, m.name_bytes, m.mid_bytes, m.payload_bytes))
             return set_err(ctx, NTC_ERR_FORMAT, "name section " + std::to_string(b) + ": counts or payload size");
         if ((m.payload_off & 7) || m.payload_off > payload_bytes || m.payload_bytes > payload_bytes - m.payload_off)
             return set_err(ctx, NTC_ERR_FORMAT, "name section " + std::to_string(b) + ": payload place");
-        name_bytes += m.name_bytes;
     }
-    ctx->nd_metas.assign(metas, metas + n_blocks);
-    ctx->nd_payload.resize(payload_bytes / 8);
-    if (payload_bytes) std::memcpy(ctx->nd_payload.data(), payload, payload_bytes);
-    ctx->nd_name_bytes = name_bytes;
-    ctx->nd_has_pending = true;
+    ctx->names.pending.metas.assign(metas, metas + n_blocks);
+    ctx->names.pending.payload.resize(payload_bytes / 8);
+    if (payload_bytes) std::memcpy(ctx->names.pending.payload.data(), payload, payload_bytes);
+    ctx->names.pending.has = true;
     return NTC_OK;
 }
 
 int ntc_encode_digests(ntc_ctx *ctx, ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks) {
     if (!ctx || !n_blocks || (cap && !metas)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    *n_blocks = ctx->dg_blocks;
-    if (ctx->dg_blocks > cap) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the digest table");
-    if (ctx->dg_blocks == 0) return NTC_OK;
+    *n_blocks = ctx->dig.blocks;
+    if (ctx->dig.blocks > cap) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the digest table");
+    if (ctx->dig.blocks == 0) return NTC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpy(metas, ctx->ws[WS_DG_TABLE].p, ctx->dg_blocks * sizeof(ntc_digest_meta), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(metas, ctx->ws[WS_DG_TABLE].p, ctx->dig.blocks * sizeof(ntc_digest_meta), hipMemcpyDeviceToHost));
     return NTC_OK;
 }
 
 int ntc_decode_set_digests(ntc_ctx *ctx, const ntc_digest_meta *metas, uint64_t n_blocks) {
     if (!ctx || (n_blocks && !metas)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    ctx->dd_metas.clear();
-    ctx->dd_has_pending = false;
+    ctx->dig.pending.clear();
     for (uint64_t b = 0; b < n_blocks; b++) {
         const ntc_digest_meta &m = metas[b];
         const uint64_t d[4] = {m.d_seq, m.d_sym, m.d_qual, m.d_name};
-        bool ok = !(m.components & ~kDgAll) && (m.components & kDgSeq) && !m.reserved && m.n_reads && !(m.n_reads >> 32);
-        for (uint32_t c = 0; c < 4; c++) ok = ok && ((m.components >> c & 1) || !d[c]);
-        if (!ok)
+        if (!dg_meta_ok(m.components, m.reserved, d) || !m.n_reads || m.n_reads >> 32)
             return set_err(ctx, NTC_ERR_INVALID_ARG, "digest section " + std::to_string(b) + ": components, reads or a digest "
                                                      "of an absent component");
     }
-    ctx->dd_metas.assign(metas, metas + n_blocks);
-    ctx->dd_has_pending = n_blocks != 0;
+    ctx->dig.pending.metas.assign(metas, metas + n_blocks);
+    ctx->dig.pending.has = n_blocks != 0;
     return NTC_OK;
 }
 
 int ntc_decode_digests(ntc_ctx *ctx, ntc_digest_meta *metas, uint64_t cap, uint64_t *n_blocks) {
     if (!ctx || !n_blocks || (cap && !metas)) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
-    *n_blocks = ctx->dd_computed.size();
-    if (ctx->dd_computed.size() > cap) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the digest table");
-    if (!ctx->dd_computed.empty())
-        std::memcpy(metas, ctx->dd_computed.data(), ctx->dd_computed.size() * sizeof(ntc_digest_meta));
+    *n_blocks = ctx->dig.computed.size();
+    if (ctx->dig.computed.size() > cap) return set_err(ctx, NTC_ERR_CAPACITY, "capacity smaller than the digest table");
+    if (!ctx->dig.computed.empty())
+        std::memcpy(metas, ctx->dig.computed.data(), ctx->dig.computed.size() * sizeof(ntc_digest_meta));
     return NTC_OK;
 }
 
@@ -3497,8 +3467,8 @@ struct NxHookFill {
         ntc::g_nx_hooks.last_counts = [](ntc_ctx *ctx, uint32_t *sub, uint64_t *runs, uint64_t *bases) {
             if (!ctx) return (int)NTC_ERR_INVALID_ARG;
             if (sub) *sub = ctx->has_index ? nx_substitute(ctx->dix.absent) : 0;
-            if (runs) *runs = ctx->nx_runs;
-            if (bases) *bases = ctx->nx_bases;
+            if (runs) *runs = ctx->nx.runs;
+            if (bases) *bases = ctx->nx.bases;
             return (int)NTC_OK;
         };
         ntc::g_nx_hooks.encode_exceptions = ntc_encode_exceptions;

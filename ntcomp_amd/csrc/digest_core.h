@@ -27,6 +27,15 @@ constexpr uint64_t kDgK0 = 0xD6E8FEB86659FD93ull, kDgK1 = 0x9E3779B97F4A7C15ull;
 constexpr uint32_t kDgSeq = 1, kDgSym = 2, kDgQual = 4, kDgName = 8, kDgAll = 15;
 constexpr int kErrDigest = 12;  // NTC_ERR_DIGEST, a decode status code beside encode_core.h's
 
+// a section's meta on its own (ntc_digest_meta: components, reserved, d = d_seq .. d_name):
+// known bits, seq among them, nothing set for an absent component
+DG_HD bool dg_meta_ok(uint32_t components, uint32_t reserved, const uint64_t d[4]) {
+    if ((components & ~kDgAll) || !(components & kDgSeq) || reserved) return false;
+    for (uint32_t c = 0; c < 4; c++)
+        if (!(components >> c & 1) && d[c]) return false;
+    return true;
+}
+
 DG_HD uint64_t dg_mix(uint64_t x) {
     x ^= x >> 30;
     x *= 0xBF58476D1CE4E5B9ull;

@@ -538,6 +538,21 @@ void launch_dec_tiles(const uint64_t *recs, uint64_t n, uint64_t *pf, uint64_t *
                       uint64_t *tmp, hipStream_t s);
 void launch_dec_walk(const DecWalkArgs &a, hipStream_t s);
 void launch_rank2(const DevIndex &ix, Rank2Chunk *out, hipStream_t s);
+// The words of a context's status mailbox (16 words of pinned host memory, written by the last
+// kernels of a call and read after the call's own stream sync).  k_status_box fills the first
+// four: the call's status, then up to three counts whose meaning is the call's (encode:
+// records, entries and records reserved in the overflow pools; decode: reads, bases; FASTQ
+// parse: bases kept).  Each side pass owns the words after them.
+enum BoxWord {
+    kBoxStatus = 0, kBoxA = 1, kBoxB = 2, kBoxC = 3,
+    kBoxNxRuns = 4, kBoxNxBases = 5,         // nonacgt.hip k_nx_total: runs found, symbols masked
+    kBoxQualStatus = 6, kBoxQualWords = 7,   // quality.hip / qrans.hip: the pass's status, payload words
+    kBoxNameStatus = 8, kBoxNameBytes = 9,   // names.hip: the pass's status, payload bytes
+    kBoxWeave = 10, kBoxMateCheck = 11,      // pairs.hip k_pair_box: the weave's status, the mate check's
+    kBoxPairFirst = 12,                      // pairs.hip k_pair_split: bytes of the first part
+    kBoxWindow = 13,                         // window.hip: bytes of the text window
+    kBoxWords = 16
+};
 void launch_status_box(const unsigned long long *status, const uint64_t *a, const uint64_t *b, const uint64_t *c,
                        uint64_t *box, hipStream_t s);
 void launch_walk_build(const uint32_t *pred, const uint8_t *code, uint64_t n, WalkStep *a, WalkStep *b,

@@ -120,8 +120,8 @@ __global__ __launch_bounds__(256) void k_n_blocks(NEncArgs a) {
         bytes += a.blocks[b].payload_bytes;
     }
     a.blocks[a.n_blocks].payload_off = bytes;
-    a.box[8] = *a.status;
-    a.box[9] = bytes;
+    a.box[kBoxNameStatus] = *a.status;
+    a.box[kBoxNameBytes] = bytes;
 }
 
 __global__ __launch_bounds__(256) void k_n_emit(NEncArgs a) {

@@ -73,4 +73,10 @@ N_HD uint8_t n_byte(const uint8_t *p, uint32_t plen, const uint8_t *mid, uint32_
 // bytes of a section's payload: the three columns (4 n), the mids, zeros to a multiple of 8
 N_HD uint64_t n_payload_bytes(uint64_t n_reads, uint64_t mid_bytes) { return (4 * n_reads + mid_bytes + 7) / 8 * 8; }
 
+// the counts of a section's meta (ntc_name_meta) agree with one another (payload_off is the caller's)
+N_HD bool n_meta_ok(uint64_t n_reads, uint64_t name_bytes, uint64_t mid_bytes, uint64_t payload_bytes) {
+    return !(n_reads >> 40) && mid_bytes <= name_bytes && name_bytes <= n_reads * kNMax &&
+           payload_bytes == n_payload_bytes(n_reads, mid_bytes);
+}
+
 }  // namespace ntc

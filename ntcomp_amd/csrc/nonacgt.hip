@@ -84,7 +84,7 @@ __global__ __launch_bounds__(64) void k_nx_total(NxArgs a) {
     const uint64_t ns = a.n_words ? a.soff[a.n_words] : 0, ne = a.n_words ? a.eoff[a.n_words] : 0;
     const uint64_t v = t == 0 ? ns : a.counts[1];
     if (t == 0) a.counts[0] = ns;
-    a.box[4 + t] = v;
+    a.box[kBoxNxRuns + t] = v;  // then kBoxNxBases
     if (t == 0 && ns != ne) atomicMin(a.status, (unsigned long long)kErrFormat);
 }
 

@@ -126,8 +126,8 @@ __global__ __launch_bounds__(256) void k_pm_check(PairCheckArgs a) {
 }
 
 __global__ void k_pair_box(const unsigned long long *weave, const unsigned long long *check, uint64_t *box) {
-    box[10] = *weave;
-    box[11] = *check;
+    box[kBoxWeave] = *weave;
+    box[kBoxMateCheck] = *check;
 }
 
 // ---- decode -----------------------------------------------------------------------------------
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void k_ps_sizes(const uint64_t *out_offs, uint
 
 __global__ __launch_bounds__(256) void k_ps_copy(PairSplitArgs a) {
     const uint64_t n = 2 * a.n_pairs;
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.box[12] = a.o1[a.n_pairs];
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.box[kBoxPairFirst] = a.o1[a.n_pairs];
     if (a.out_offs[n] == 0 || a.out_offs[n] > a.cap) return;  // a failed call (sizes 0) or a short buffer
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t waves = (uint64_t)gridDim.x * 4;

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void k_qr_layout(QREncArgs a) {
         at += (blocks[b].body_bytes + 7) & ~7ull;
     }
     blocks[nb].word_off = at / 8;
-    a.q.box[7] = at / 8;
+    a.q.box[kBoxQualWords] = at / 8;
 }
 
 __global__ __launch_bounds__(256) void k_qr_place(QREncArgs a) {

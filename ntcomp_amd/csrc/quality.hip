@@ -97,8 +97,8 @@ __global__ __launch_bounds__(256) void k_q_alpha(QEncArgs a) {
     }
     a.blocks[a.n_blocks].word_off = words;
     a.blocks[a.n_blocks].span_off = spans;
-    a.box[6] = *a.status;
-    a.box[7] = words;
+    a.box[kBoxQualStatus] = *a.status;
+    a.box[kBoxQualWords] = words;
 }
 
 // 8 bytes from any address: two aligned loads (the arrays end in 64 bytes of slack)

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void k_window_sizes(uint64_t *sizes, uint64_t 
     if (!w_keeps(r, first, count)) sizes[r] = 0;  // (always: r is outside by construction; the rule stays in one place)
 }
 
-__global__ void k_window_box(const uint64_t *total, uint64_t *box) { box[13] = *total; }
+__global__ void k_window_box(const uint64_t *total, uint64_t *box) { box[kBoxWindow] = *total; }
 
 }  // namespace
 

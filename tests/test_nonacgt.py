@@ -74,6 +74,8 @@ MALFORMED = {
     "magic": lambda r: b"NTCY" + r[4:],
     "version": lambda r: _patched(r, 4, struct.pack("<I", 2)),
     "truncated header": lambda r: r[:20],
+    "reserved header byte": lambda r: _patched(r, 20, b"\x01"),
+    "reserved last header byte": lambda r: _patched(r, 31, b"\x01"),
     "truncated section header": lambda r: r[:32 + 8],
     "truncated run": lambda r: r[:-5],
     "section longer than the file": lambda r: _patched(r, 32, struct.pack("<Q", 3)),
