@@ -110,7 +110,12 @@ int ntc_ctx_synchronize(ntc_ctx *ctx);
  * substitution words in the path stream's spare words, which let the build without joint
  * runs skip the SCAN after a lone substitution (auto: on without joint runs when the table
  * carries path positions and U >= 4; 0: zeroed; after an upload get_option returns whether
- * the index in use carries them; results never depend on it).  "decode_only" (0 default
+ * the index in use carries them; results never depend on it).  "uniq_hint" (-1 auto / 0)
+ * for the NEXT upload: a 2-bit run-length code in the spare bits of the path cover's node
+ * words, which answers the parse's left-extension test without its second load (auto: on
+ * for an index of at most 2^29 nodes; environment default NTC_UNIQ_HINT=0; after an upload
+ * get_option returns whether the index in use carries the codes; ntc_index_share passes it
+ * on; results never depend on it).  "decode_only" (0 default
  * / 1) for the NEXT upload: build only what decoding reads (the walk table), none of the
  * encoder's path cover, suffix table or SCAN words; encode calls on that index then fail
  * with NTC_ERR_NO_INDEX (after the upload get_option returns whether the index in use is

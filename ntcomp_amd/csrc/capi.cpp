@@ -211,6 +211,8 @@ struct ntc_ctx {
     int subst_opt = subst_on() ? -1 : 0;  // substitution words at the next upload: -1 auto (the build without
                                                // joint runs, path positions in the table, U >= 4), 0 zeroed
     int subst_built = 0;     // the index in use carries substitution words
+    int uniq_hint_opt = uniq_hint_on() ? -1 : 0;  // run-length codes in colex_at at the next upload: -1 auto
+                                                  // (n <= kUniqHintMaxN), 0 none
     int decode_only_opt = 0;  // the next upload builds only what decode needs (walk table): no path
                               // cover, suffix table or SCAN words; encode calls then fail
     bool index_decode_only = false;  // the index in use was uploaded that way
@@ -1449,7 +1451,7 @@ struct Upload {
     void *d_walk_a = nullptr, *d_walk_b = nullptr, *d_pred = nullptr, *d_code = nullptr;
     // the path cover: has_paths says that it was built and fits 31 bits
     void *d_pstream = nullptr, *d_colex_at = nullptr, *d_pos = nullptr, *d_puniq = nullptr;
-    bool has_paths = false;
+    bool has_paths = false, uniq_hint = false;
     uint64_t tlen = 0, n_paths = 0;
     // the suffix table: levels 1..U, its presence bits, those of the filter level (F != 0)
     uint32_t U = 0;
@@ -1600,6 +1602,11 @@ int up_path_cover(Upload &u, bool dec_only) {
             if (hx.k >= kForkBlockMinK)
                 launch_path_forks(pa, st, (const uint32_t *)d_len, (const uint64_t *)d_base, (const uint32_t *)u.d_pos,
                                   (const uint4 *)u.d_pstream, (uint32_t *)u.d_colex_at, ctx->stream);
+            if (ctx->uniq_hint_opt != 0 && n <= kUniqHintMaxN) {
+                launch_path_hint(hx.k, tlen, (const uint4 *)u.d_pstream, (const uint64_t *)u.d_puniq,
+                                 (uint32_t *)u.d_colex_at, ctx->stream);
+                u.uniq_hint = true;
+            }
             HIP_TRY(ctx, hipGetLastError());
             u.has_paths = true;
         }
@@ -1637,6 +1644,8 @@ int up_joint_choice(Upload &u) {
     d.pos_of_node = (const uint32_t *)u.d_pos;
     d.puniq = (const uint64_t *)u.d_puniq;
     d.forks = has_paths && u.hx.k >= kForkBlockMinK ? 1u : 0u;
+    d.uniq_hint = has_paths && u.uniq_hint ? 1u : 0u;
+    d.node_mask = d.uniq_hint ? kNodeMaskHint : kNodeMaskPlain;
     d.absent = u.dv.absent;
     // Joint path runs pay off when MS intervals above U hold several nodes for long stretches:
     // genome collections, whose shared regions split the path cover into short unitigs (S91:
@@ -1888,6 +1897,7 @@ const Option kOptions[] = {
     {"path_link", 0, 1, kInRange, "path_link must be 0 or 1", OPT_VALUE(path_link_opt)},
     {"win", -1, 1, kInRange, "win must be -1 (auto), 0 or 1", OPT_UPLOAD(win_opt, c->dix.win_w != nullptr)},
     {"subst", -1, 0, kInRange, "subst must be -1 (auto) or 0", OPT_UPLOAD(subst_opt, c->subst_built)},
+    {"uniq_hint", -1, 0, kInRange, "uniq_hint must be -1 (auto) or 0", OPT_UPLOAD(uniq_hint_opt, c->dix.uniq_hint)},
     {"decode_only", 0, 1, kInRange, "decode_only must be 0 or 1", OPT_UPLOAD(decode_only_opt, c->index_decode_only)},
     {"ext2", 0, 1, kInRange, "ext2 must be 0 or 1", OPT_UPLOAD(ext2_opt, c->dix.rank2 != nullptr)},
     {"warm_dma", 1, 1ll << 30, kInRange, "warm_dma: 1 .. 2^30 bytes", warm_dma, nullptr},

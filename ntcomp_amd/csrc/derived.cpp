@@ -241,6 +241,11 @@ bool subst_on() {
     return !(e && std::atoi(e) == 0);
 }
 
+bool uniq_hint_on() {
+    const char *e = std::getenv("NTC_UNIQ_HINT");
+    return !(e && std::atoi(e) == 0);
+}
+
 bool path_link_on() {
     const char *e = std::getenv("NTC_PATH_LINK");
     return !(e && std::atoi(e) == 0);
@@ -304,10 +309,11 @@ void link_unitigs(const HostIndex &ix, const Derived &dv, const std::vector<uint
 // The device builds the same cover in parallel (kernels.hip "path cover"); only speed
 // depends on it -- the kernel uses a path step only when it provably equals the SBWT step
 // (encode_core.h).
-void build_paths(const HostIndex &ix, Derived &dv) {
+void build_paths(const HostIndex &ix, Derived &dv, bool hint, uint64_t hint_max_n) {
     const uint64_t n = ix.n;
     const uint32_t k = ix.k;
     dv.has_paths = false;
+    dv.uniq_hint = false;
     if (n >= (1ULL << 31) || k < 1) return;
     const std::vector<uint8_t> dummy = dummy_nodes(ix, dv);
     std::vector<uint32_t> nxt(n), prv(n, kNoNode);
@@ -377,6 +383,16 @@ void build_paths(const HostIndex &ix, Derived &dv) {
             if (u) dv.puniq[pos >> 6] |= 1ULL << (pos & 63);
         }
         b += (e - a) + k;  // last node at b+(e-a)-1; positions up to b+(e-a)+k-1 hold no node
+    }
+    // Run-length codes (encode_core.h uniq_code; kernels.hip k_path_hint on the device): r = the
+    // set puniq bits straight below j.  Only node words exist so far: the rest is kNoNode.
+    if (hint && n <= hint_max_n) {
+        uint32_t r = 0;
+        for (uint64_t j = 0; j < tlen; j++) {
+            if (dv.colex_at[j] != kNoNode) dv.colex_at[j] |= uniq_code(r) << kUniqShift;
+            r = ((dv.puniq[j >> 6] >> (j & 63)) & 1u) ? (r < 128 ? r + 1 : r) : 0u;
+        }
+        dv.uniq_hint = true;
     }
     // Fork blocks (encode_core.h fork_block, k >= kForkBlockMinK): in the k free positions
     // after a path's last node v, per character c the path position of the node v[1..k]c
@@ -462,6 +478,8 @@ DevIndex host_dev_index(const HostIndex &ix, const Derived &dv, const std::vecto
     d.pos_of_node = dv.pos_of_node.empty() ? nullptr : dv.pos_of_node.data();
     d.puniq = dv.puniq.empty() ? nullptr : dv.puniq.data();
     d.forks = dv.has_paths && ix.k >= kForkBlockMinK ? 1u : 0u;
+    d.uniq_hint = dv.has_paths && dv.uniq_hint ? 1u : 0u;
+    d.node_mask = d.uniq_hint ? kNodeMaskHint : kNodeMaskPlain;
     d.absent = dv.absent;
     d.tab = nullptr;  // see build_tab_host
     d.tab_u = 0;

@@ -21,18 +21,25 @@ struct Derived {
     bool has_paths = false;
     uint64_t tlen = 0;               // path text length (characters)
     std::vector<uint4> pstream;      // per 32 text chars: {chars lo, chars hi, end bits, 0}
-    std::vector<uint32_t> colex_at;  // per text position: node | uniq << 31, or kNoNode
+    std::vector<uint32_t> colex_at;  // per text position: node | uniq << 31 (| uniq_code << 29), or kNoNode
     std::vector<uint32_t> pos_of_node;  // per node: text position of its k-mer, or kNoNode
     std::vector<uint64_t> puniq;        // bit j: colex_at[j]'s group is a singleton
     uint64_t n_paths = 0;
+    bool uniq_hint = false;             // colex_at's node words carry the run-length code (uniq_code)
     uint32_t absent = 0;                // bit c: C[c+1] == C[c] (no node ends with c)
 };
 
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;
 
+// the run-length codes of colex_at (encode_core.h uniq_code) are written unless
+// NTC_UNIQ_HINT=0; the upload's default for ctx option "uniq_hint"
+bool uniq_hint_on();
 // Builds the path cover on the host (fills has_paths, tlen, pstream, colex_at,
 // pos_of_node, puniq); test emulation -- the upload builds the same cover on the device.
-void build_paths(const HostIndex &ix, Derived &dv);
+// With hint (and n <= hint_max_n, so that bits 29-30 of a node word are free) every node word
+// of colex_at also gets its run-length code (encode_core.h uniq_code).
+void build_paths(const HostIndex &ix, Derived &dv, bool hint = uniq_hint_on(),
+                 uint64_t hint_max_n = kUniqHintMaxN);
 // the path cover links unitigs across branches (derived.cpp link_unitigs) unless
 // NTC_PATH_LINK=0; the upload's default for ctx option "path_link"
 bool path_link_on();

@@ -101,6 +101,7 @@ struct alignas(64) Rank2Chunk {
 static_assert(sizeof(Rank2Chunk) == 64, "rank2 chunk");
 NTC_HD uint64_t rank2_blocks(uint64_t n) { return (n >> 5) + 2; }  // every block of 32 positions up to n
 
+constexpr uint32_t kNodeMaskPlain = 0x7FFFFFFFu, kNodeMaskHint = 0x1FFFFFFFu;
 struct DevIndex {
     const uint2 *rank;      // [4][rwords] rank words
     const uint8_t *lcs;     // [n]
@@ -114,7 +115,7 @@ struct DevIndex {
     // path walk (encode v2): a path cover of the de Bruijn graph, see derived.cpp
     uint32_t has_paths;
     const uint4 *pstream;         // path text in 32-char groups: {chars (2-bit, u64), end bits, 0}
-    const uint32_t *colex_at;     // node | uniq << 31 at each k-mer start, 0xFFFFFFFF elsewhere
+    const uint32_t *colex_at;     // node | uniq << 31 (| uniq_code << 29) at each k-mer start, 0xFFFFFFFF elsewhere
     const uint32_t *pos_of_node;  // text position of each real node's k-mer, or 0xFFFFFFFF
     const uint64_t *puniq;        // bit j: that node's (k-1)-suffix group is a singleton
     const uint2 *tab;             // suffix table, levels 1..tab_u (see tab_make)
@@ -130,7 +131,18 @@ struct DevIndex {
     uint32_t joint;               // 1: encode with joint path runs (k_ms4<true>, MsLaneT)
     const uint32_t *win_w;        // window words of each (U-3)-mer (see win_word), or null
     uint32_t forks;               // 1: colex_at holds fork blocks after each path end (fork_block)
+    uint32_t node_mask = kNodeMaskPlain;  // the node bits of a colex_at word (kNodeMaskHint with the codes)
+    uint32_t uniq_hint = 0;       // 1: valid colex_at words carry the run-length code (uniq_code)
 };
+
+// Run-length code of colex_at (n <= kUniqHintMaxN: bits 29-30 of a node word are free).  For a
+// text position j, r(j) = the consecutive set puniq bits at j-1, j-2, ... (ones_down from
+// j-1); the code says r >= 32 / 64 / 128, and the parse's left-extension test
+// (EntryView::run_from) needs no puniq load when that bound decides its result.
+constexpr uint64_t kUniqHintMaxN = 1ull << 29;
+constexpr uint32_t kUniqShift = 29;
+NTC_HD uint32_t uniq_code(uint32_t r) { return r >= 128 ? 3u : (r >= 64 ? 2u : (r >= 32 ? 1u : 0u)); }
+NTC_HD uint32_t uniq_floor(uint32_t code) { return (0x80402000u >> (8 * code)) & 0xFFu; }  // 0, 32, 64, 128
 
 // Fork blocks (k >= kForkBlockMinK, derived.cpp build_paths, kernels.hip k_path_forks).  A
 // path's last node at position t - 1 is followed by k free colex_at slots; the 16 from
@@ -836,36 +848,10 @@ NTC_HD void tab_ds(const DevIndex &ix, const uint64_t *Q, uint64_t qo, uint32_t 
     s = e.x;
 }
 
-// consecutive set bits at positions a, a-1, ... (at most maxn) of bitvector w.
-// NTC_ONES_PAIR=1 loads the word holding a and the one below it together, so that a run
-// crossing into the lower word (C31: up to ~100 positions of d = k per record) costs one
-// round trip instead of two dependent ones; A/B on one box (round 6, 3 runs each): C31
-// 309.7-311.7 Gbases/s with it, 309.9-310.4 without -- the parse's time is not there, so
-// it stays off.
-#ifndef NTC_ONES_PAIR
-#define NTC_ONES_PAIR 0
-#endif
+// consecutive set bits at positions a, a-1, ... (at most maxn) of bitvector w
 NTC_HD uint32_t ones_down(const uint64_t *w, uint32_t a, uint32_t maxn) {
     uint32_t cnt = 0;
     int64_t pos = a;
-#if NTC_ONES_PAIR
-    {
-        const uint32_t wi = (uint32_t)(pos >> 6), b = (uint32_t)(pos & 63);
-        NTC_TOUCH(kTrPuniq, w + wi);
-        const uint64_t hiw = w[wi], low = w[wi > 0 ? wi - 1 : 0];  // both issued before either is used
-        const uint64_t x = ~hiw << (63 - b);
-        const uint32_t z = x ? (uint32_t)__builtin_clzll(x) : 64u;
-        if (z <= b || wi == 0 || maxn <= b + 1) return (z <= b ? z : b + 1) < maxn ? (z <= b ? z : b + 1) : maxn;
-        NTC_TOUCH(kTrPuniq, w + wi - 1);
-        cnt = b + 1;
-        const uint64_t y = ~low;
-        const uint32_t z2 = y ? (uint32_t)__builtin_clzll(y) : 64u;
-        if (z2 < 64) { cnt += z2; return cnt < maxn ? cnt : maxn; }
-        cnt += 64;
-        pos -= b + 1 + 64;
-        if (pos < 0) return cnt < maxn ? cnt : maxn;
-    }
-#endif
     while (cnt < maxn) {
         const uint32_t wi = (uint32_t)(pos >> 6), b = (uint32_t)(pos & 63);
         NTC_TOUCH(kTrPuniq, w + wi);
@@ -992,8 +978,14 @@ struct EntryView {
         return (en.dk & kRunTag) ? (d < k ? d : k) : d0;
     }
     NTC_HD uint32_t sval(const Entry &en, uint32_t x) const {
+        const uint32_t s = sval_coded(en, x);
+        return (en.dk & kRunTag) ? (s & ix->node_mask) : s;
+    }
+    // S with the colex_at word's run-length code (uniq_code) still in bits 29-30 (uniq_hint; a
+    // node is < 2^29 then): DS hands it to run_from, the record takes the node bits
+    NTC_HD uint32_t sval_coded(const Entry &en, uint32_t x) const {
         if (en.dk & kRunTag) NTC_TOUCH(kTrColex, ix->colex_at + en.v + (x - en.p));
-        return (en.dk & kRunTag) ? (ix->colex_at[en.v + (x - en.p)] & 0x7FFFFFFFu) : en.v;
+        return (en.dk & kRunTag) ? (ix->colex_at[en.v + (x - en.p)] & kNodeMaskPlain) : en.v;
     }
     NTC_HD uint32_t D(uint32_t x) {
         if (covered(x)) return dval(cur, x);
@@ -1001,22 +993,40 @@ struct EntryView {
         tab_ds(*ix, Q, qo, x, d, s);
         return d;
     }
-    // d at x, and S at x when S is needed for a record (d > 11 or d = k)
+    // d at x, and S at x when S is needed for a record (d > 11 or d = k): S as sval_coded
     NTC_HD void DS(uint32_t x, uint32_t &d, uint32_t &s) {
         if (covered(x)) {
             d = dval(cur, x);
-            s = (d > 11 || d == k) ? sval(cur, x) : 0u;
+            s = (d > 11 || d == k) ? sval_coded(cur, x) : 0u;
         } else {
             tab_ds(*ix, Q, qo, x, d, s);
         }
     }
     // consecutive positions x, x-1, ... with d = k and a singleton (k-1)-suffix group
-    // (left_extend_kmer's per-step test)
-    NTC_HD uint32_t run_from(uint32_t x, uint32_t cap) const {
+    // (left_extend_kmer's per-step test).  sx: DS(x + 1)'s S, the cursor
+    // still where that call left it.  When x + 1 and x lie in one run entry, sx's code bounds
+    // from below what ones_down returns for the first stretch (the puniq bits below x + 1's path
+    // position are that stretch's); it is used only where the bound decides the result, and
+    // then no puniq word is loaded.
+    NTC_HD uint32_t run_from(uint32_t x, uint32_t cap, uint32_t sx = 0) const {
         int32_t c = e;
         uint32_t cnt = 0;
         int64_t pos = x;
         Entry en = cur;
+        const uint32_t T = ix->uniq_hint ? uniq_floor((sx >> kUniqShift) & 3u) : 0u;
+        if (T && e >= 0 && (cur.dk & kRunTag) && cur.p <= x && x < cur.p + cur.m && cap > 0) {
+            const uint32_t d0 = cur.dk & 0xFFu, tx = x - cur.p;
+            const uint32_t tk = d0 >= k ? 0u : k - d0;
+            if (tx < tk) return 0;
+            const uint32_t want = tx - tk + 1;
+            if (T >= want) {
+                if (tk > 0 || want >= cap) return want < cap ? want : cap;
+                cnt = want;
+                pos = (int64_t)cur.p - 1;
+            } else if (T >= cap) {  // ones_down gives min(r, want) >= T
+                return cap;
+            }
+        }
         while (cnt < cap && pos >= 0) {
             while (c > 0 && en.p > (uint32_t)pos) en = at(--c);
             if (!(c >= 0 && en.p <= (uint32_t)pos && (uint32_t)pos < en.p + en.m)) {
@@ -1625,8 +1635,8 @@ struct MsLaneT {
                 if (m > 0 || nohop) {
                     NTC_TOUCH(kTrColex, ix.colex_at + j + m);
                     NTC_TOUCH(kTrColex, ix.colex_at + jy() + m);
-                    l = ld_hint<256>(ix.colex_at + j + m) & 0x7FFFFFFFu;
-                    r = (ld_hint<256>(ix.colex_at + jy() + m) & 0x7FFFFFFFu) + 1;
+                    l = ld_hint<256>(ix.colex_at + j + m) & ix.node_mask;
+                    r = (ld_hint<256>(ix.colex_at + jy() + m) & ix.node_mask) + 1;
 #if defined(NTC_STATS) && !defined(__HIP_DEVICE_COMPILE__)
                     if (p < len) {  // (emulator census) the stop's first/last node: edge of the read's character?
                         const int c = (int)((Q[(qo + p) >> 5] >> (2 * ((qo + p) & 31))) & 3u);
@@ -1664,7 +1674,7 @@ struct MsLaneT {
                 ge = p;
 #if defined(NTC_STATS) && !defined(__HIP_DEVICE_COMPILE__)
                 {  // (emulator census) the node before the break: edge of the read's character?
-                    const uint32_t v = ix.colex_at[j] & 0x7FFFFFFFu;
+                    const uint32_t v = ix.colex_at[j] & ix.node_mask;
                     const int c = (int)((Q[(qo + p) >> 5] >> (2 * ((qo + p) & 31))) & 3u);
                     NTC_STAT(((ix.rank[(uint64_t)c * ix.rwords + (v >> 5)].y >> (v & 31)) & 1u) ? 11 : 12);
                 }
@@ -2076,7 +2086,7 @@ struct MsLaneT {
         if (!covers(p + 1 - U, p)) window(b, p + 1 - U);
         if (mode == kModeBrkLong) {  // the run broke at a long p: extend from the node before p
             NTC_TOUCH(kTrColex, ix.colex_at + j);
-            l = ld_hint<256>(ix.colex_at + j) & 0x7FFFFFFFu;
+            l = ld_hint<256>(ix.colex_at + j) & ix.node_mask;
             r = l + 1;
             mode = kModeExt;
 #if !NTC_CHAIN
@@ -2099,7 +2109,7 @@ struct MsLaneT {
                 NTC_TOUCH(kTrBits, ix.pair_w + M);
                 NTC_TOUCH(kTrColex, ix.colex_at + j);
                 const uint32_t pw = ld_hint<32>(ix.pair_w + M);
-                const uint32_t v = ld_hint<256>(ix.colex_at + j) & 0x7FFFFFFFu;  // node before p, for a long p
+                const uint32_t v = ld_hint<256>(ix.colex_at + j) & ix.node_mask;  // node before p, for a long p
                 if (!((pw >> (4 + c)) & 1u)) {
                     p += 1;
                     mode = kModeScan;
@@ -2115,7 +2125,7 @@ struct MsLaneT {
             NTC_TOUCH(kTrTabU, ix.tab + tab_base(U) + key_at(p, U));
             const uint2 te = load2_stream(ix.tab + tab_base(U) + key_at(p, U));
             NTC_TOUCH(kTrColex, ix.colex_at + j);
-            const uint32_t v = ld_hint<256>(ix.colex_at + j) & 0x7FFFFFFFu;  // node before p, for a long p
+            const uint32_t v = ld_hint<256>(ix.colex_at + j) & ix.node_mask;  // node before p, for a long p
             if (!tab_long(te)) {
                 skip_short(b, te, U);
                 return p >= len ? 1 : 0;
@@ -2248,7 +2258,8 @@ NTC_HD int parse_read(const DevIndex &ix, const uint64_t *Q, uint64_t qo, const 
         const uint32_t segend = i;
         uint32_t seglen;
         if (di == k && i > k + 1) {
-            const uint32_t ext = ev.run_from(i - 2, i - k - 1);
+            const uint32_t ext = ev.run_from(i - 2, i - k - 1, st);
+            ntc_stat_add(15, (uint64_t)(ext + 1) * i);  // (emulator census: a checksum of the test's results)
             const uint32_t L = k + ext;
             uint32_t m = L, pp = i;
             for (;;) {  // jump loop lib.rs:193-203
@@ -2273,7 +2284,8 @@ NTC_HD int parse_read(const DevIndex &ix, const uint64_t *Q, uint64_t qo, const 
         const uint64_t first = nrec == 0 ? 1u : 0u;
         uint64_t w;
         if (seglen > 11) {
-            w = (uint64_t)st | ((uint64_t)(seglen & 0xFFFFFFu) << 32) | (first << 56);
+            const uint32_t node = ix.uniq_hint ? st & kNodeMaskHint : st;  // (DS: S may carry the code)
+            w = (uint64_t)node | ((uint64_t)(seglen & 0xFFFFFFu) << 32) | (first << 56);
         } else {
             if (seglen > k) return -kErrRefPanic;  // encode.rs:151-152: kmer[(k - len)..k] underflows
             NTC_TOUCH(kTrQ, Q + ((qo + segend - seglen) >> 5));

@@ -584,6 +584,10 @@ void launch_path_link(const PathArgs &a, const uint4 *st, const uint32_t *len, u
 // fork blocks after each path end (k >= kForkBlockMinK), after launch_path_place
 void launch_path_forks(const PathArgs &a, const uint4 *st, const uint32_t *len, const uint64_t *base,
                        const uint32_t *pos_of_node, const uint4 *pstream, uint32_t *colex_at, hipStream_t s);
+// run-length codes into colex_at's node words (encode_core.h uniq_code; n <= kUniqHintMaxN),
+// after launch_path_place
+void launch_path_hint(uint32_t k, uint64_t tlen, const uint4 *pstream, const uint64_t *puniq, uint32_t *colex_at,
+                      hipStream_t s);
 // cut every cycle at its smallest node (prv[min] = none); *flag = 1 if any was cut
 void launch_path_cut(const PathArgs &a, const uint4 *st, uint32_t *prv, uint32_t *flag, hipStream_t s);
 // len[start] = path length (len zeroed first); vals[z] = len + k at starts, else 0;

@@ -1275,6 +1275,25 @@ void launch_path_forks(const PathArgs &a, const uint4 *st, const uint32_t *len, 
     hipLaunchKernelGGL(k_path_forks, grid_for(a.n), dim3(256), 0, s, a, st, len, base, pos_of_node, pstream, colex_at);
 }
 
+// run-length codes of the node words (encode_core.h uniq_code; derived.cpp build_paths): one
+// thread per text position, after k_path_place has set every puniq and k-mer end bit.  A
+// position holds a node exactly when a k-mer ends k - 1 further on; fork block slots and free
+// slots stay as they are.
+__global__ __launch_bounds__(256) void k_path_hint(uint32_t k, uint64_t tlen, const uint4 *pstream,
+                                                   const uint64_t *puniq, uint32_t *colex_at) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j == 0 || j >= tlen) return;  // (position 0 has nothing below it: code 0)
+    const uint64_t end = j + k - 1;
+    if (!((pstream[end >> 5].z >> (end & 31)) & 1u)) return;
+    const uint32_t code = uniq_code(ones_down(puniq, (uint32_t)(j - 1), 128));
+    if (code) colex_at[j] |= code << kUniqShift;
+}
+
+void launch_path_hint(uint32_t k, uint64_t tlen, const uint4 *pstream, const uint64_t *puniq, uint32_t *colex_at,
+                      hipStream_t s) {
+    hipLaunchKernelGGL(k_path_hint, grid_for(tlen), dim3(256), 0, s, k, tlen, pstream, puniq, colex_at);
+}
+
 void launch_path_edges(const PathArgs &a, uint32_t *prv, hipStream_t s) {
     hipLaunchKernelGGL(k_path_edges, grid_for(a.n), dim3(256), 0, s, a, prv);
 }
