@@ -730,6 +730,13 @@ constexpr uint32_t kScanExact = 4;   // filter candidates tested exactly per SCA
 #ifndef NTC_PAIR_STRIDE
 #define NTC_PAIR_STRIDE 2  // SCAN pair words at non-overlapping positions (or window words): 1 in the joint-run build, 2 always, 0 never
 #endif
+#ifndef NTC_PARSE_QLDS
+// 1: a block of k_parse4 copies its reads' piece of Q into LDS once (coalesced 16-byte loads) and
+// parses from there: every query access of the parse is then an LDS read, not a per-lane global
+// load in front of a dependent table or store address.  0: all blocks parse from global memory
+// (C91 3.85-3.88 -> 3.72-3.74 ms per step).
+#define NTC_PARSE_QLDS 1
+#endif
 #ifndef NTC_SEEK_BS
 #define NTC_SEEK_BS 1  // EntryView::seek: binary search instead of a forward scan
 #endif
@@ -824,6 +831,34 @@ NTC_HD uint64_t window2(const uint64_t *w, uint64_t off) {
     load_w2(w + i, a, b);
     return sh ? ((a >> sh) | (b << (64 - sh))) : a;
 }
+// Query readers.  The parse (parse_read, EntryView, tab_ds) takes the packed query stream as a
+// reader type: the plain reader is the pointer itself (the default, window2 above), and a staged
+// reader answers word w of the stream from a copy of words [w0, w0 + n) held elsewhere (k_parse4:
+// the block's piece of Q in LDS).  P is the copy's pointer type, address space included, so a
+// device instantiation on an LDS pointer loads with LDS instructions.
+template <class P>
+struct QStaged {
+    P buf;        // buf[i] = word w0 + i of the stream
+    uint64_t w0;
+};
+// Words a parse of reads at stream positions [b, e) can read, first and count (e > b).  Every
+// query access of the parse is a window2 at a character offset inside [b, e - 1]: tab_ds reads
+// the u <= x + 1 characters ending at position x <= e - 1 of a read, the short record the seglen
+// >= 1 characters ending inside the read.  window2 loads the word of its offset and the next one
+// whatever the shift, so the last word touched is that of character e - 1 plus ONE word of slack.
+NTC_HD uint64_t stage_first_word(uint64_t b) { return b >> 5; }
+NTC_HD uint64_t stage_word_count(uint64_t b, uint64_t e) { return ((e - 1) >> 5) + 2 - (b >> 5); }
+template <class P>
+NTC_HD uint64_t window2(const QStaged<P> &q, uint64_t off) {
+    const uint32_t i = (uint32_t)((off >> 5) - q.w0);
+    const uint32_t sh = (uint32_t)(off & 31) * 2;
+    const uint64_t a = q.buf[i], b = q.buf[i + 1];
+    return sh ? ((a >> sh) | (b << (64 - sh))) : a;
+}
+// the stream word a trace line names (emulator census)
+NTC_HD const uint64_t *q_word_ptr(const uint64_t *w, uint64_t off) { return w + (off >> 5); }
+template <class P>
+NTC_HD const uint64_t *q_word_ptr(const QStaged<P> &, uint64_t) { return nullptr; }
 // 64 bits starting at bit offset off of a bitvector
 NTC_HD uint64_t window1(const uint64_t *w, uint32_t off) {
     const uint32_t i = off >> 6, sh = off & 63;
@@ -839,7 +874,8 @@ NTC_HD uint32_t uniq_bit(const DevIndex &ix, uint32_t v) {
 // (d, S) of a position not covered by an entry, from the suffix table: u = min(x+1, U)
 // characters ending at x; long => d = u (x < U-1: the whole prefix; else the predecessor
 // is short, so d = U), short => d = m.
-NTC_HD void tab_ds(const DevIndex &ix, const uint64_t *Q, uint64_t qo, uint32_t x, uint32_t &d, uint32_t &s) {
+template <class QR>
+NTC_HD void tab_ds(const DevIndex &ix, const QR &Q, uint64_t qo, uint32_t x, uint32_t &d, uint32_t &s) {
     const uint32_t u = x + 1 < ix.tab_u ? x + 1 : ix.tab_u;
     const uint64_t key = window2(Q, qo + x + 1 - u) & ((1ULL << (2 * u)) - 1);
     NTC_TOUCH(u == ix.tab_u ? kTrTabU : kTrTabLo, ix.tab + tab_base(u) + key);
@@ -890,15 +926,17 @@ NTC_HD const Entry *ent_ptr(const Entry *E, const Entry *Ed, uint64_t es, uint32
     return j < kEntSlot ? Ed + (uint64_t)j * es : (j - kEntSlot < S ? E + j : E2 + j);
 }
 
-// Right-to-left reader of one read's entries (+ suffix table for uncovered positions).
-struct EntryView {
+// Right-to-left reader of one read's entries (+ suffix table for uncovered positions).  QR: the
+// query reader (const uint64_t * = the stream itself, or a QStaged).
+template <class QR>
+struct EntryViewT {
     const Entry *E;
     const Entry *Ed;  // dense slots (see ent_ptr)
     const Entry *E2;  // overflow reservation (see ent_ptr)
     uint32_t S;
     uint64_t es;
     const DevIndex *ix;
-    const uint64_t *Q;
+    QR Q;
     uint64_t qo;
     uint32_t k;
     int32_t e;  // cursor (-1: the read has no entries); moves left only
@@ -907,9 +945,9 @@ struct EntryView {
     // 0..3 then cost no dependent load in the seeks and run scans
     Entry c0{0, 0, 0, 0}, c1{0, 0, 0, 0}, c2{0, 0, 0, 0}, c3{0, 0, 0, 0};
     bool dc = false;
-    NTC_HD EntryView(const Entry *E_, const DevIndex *ix_, const uint64_t *Q_, uint64_t qo_, uint32_t k_, int32_t e_,
-                     const Entry *Ed_ = nullptr, uint64_t es_ = 1, const Entry *pre = nullptr,
-                     const Entry *E2_ = nullptr, uint32_t S_ = kNoLimit)
+    NTC_HD EntryViewT(const Entry *E_, const DevIndex *ix_, QR Q_, uint64_t qo_, uint32_t k_, int32_t e_,
+                      const Entry *Ed_ = nullptr, uint64_t es_ = 1, const Entry *pre = nullptr,
+                      const Entry *E2_ = nullptr, uint32_t S_ = kNoLimit)
         : E(E_), Ed(Ed_ ? Ed_ : E_), E2(E2_), S(S_), es(Ed_ ? es_ : 1), ix(ix_), Q(Q_), qo(qo_), k(k_), e(e_),
           cur{0, 0, 0, 0} {
         if (pre) {
@@ -1058,6 +1096,7 @@ struct EntryView {
         return cnt < cap ? cnt : cap;
     }
 };
+using EntryView = EntryViewT<const uint64_t *>;
 
 // ======================================================================================
 // encode pipeline:
@@ -2239,16 +2278,18 @@ struct RecPool {
 };
 
 // greedy right-to-left parse over the entries, lib.rs:175-218 (+ encode.rs:144-158).
-// Record j goes to slot[j * sstride] (j < kRecSlot) or spill[j] (rp: spill is reserved at
+// Record j goes to slot[j * sstride + sfirst] (j < kRecSlot) or spill[j] (rp: spill is reserved at
 // record kRecSlot, null when the pool ran out).  The kernel interleaves the reads' slots
 // (sstride = reads in the batch): the loop runs in lock step over a wave's lanes, so the
 // lanes' j-th records are one coalesced store.
-NTC_HD int parse_read(const DevIndex &ix, const uint64_t *Q, uint64_t qo, const Entry *E, uint32_t ne,
+template <class QR>
+NTC_HD int parse_read(const DevIndex &ix, const QR &Q, uint64_t qo, const Entry *E, uint32_t ne,
                       uint32_t len, uint64_t *slot, uint64_t *spill, uint64_t sstride = 1,
                       const Entry *Ed = nullptr, uint64_t es = 1, const Entry *pre = nullptr,
-                      const Entry *E2 = nullptr, uint32_t S = kNoLimit, const RecPool *rp = nullptr) {
+                      const Entry *E2 = nullptr, uint32_t S = kNoLimit, const RecPool *rp = nullptr,
+                      uint64_t sfirst = 0) {
     const uint32_t k = ix.k;
-    EntryView ev(E, &ix, Q, qo, k, (int32_t)ne - 1, Ed, es, pre, E2, S);
+    EntryViewT<QR> ev(E, &ix, Q, qo, k, (int32_t)ne - 1, Ed, es, pre, E2, S);
     uint32_t i = len;
     int nrec = 0;
     while (i > 0) {
@@ -2288,12 +2329,16 @@ NTC_HD int parse_read(const DevIndex &ix, const uint64_t *Q, uint64_t qo, const 
             w = (uint64_t)node | ((uint64_t)(seglen & 0xFFFFFFu) << 32) | (first << 56);
         } else {
             if (seglen > k) return -kErrRefPanic;  // encode.rs:151-152: kmer[(k - len)..k] underflows
-            NTC_TOUCH(kTrQ, Q + ((qo + segend - seglen) >> 5));
+            NTC_TOUCH(kTrQ, q_word_ptr(Q, qo + segend - seglen));
             const uint64_t bits = window2(Q, qo + segend - seglen);
             w = (bits & ((1ULL << (2 * seglen)) - 1)) | ((uint64_t)((first + 2) | (seglen << 2)) << 56);
         }
         if (nrec < (int)kRecSlot) {
-            slot[(uint64_t)nrec * sstride] = w;
+            uint64_t sf = sfirst;
+#if defined(__HIP_DEVICE_COMPILE__) && NTC_PARSE_QLDS
+            asm volatile("" : "+v"(sf));  // (as rid below: slot + sfirst is formed here, per record)
+#endif
+            slot[(uint64_t)nrec * sstride + sf] = w;
         } else {
             if (rp && nrec == (int)kRecSlot) {
                 // this record and at most one per position left of i (each starts one further left)
@@ -2305,7 +2350,13 @@ NTC_HD int parse_read(const DevIndex &ix, const uint64_t *Q, uint64_t qo, const 
                 *rp->cnt += need;
 #endif
                 if (at + need <= rp->cap) {
-                    rp->rbase[rp->rid] = (uint32_t)at;
+                    uint64_t rid = rp->rid;
+#if defined(__HIP_DEVICE_COMPILE__) && NTC_PARSE_QLDS
+                    // (the empty statement keeps rbase + rid from being formed per read ahead of
+                    // the loop, where k_parse4's staged build would hold it in scratch)
+                    asm volatile("" : "+v"(rid));
+#endif
+                    rp->rbase[rid] = (uint32_t)at;
                     spill = rp->pool + at - kRecSlot;
                 } else {
                     spill = nullptr;

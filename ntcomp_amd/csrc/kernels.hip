@@ -253,13 +253,19 @@ __device__ __forceinline__ uint32_t read_entry_count(const Enc4Args &a, uint64_t
 }
 
 #ifndef NTC_PARSE_WAVES
-#define NTC_PARSE_WAVES 8  // waves per SIMD k_parse4 is compiled for (62 VGPRs, no scratch)
+#define NTC_PARSE_WAVES 8  // waves per SIMD k_parse4 is compiled for (64 VGPRs, no scratch; 63 with the query stage)
 #endif
 #ifndef NTC_PARSE_DC
 #define NTC_PARSE_DC 1  // k_parse4 holds each read's dense entry group in registers
 #endif
-// parse of read r (k_parse4's body); returns its record count (0 on error)
-__device__ __forceinline__ uint32_t parse_one(const Enc4Args &a, uint64_t r) {
+// The stage of k_parse4 (NTC_PARSE_QLDS, encode_core.h): 1536 words = 12 KB, 8 blocks per CU = 96
+// KB of its 160 KB of LDS.  256 reads of 150 bases are 1200 words + the slack (stage_word_count);
+// a block whose reads need more (long reads) parses from global memory.
+constexpr uint32_t kParseStageWords = 1536;
+typedef const __attribute__((address_space(3))) uint64_t *lds_words_t;
+// parse of read r (k_parse4's body) through the query reader Q; returns its record count (0 on error)
+template <class QR>
+__device__ __forceinline__ uint32_t parse_one(const Enc4Args &a, uint64_t r, const QR &Q) {
     const uint64_t o0 = a.offs[0], b = a.offs[r], e = a.offs[r + 1];
     const uint64_t P = b - o0;
 #if NTC_PARSE_DC && NTC_ECOMB
@@ -276,8 +282,15 @@ __device__ __forceinline__ uint32_t parse_one(const Enc4Args &a, uint64_t r) {
     const RecPool rp{a.R, a.rcap, a.counter + kPoolCntR, a.rbase, a.status, r};
     const Entry *E1 = a.Es + r * a.S - kEntSlot;
     const Entry *E2 = ne > kEntSlot + a.S ? a.Ep + a.obase[r] - kEntSlot - a.S : nullptr;
-    const int rc = parse_read(a.ix, a.Q, P, E1, ne, (uint32_t)(e - b), a.R2 + r, nullptr, a.n_reads,
+#if NTC_PARSE_QLDS
+    // the record slots by index from the uniform base: no per-read slot pointer held over the
+    // loop (parse_read, sfirst), which the staged build has no register for
+    const int rc = parse_read(a.ix, Q, P, E1, ne, (uint32_t)(e - b), a.R2, nullptr, a.n_reads,
+                              a.Ed + r * kEntSlot, 1, pre, E2, a.S, &rp, r);
+#else
+    const int rc = parse_read(a.ix, Q, P, E1, ne, (uint32_t)(e - b), a.R2 + r, nullptr, a.n_reads,
                               a.Ed + r * kEntSlot, 1, pre, E2, a.S, &rp);
+#endif
     if (rc < 0) {
         atomicMin(a.status, (unsigned long long)((r << 8) | (uint64_t)(-rc)));
         a.rec_count[r] = 0;
@@ -358,10 +371,46 @@ __global__ __launch_bounds__(256, kJoint ? NTC_MS_WAVES_J : NTC_MS_WAVES) void k
 __global__ __launch_bounds__(256, NTC_PARSE_WAVES) void k_parse4(Enc4Args a) {
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t cnt = 0;
+#if NTC_PARSE_QLDS
+    // The block's reads [r0, r1) cover stream positions [b, e): words stage_first_word(b) ...
+    // + stage_word_count(b, e) are all its parses can read (the count holds window2's one word of
+    // slack).  The stage starts at the even word at or below the first, so the copy moves aligned
+    // 16-byte pairs; the last pair may hold one word past the counted ones, inside Q's padding
+    // (capi.cpp sizes Q four words past the batch's last).  The decision depends on the offsets
+    // alone, so it is the same for every thread; all 256 threads reach the barrier, those past
+    // n_reads too, and the status is looked at only after it (it may change while blocks run).
+    // The two parses are separate instantiations: the staged one holds no global query pointer
+    // and loads with ds_read_b64 only, the other is the code of a build without the stage.
+    __shared__ __attribute__((aligned(16))) uint64_t s_q[kParseStageWords];
+    const uint64_t r0 = (uint64_t)blockIdx.x * 256;
+    const uint64_t r1 = r0 + 256 < a.n_reads ? r0 + 256 : a.n_reads;
+    bool staged = false;
+    uint64_t w0 = 0;
+    if (r0 < a.n_reads) {
+        const uint64_t o0 = a.offs[0], b = a.offs[r0] - o0, e = a.offs[r1] - o0, total = a.offs[a.n_reads] - o0;
+        if (a.offs[r0] >= o0 && b < e && e <= total) {  // (offsets out of order: k_ms4 has set the status)
+            w0 = stage_first_word(b) & ~1ull;
+            const uint64_t n = stage_first_word(b) - w0 + stage_word_count(b, e);
+            staged = n <= kParseStageWords;
+            if (staged) {
+                const uint32_t pairs = (uint32_t)((n + 1) / 2);
+                const uint4 *src = reinterpret_cast<const uint4 *>(a.Q + w0);
+                for (uint32_t i = threadIdx.x; i < pairs; i += 256) reinterpret_cast<uint4 *>(s_q)[i] = src[i];
+            }
+        }
+    }
+    __syncthreads();
     if (r < a.n_reads) {
         if (*a.status != ~0ull) a.rec_count[r] = 0;
-        else cnt = parse_one(a, r);
+        else if (staged) cnt = parse_one(a, r, QStaged<lds_words_t>{(lds_words_t)s_q, w0});
+        else cnt = parse_one(a, r, (const uint64_t *)a.Q);
     }
+#else
+    if (r < a.n_reads) {
+        if (*a.status != ~0ull) a.rec_count[r] = 0;
+        else cnt = parse_one(a, r, (const uint64_t *)a.Q);
+    }
+#endif
     // the wave's record total: k_emit4 turns the scanned totals into record offsets
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
     if ((threadIdx.x & 63) == 0 && r < a.n_reads) a.wave_cnt[r >> 6] = cnt;
