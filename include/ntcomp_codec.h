@@ -230,7 +230,25 @@ int ntc_nx_read(const char *path, ntc_nx_run **runs, uint64_t *n_runs, uint32_t 
  *             first 4 bytes; per symbol slot = x & 4095, s the symbol with c_s <= slot < c_s +
  *             f_s, x = f_s (x >> 12) + slot - c_s, and while x < L: x = x << 8 | next byte.  At
  *             the end x = L and the span's bytes are used up.
- * A section with n_syms <= 1 has an empty body. */
+ * A section with n_syms <= 1 has an empty body.
+ *
+ * Smoothing inside long matches (lossy), three more options of the context:
+ *   "quality_smooth"     0 (off, default) or M in 12..16777215
+ *   "quality_smooth_to"  the target T, a byte in '$'..'~' (default 'I')
+ *   "quality_smoothed"   read-only: the bytes the last ntc_encode_pack_fastq call replaced
+ *                        ("quality_smoothed_total": of all calls since quality_smooth was set)
+ * A read's records come in archive order, rightmost first, with lengths L_0 .. L_{m-1}; record j
+ * covers positions [e_j - L_j, e_j) of the read, e_0 = its bases, e_{j+1} = e_j - L_j.  A
+ * position is trusted iff it lies in a long record (flag bit 1 of byte 7 clear) with L_j >= M.
+ * With tab the mode's table: a byte q = tab[input] at a trusted position with q > tab['#']
+ * becomes tab[T]; every other byte stays (scores at or below the image of '#' are the no-call
+ * marker, which is never raised).  The pass runs on the GPU once the call has its final
+ * records, and everything after it sees the smoothed bytes: the alphabets and widths, the
+ * packed words, the rANS tables and streams, and the qual digest (which is that of the bytes
+ * decode prints).  The records, the packed blocks, every other side list and the section
+ * format are those of a call without it.  ntc_encode_pack_fastq returns NTC_ERR_INVALID_ARG
+ * when M is set under qualities = 0, or when tab[T] <= tab['#'] (under mode 2, T in '$'..'*').
+ * The options hold until they are changed. */
 typedef struct ntc_qual_meta {
     uint64_t n_reads;       /* reads of the block                                          */
     uint64_t n_quals;       /* their quality bytes (= their bases)                         */

@@ -81,6 +81,34 @@ def _coder_code(coder):
     return QUALITY_CODERS[coder] if isinstance(coder, str) else int(coder)
 
 
+# smoothing inside long matches (ctx options "quality_smooth", "quality_smooth_to"): a quality
+# inside a long record of at least M bases becomes the target byte; 0 = off
+QUALITY_SMOOTH_MIN, QUALITY_SMOOTH_MAX, QUALITY_SMOOTH_DEFAULT = 12, 16777215, 32
+QUALITY_SMOOTH_TO = b"I"
+
+
+def _smooth_code(m):
+    """quality_smooth as the option takes it: 0 (off) or M in 12..16777215."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+        raise ValueError(f"quality_smooth must be an integer, not {m!r}")
+    if m != 0 and not QUALITY_SMOOTH_MIN <= m <= QUALITY_SMOOTH_MAX:
+        raise ValueError(f"quality_smooth must be 0 (off) or {QUALITY_SMOOTH_MIN}..{QUALITY_SMOOTH_MAX}, not {m}")
+    return int(m)
+
+
+def _smooth_to_code(to):
+    """quality_smooth_to as the option takes it: one byte in '$'..'~' (bytes, str or int)."""
+    if isinstance(to, str):
+        to = to.encode("latin-1", errors="replace")
+    if isinstance(to, (bytes, bytearray)):
+        if len(to) != 1:
+            raise ValueError(f"quality_smooth_to must be one byte, not {bytes(to)!r}")
+        to = to[0]
+    if isinstance(to, bool) or not isinstance(to, (int, np.integer)) or not ord("$") <= to <= ord("~"):
+        raise ValueError(f"quality_smooth_to must be a byte in '$'..'~', not {to!r}")
+    return int(to)
+
+
 # name modes (ctx option "names", include/ntcomp_codec.h)
 NAMES = {"drop": 0, "keep": 1, "id": 2}
 NAME_MAX, NAME_GROUP = 4095, 64
@@ -696,6 +724,36 @@ class GpuContext:
     def quality_coder(self, coder):
         self.set_option("quality_coder", _coder_code(coder))
 
+    def _qsmooth(self, m):
+        return GpuContext._Option(self, "quality_smooth", None if m is None else _smooth_code(m))
+
+    def _qsmooth_to(self, to):
+        return GpuContext._Option(self, "quality_smooth_to", None if to is None else _smooth_to_code(to))
+
+    @property
+    def quality_smooth(self):
+        """Smoothing inside long matches ("quality_smooth"): 0 off, or M: a quality above the mode's image of
+        '#' that lies in a long record of at least M bases becomes quality_smooth_to."""
+        return self.get_option("quality_smooth")
+
+    @quality_smooth.setter
+    def quality_smooth(self, m):
+        self.set_option("quality_smooth", _smooth_code(m))
+
+    @property
+    def quality_smooth_to(self):
+        """The byte smoothing writes ("quality_smooth_to"), as bytes of length 1."""
+        return bytes([self.get_option("quality_smooth_to")])
+
+    @quality_smooth_to.setter
+    def quality_smooth_to(self, to):
+        self.set_option("quality_smooth_to", _smooth_to_code(to))
+
+    @property
+    def quality_smoothed(self):
+        """Quality bytes the last encode_pack_fastq call replaced ("quality_smoothed", read-only)."""
+        return self.get_option("quality_smoothed")
+
     def qualities(self):
         """The quality sections of the last encode_pack_fastq call under "keep" or "bin8"
         (ntc_encode_qualities) -> (list of QualMeta, their packed words as bytes)."""
@@ -936,7 +994,7 @@ class GpuContext:
         return bases[:nb.value].copy(), offs
 
     def encode_pack_fastq(self, text, n_reads, block_reads=65536, non_acgt=None, qualities=None, names=None,
-                          quality_coder=None, digests=None):
+                          quality_coder=None, digests=None, quality_smooth=None, quality_smooth_to=None):
         """encode_pack on FASTQ text parsed on the GPU (ntc_encode_pack_fastq) -> (list of
         BlockMeta, payload bytes, bases encoded).  With non_acgt (as for encode) the exception
         runs come fourth.  With qualities ("drop", "keep" or "bin8"; the call runs under that
@@ -944,13 +1002,15 @@ class GpuContext:
         "keep" or "id") the name sections come last, as names() returns them.  quality_coder ("pack" or
         "rans"; the call runs under it): the coder of the quality sections.  With digests (True / False;
         the call runs under it) the blocks' DigestMeta come after all of those, as encode_digests()
-        returns them."""
+        returns them.  quality_smooth (0 or M) and quality_smooth_to (one byte) hold for the call
+        only, as quality_coder does: the qualities inside long records of at least M bases become
+        that byte before they are coded."""
         t = np.frombuffer(bytes(text), dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
         nb = (n_reads + block_reads - 1) // block_reads
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
         with self._policy(non_acgt), self._qmode(qualities), self._nmode(names), self._qcoder(quality_coder), \
-                self._digests(digests):
+                self._digests(digests), self._qsmooth(quality_smooth), self._qsmooth_to(quality_smooth_to):
             rc = self.L.ntc_encode_pack_fastq(self.h, _p(t), len(text), n_reads, block_reads, metas,
                                               ctypes.byref(out), ctypes.byref(used), ctypes.byref(nbases),
                                               ctypes.byref(bad))
@@ -987,7 +1047,8 @@ class GpuContext:
         self.set_option("paired", _pair_code(mode))
 
     def encode_pack_fastq_paired(self, text1, text2, n_pairs, block_reads=65536, non_acgt=None, qualities=None,
-                                 names=None, quality_coder=None, digests=None):
+                                 names=None, quality_coder=None, digests=None, quality_smooth=None,
+                                 quality_smooth_to=None):
         """encode_pack_fastq of the two mate texts woven on the GPU
         (ntc_encode_pack_fastq_paired): record p of text1, then record p of text2.  Needs
         `paired` set; returns what encode_pack_fastq returns for the interleaved text."""
@@ -997,7 +1058,7 @@ class GpuContext:
         metas = (BlockMeta * max(nb, 1))()
         out, used, nbases, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int64(-1)
         with self._policy(non_acgt), self._qmode(qualities), self._nmode(names), self._qcoder(quality_coder), \
-                self._digests(digests):
+                self._digests(digests), self._qsmooth(quality_smooth), self._qsmooth_to(quality_smooth_to):
             rc = self.L.ntc_encode_pack_fastq_paired(self.h, _p(t1), len(text1), _p(t2), len(text2), n_pairs,
                                                      block_reads, metas, ctypes.byref(out), ctypes.byref(used),
                                                      ctypes.byref(nbases), ctypes.byref(bad))

@@ -65,6 +65,19 @@ class _Stats:
             log(json.dumps({"stats": d, "wall_s": round(self.time() - self.t0, 3), **extra}))
 
 
+SMOOTH_MIN, SMOOTH_MAX, SMOOTH_DEFAULT = 12, 16777215, 32  # --quality-smooth [M]
+
+
+def _smooth_default(argv):
+    """--quality-smooth may stand without a value: it takes the next argument only when that is
+    a number (as the native CLI does), else M = 32."""
+    out = []
+    for i, a in enumerate(argv):
+        bare = a == "--quality-smooth" and not (i + 1 < len(argv) and argv[i + 1].isascii() and argv[i + 1].isdigit())
+        out.append(f"--quality-smooth={SMOOTH_DEFAULT}" if bare else a)
+    return out
+
+
 def _bad_args(msg):
     """An argument error found after parsing: status 2, before anything is loaded or written
     (the native CLI's bad_args, same messages)."""
@@ -190,6 +203,22 @@ def _check_q_args(args):
         _bad_args("encode: --quality-coder: pack or rans")
     if args.quality_coder is not None and args.qualities == "drop":
         _bad_args("encode: --quality-coder needs --qualities keep or bin8")
+    # smoothing inside long matches: --quality-smooth [M] and --quality-smooth-to C
+    for flag, value in (("--quality-smooth", args.quality_smooth), ("--quality-smooth-to", args.quality_smooth_to)):
+        if value is not None and args.qualities == "drop":
+            _bad_args(f"encode: {flag} needs --qualities keep or bin8")
+    if args.quality_smooth is not None:
+        m = args.quality_smooth
+        if not (m.isascii() and m.isdigit() and len(m) <= 8 and SMOOTH_MIN <= int(m) <= SMOOTH_MAX):
+            _bad_args(f"encode: --quality-smooth: M must be {SMOOTH_MIN}..{SMOOTH_MAX}")
+        args.quality_smooth = int(m)
+    if args.quality_smooth_to is not None:
+        c = args.quality_smooth_to.encode("utf-8", errors="surrogateescape")
+        if len(c) != 1 or not ord("$") <= c[0] <= ord("~"):
+            _bad_args("encode: --quality-smooth-to: one printable byte in '$'..'~'")
+        if args.qualities == "bin8" and c[0] <= ord("*"):
+            _bad_args("encode: --quality-smooth-to: under bin8 the byte must lie above '*', or its level is that of '#'")
+        args.quality_smooth_to = c
 
 
 def _check_n_args(args):
@@ -348,8 +377,11 @@ def cmd_encode(args):
                                                        "nx_fd": nx_file.fileno() if nx_file else -1}
         if q_file:
             nx_args.update(qualities=args.qualities, q_fd=q_file.fileno())
-            for c in ctxs:  # the pipeline takes the coder from its contexts
+            for c in ctxs:  # the pipeline takes the coder and the smoothing from its contexts
                 c.quality_coder = args.quality_coder or "pack"
+                c.quality_smooth = args.quality_smooth or 0
+                if args.quality_smooth_to is not None:
+                    c.quality_smooth_to = args.quality_smooth_to
         if n_file:
             nx_args.update(names=args.names, n_fd=n_file.fileno())
         if d_file:
@@ -371,6 +403,7 @@ def cmd_encode(args):
             n_file.close()
         if d_file:
             d_file.close()
+        smoothed = sum(c.get_option("quality_smoothed_total") for c in ctxs) if args.quality_smooth else 0
         for c in ctxs:
             c.close()
     if res["dropped_blocks"]:
@@ -386,6 +419,8 @@ def cmd_encode(args):
                                                                         "runs_in_dropped_blocks"), 0)).items()},
               **({"qualities": args.qualities, "quality_coder": args.quality_coder or "pack",
                   **{"q_" + k: v for k, v in res["q"].items()}} if "q" in res else {}),
+              **({"quality_smooth": args.quality_smooth, "quality_smooth_to": (args.quality_smooth_to or b"I").decode(),
+                  "q_smoothed": smoothed} if args.quality_smooth else {}),
               **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}),
               **({"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"} if "d" in res else {}),
               **({"pairs": res["p"]["pairs"], "mate_check": "off" if pair_mode == "nocheck" else "ids",
@@ -541,6 +576,12 @@ def main(argv=None):
     e.add_argument("--quality-coder", default=None, metavar="CODER",
                    help="with --qualities keep or bin8: pack (default; packed codes, deflated on the host) or rans "
                         "(order-1 rANS coded on the GPU, no host deflate)")
+    e.add_argument("--quality-smooth", default=None, metavar="M",
+                   help="with --qualities keep or bin8: smooth the scores inside long matches to the index (lossy): a "
+                        "score above '#' that lies in a long record of at least M bases (12..16777215; 32 when M is "
+                        "left out) becomes the --quality-smooth-to byte")
+    e.add_argument("--quality-smooth-to", default=None, metavar="C",
+                   help="the byte --quality-smooth writes: one of '$'..'~' (default I; under bin8 above '*')")
     e.add_argument("--names", default="drop", metavar="MODE",
                    help="FASTQ read names: drop (default), keep (lossless: the header line after '@') or id (the name up "
                         "to its first space or tab, lossy); keep and id write them, front-coded on the GPU, to the "
@@ -602,7 +643,7 @@ def main(argv=None):
     n = sub.add_parser("info", help="What an encoded file holds, from its block headers (no index, no GPU)")
     n.add_argument("input_path", help="File with encoded fastX data.")
     n.add_argument("--blocks", action="store_true", help="one line per block")
-    args = ap.parse_args(argv)
+    args = ap.parse_args(_smooth_default(sys.argv[1:] if argv is None else list(argv)))
     if getattr(args, "threads", None) == 0:
         import ntcomp_amd as nt
         args.threads = nt.host_threads()

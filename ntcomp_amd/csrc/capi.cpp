@@ -22,6 +22,7 @@
 #include "nonacgt_core.h"
 #include "qrans_core.h"
 #include "quality_core.h"
+#include "qsmooth_core.h"
 #include "names_core.h"
 #include "digest_core.h"
 #include "pair_core.h"
@@ -110,10 +111,16 @@ struct QualState {
     int mode = 0;
     int coder = 0;  // option "quality_coder": 0 pack, 1 rans (qrans.hip); coder_last: of those sections
     int coder_last = 0;
+    // options "quality_smooth" (0 off, or M) and "quality_smooth_to"; smoothed: bytes the last call replaced
+    int smooth = 0, smooth_to = (int)kQsToDefault;
+    uint64_t smoothed = 0, smoothed_total = 0;  // (the total: of all calls since "quality_smooth" was last set)
+    // a smoothing call in flight: what q_pack prepared and q_finish launches after the encode
+    QREncArgs deferred{};
+    uint64_t deferred_total = 0;
     uint64_t blocks = 0, words = 0, reads = 0;
     uint32_t block_reads = 0;
     Pending<ntc_qual_meta> pending;
-    void begin() { blocks = words = reads = 0; }  // an encode call starts: the last call's sections are gone
+    void begin() { blocks = words = reads = smoothed = 0; }  // an encode call starts: the last call's sections are gone
 };
 
 // read names (names.hip): the mode (0 drop, 1 keep, 2 id), the sections the last
@@ -685,7 +692,10 @@ int nx_patch(ntc_ctx *ctx, const std::vector<ntc_nx_run> &runs, uint32_t sub, ui
 // preset again by the encode that follows), which reaches the host with the payload's size
 // in mailbox words kBoxQualStatus and kBoxQualWords at the encode call's own status sync
 // (q_collect).  Mode 0 returns before anything is launched.
-int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t total, uint32_t block_reads) {
+//
+// defer (option "quality_smooth"): only k_q_gather runs here, and q_finish does the rest once
+// the encode has its final records; the workspace of both halves is ensured here.
+int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t total, uint32_t block_reads, bool defer) {
     if (ctx->qual.mode == 0 || n_reads == 0) return NTC_OK;
     const uint64_t nb = (n_reads + block_reads - 1) / block_reads;
     void *quals, *blk, *pay;
@@ -715,8 +725,16 @@ int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t tota
     a.box = ctx->h_box;
     ctx->h_box[kBoxQualStatus] = ~0ull;  // (the last call's kernels are done: every encode call ends synchronised)
     ctx->h_box[kBoxQualWords] = 0;
+    ctx->h_box[kBoxQualSmoothed] = 0;
     ctx->qual.coder_last = ctx->qual.coder;
-    if (!rans) {
+    if (defer) {
+        ctx->qual.deferred = QREncArgs{};
+        ctx->qual.deferred.q = a;
+        ctx->qual.deferred_total = total;
+        launch_quality_lines(a, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+        if (!rans) return NTC_OK;
+    } else if (!rans) {
         launch_quality_pack(a, total, ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
         return NTC_OK;
@@ -737,9 +755,44 @@ int q_pack(ntc_ctx *ctx, const uint64_t *d_offs, uint64_t n_reads, uint64_t tota
     ra.offs = ra.sizes + (S + 1);
     ra.tmp = ra.offs + (S + 1);
     ra.spans_max = S;
+    if (defer) {
+        ctx->qual.deferred = ra;
+        return NTC_OK;
+    }
     launch_quality_gather(a, ctx->stream);
     launch_quality_rans(ra, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
+    return NTC_OK;
+}
+int dg_add(ntc_ctx *ctx, uint32_t c, const void *buf, uint64_t buf_bytes, const uint64_t *offs, const uint32_t *start,
+           const uint32_t *len, uint64_t n_reads, uint32_t block_reads);
+// The rest of a deferred quality pass, after encode_pack_staged (which ended synchronised, its
+// final records in WS_STAGE_RECS, their offsets behind d_offs).  encoded: the rule, the
+// presence maps, the alphabets, the coder and the qual digest; otherwise only k_q_alpha, so
+// that the gather's verdict reaches the mailbox.  Ends with the pass's own sync.
+int q_finish(ntc_ctx *ctx, bool encoded, const uint64_t *d_offs, uint64_t n_reads, uint64_t total, uint32_t block_reads,
+             uint32_t dg) {
+    const QREncArgs &ra = ctx->qual.deferred;
+    if (encoded) {
+        QSmoothArgs sa{};
+        sa.q = ra.q;
+        sa.recs = (const uint64_t *)ctx->ws[WS_STAGE_RECS].p;
+        sa.roffs = d_offs + (n_reads + 1);
+        sa.m = (uint32_t)ctx->qual.smooth;
+        sa.to = (uint32_t)ctx->qual.smooth_to;
+        sa.count = ra.q.status + 1;  // (the status word has 64 bytes to itself)
+        launch_quality_smooth(sa, ctx->stream);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_box + kBoxQualSmoothed, sa.count, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    launch_quality_alpha(ra.q, ctx->stream);
+    if (encoded && ctx->qual.coder_last == 1) launch_quality_rans(ra, ctx->stream);
+    else if (encoded) launch_quality_spans(ra.q, ctx->qual.deferred_total, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    int rc;
+    if (encoded && (dg & kDgQual) &&
+        (rc = dg_add(ctx, 2, ra.q.quals, total, d_offs, nullptr, nullptr, n_reads, block_reads)))
+        return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NTC_OK;
 }
 // After the encode call's sync: the quality pass's verdict.  A read it refused fails the call.
@@ -755,6 +808,8 @@ int q_collect(ntc_ctx *ctx, uint64_t n_reads, uint32_t block_reads, int64_t *bad
     }
     ctx->qual.blocks = (n_reads + block_reads - 1) / block_reads;
     ctx->qual.words = box(ctx, kBoxQualWords);
+    ctx->qual.smoothed = box(ctx, kBoxQualSmoothed);
+    ctx->qual.smoothed_total += ctx->qual.smoothed;
     ctx->qual.reads = n_reads;
     ctx->qual.block_reads = block_reads;
     return NTC_OK;
@@ -1888,6 +1943,7 @@ int get_workspace_bytes(const ntc_ctx *ctx, int64_t *value) {
 #define OPT_DEV(f) {"dev_" #f, 0, 0, kInRange, nullptr, nullptr, \
                     [](const ntc_ctx *c, int64_t *v) { return get_dev_addr(c, c->dix.f, v); }}
 
+constexpr const char *kSmoothMsg = "quality_smooth must be 0 (off) or 12..16777215";
 const Option kOptions[] = {
     {"encode_variant", 1, 4, kEndsOnly, "encode_variant must be 4 (default) or 1 (A/B baseline)", OPT_VALUE(encode_variant)},
     {"tab_u", 0, kTabMaxU, kInRange, "tab_u must be 0 (default) or 1..15", OPT_UPLOAD(tab_u_opt, c->dix.tab_u)},
@@ -1910,6 +1966,19 @@ const Option kOptions[] = {
     // the side data of FASTQ and FASTA text (ntcomp_codec.h, ntcomp_gpu.h)
     {"qualities", 0, 2, kInRange, "qualities must be 0 (drop), 1 (keep) or 2 (bin8)", OPT_VALUE(qual.mode)},
     {"quality_coder", 0, 1, kInRange, "quality_coder must be 0 (pack) or 1 (rans)", OPT_VALUE(qual.coder)},
+    // smoothing inside long matches: refused at the call when qualities is 0, or when the mode's image of the
+    // target does not exceed that of '#'
+    {"quality_smooth", 0, kQsMaxM, kInRange, kSmoothMsg,
+     [](ntc_ctx *c, int64_t v) {
+         if (v && v < kQsMinM) return set_err(c, NTC_ERR_INVALID_ARG, kSmoothMsg);
+         c->qual.smooth = (int)v;
+         c->qual.smoothed_total = 0;
+         return (int)NTC_OK;
+     },
+     OPT_GET(c->qual.smooth)},
+    {"quality_smooth_to", kQsToLo, kQsToHi, kInRange, "quality_smooth_to must be a byte in '$'..'~'", OPT_VALUE(qual.smooth_to)},
+    OPT_READ("quality_smoothed", c->qual.smoothed),
+    OPT_READ("quality_smoothed_total", c->qual.smoothed_total),  // of the calls since quality_smooth was set: the CLIs' --stats
     {"names", 0, 2, kInRange, "names must be 0 (drop), 1 (keep) or 2 (id)", OPT_VALUE(names.mode)},
     {"discard_text", 0, 1, kInRange, "discard_text must be 0 or 1", OPT_VALUE(discard_text)},
     {"paired", 0, 2, kInRange, "paired must be 0 (off), 1 (ids) or 2 (no check)", OPT_VALUE(pair.mode)},
@@ -2583,6 +2652,11 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
     if (ctx->encode_variant != 4) return set_err(ctx, NTC_ERR_UNSUPPORTED, "encode_pack needs encode_variant 4");
     if (ctx->pair.mode && ((n_reads & 1) || (block_reads & 1)))
         return set_err(ctx, NTC_ERR_INVALID_ARG, "paired: n_reads and block_reads must be even");
+    const bool smooth = ctx->qual.smooth != 0;
+    if (smooth && ctx->qual.mode == 0)
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "quality_smooth needs qualities 1 (keep) or 2 (bin8)");
+    if (smooth && qs_target((uint32_t)ctx->qual.mode, (uint32_t)ctx->qual.smooth_to) <= qs_floor((uint32_t)ctx->qual.mode))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "quality_smooth_to: under bin8 the target's image must exceed that of '#'");
     void *d_bases, *d_offs;
     uint64_t total = 0;
     int rc = fastq_stage(ctx, fastq, fastq_bytes, n_reads, &d_bases, &d_offs, &total, bad_read, pair,
@@ -2596,8 +2670,9 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
     const uint32_t dg = dg_components(ctx, true);
     if (dg && (rc = dg_init(ctx, (const uint64_t *)d_offs, n_reads, block_reads, dg, 0))) return rc;
     // the quality lines are packed from the text while the reads are encoded (mode 0: nothing runs)
-    if ((rc = q_pack(ctx, (const uint64_t *)d_offs, n_reads, total, block_reads))) return rc;
-    if ((dg & kDgQual) && (rc = dg_add(ctx, 2, ctx->ws[WS_Q_QUALS].p, total, (const uint64_t *)d_offs, nullptr, nullptr,
+    // (smoothing: only the gather; the rest and the qual digest follow the encode, q_finish below)
+    if ((rc = q_pack(ctx, (const uint64_t *)d_offs, n_reads, total, block_reads, smooth))) return rc;
+    if (!smooth && (dg & kDgQual) && (rc = dg_add(ctx, 2, ctx->ws[WS_Q_QUALS].p, total, (const uint64_t *)d_offs, nullptr, nullptr,
                                       n_reads, block_reads)))
         return rc;
     // and the names are front-coded from it (mode 0: nothing runs)
@@ -2614,6 +2689,16 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
     };
     rc = encode_pack_staged(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offs, n_reads, total, block_reads, meta,
                             payload, payload_bytes, bad_read, restage, dg);
+    if (smooth) {
+        if (rc) (void)hipStreamSynchronize(ctx->stream);  // (as below)
+        const int frc = q_finish(ctx, rc == NTC_OK, (const uint64_t *)d_offs, n_reads, total, block_reads, dg);
+        if (frc && !rc) {
+            std::free(*payload);
+            *payload = nullptr;
+            *payload_bytes = 0;
+            rc = frc;
+        }
+    }
     if (ctx->qual.mode == 0 && ctx->names.mode == 0) return rc;
     // a read the quality or the names pass refused fails the call, whatever the encode said of it
     if (rc) (void)hipStreamSynchronize(ctx->stream);  // (an encode that failed early may not have synchronised)

@@ -349,6 +349,24 @@ uint64_t q_payload_words_max(uint64_t total, uint64_t n_blocks);
 void launch_quality_pack(const QEncArgs &a, uint64_t total, hipStream_t s);
 // the first two steps alone (k_q_gather, k_q_alpha): what both coders start from
 void launch_quality_gather(const QEncArgs &a, hipStream_t s);
+// Smoothing inside long matches (option "quality_smooth", qsmooth_core.h): the steps one by
+// one, since k_q_smooth needs the encode's final records between the first and the rest.
+//   launch_quality_lines   k_q_gather alone (presets the status and the presence maps)
+//   launch_quality_smooth  the rule in place over quals, the presence maps rebuilt from the
+//                          smoothed bytes, *count = bytes replaced (zeroed here)
+//   launch_quality_alpha   k_q_alpha alone
+//   launch_quality_spans   k_q_pack alone (coder 1: launch_quality_rans instead)
+// recs / roffs: the records of the batch and the n_reads + 1 record offsets, from 0.
+struct QSmoothArgs {
+    QEncArgs q;
+    const uint64_t *recs, *roffs;
+    uint32_t m, to;  // the options: a trusted record has >= m bases, the target is the mode's image of `to`
+    unsigned long long *count;
+};
+void launch_quality_lines(const QEncArgs &a, hipStream_t s);
+void launch_quality_smooth(const QSmoothArgs &a, hipStream_t s);
+void launch_quality_alpha(const QEncArgs &a, hipStream_t s);
+void launch_quality_spans(const QEncArgs &a, uint64_t total, hipStream_t s);
 // Coder 1, the order-1 rANS coder (qrans.hip, qrans_core.h), in place of k_q_pack after
 // launch_quality_gather.  With S = qr_spans_max(total, n_blocks): counts: n_blocks *
 // kQRCountStride words (zeroed here), cum: n_blocks * kQRCumStride u16, scratch: S *
@@ -551,6 +569,7 @@ enum BoxWord {
     kBoxWeave = 10, kBoxMateCheck = 11,      // pairs.hip k_pair_box: the weave's status, the mate check's
     kBoxPairFirst = 12,                      // pairs.hip k_pair_split: bytes of the first part
     kBoxWindow = 13,                         // window.hip: bytes of the text window
+    kBoxQualSmoothed = 14,                   // quality.hip k_q_smooth: bytes replaced (copied from the device counter)
     kBoxWords = 16
 };
 void launch_status_box(const unsigned long long *status, const uint64_t *a, const uint64_t *b, const uint64_t *c,

@@ -10,6 +10,7 @@
 //                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
 //                 [--non-acgt error|mask|keep] [--exceptions PATH]
 //                 [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]
+//                 [--quality-smooth [M]] [--quality-smooth-to C]
 //                 [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]
 //                 [--mate-file R2 | --interleaved] [--mate-check ids|off] FILE > encoded.dat
 //                 (paired-end reads: FILE holds the mate-1 records and R2 the mate-2 records, or FILE
@@ -81,7 +82,8 @@ bool takes_value(const std::string &o) {
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
                               "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
-                              "--qualities", "--quality-file", "--quality-coder", "--names", "--name-file",
+                              "--qualities", "--quality-file", "--quality-coder", "--quality-smooth",
+                              "--quality-smooth-to", "--names", "--name-file",
                               "--digest-file", "--mate-file", "--mate-check", "--mate-out", "--reads", "--shard"};
     for (const char *x : v)
         if (o == x) return true;
@@ -97,6 +99,14 @@ bool is_switch(const std::string &o) {
 
 void usage(FILE *f = stderr);
 
+// all of s is decimal digits (at least one, at most 18: no overflow)
+bool all_digits(const std::string &s) {
+    if (s.empty() || s.size() > 18) return false;
+    for (const char c : s)
+        if (c < '0' || c > '9') return false;
+    return true;
+}
+
 Args parse(int argc, char **argv, int from) {
     Args a;
     for (int i = from; i < argc; i++) {
@@ -111,7 +121,9 @@ Args parse(int argc, char **argv, int from) {
                 std::printf("ntcomp %s\n", kVersion);
                 std::exit(0);
             }
-            if (s.size() > 2 && s[1] != '-' && takes_value(s.substr(0, 2))) {  // clap's attached short value: -t8, -k31
+            if (s == "--quality-smooth" && !(i + 1 < argc && all_digits(argv[i + 1]))) {
+                a.kv.push_back({s, "32"});  // the one flag whose value may be left out: the next argument only when a number
+            } else if (s.size() > 2 && s[1] != '-' && takes_value(s.substr(0, 2))) {  // clap's attached short value: -t8, -k31
                 a.kv.push_back({s.substr(0, 2), s.substr(2)});
             } else if (eq != std::string::npos && s.rfind("--", 0) == 0) {
                 const std::string name = s.substr(0, eq);
@@ -274,6 +286,17 @@ int cmd_encode(const Args &a) {
     const int q_coder = qc_name == "pack" ? 0 : qc_name == "rans" ? 1 : -1;
     if (q_coder < 0) bad_args("encode: --quality-coder: pack or rans");
     if (q_mode == 0 && a.flag("--quality-coder")) bad_args("encode: --quality-coder needs --qualities keep or bin8");
+    // ... smoothed inside long matches: --quality-smooth [M] (32 when left out), --quality-smooth-to C
+    for (const char *f : {"--quality-smooth", "--quality-smooth-to"})
+        if (q_mode == 0 && a.flag(f)) bad_args(std::string("encode: ") + f + " needs --qualities keep or bin8");
+    const std::string qs_m = a.get("--quality-smooth", nullptr, "0"), qs_to = a.get("--quality-smooth-to", nullptr, "I");
+    const bool qs_on = a.flag("--quality-smooth");
+    if (qs_on && !(all_digits(qs_m) && qs_m.size() <= 8 && std::atol(qs_m.c_str()) >= 12 && std::atol(qs_m.c_str()) <= 16777215))
+        bad_args("encode: --quality-smooth: M must be 12..16777215");
+    if (qs_to.size() != 1 || qs_to[0] < '$' || qs_to[0] > '~')
+        bad_args("encode: --quality-smooth-to: one printable byte in '$'..'~'");
+    if (q_mode == 2 && a.flag("--quality-smooth-to") && qs_to[0] <= '*')
+        bad_args("encode: --quality-smooth-to: under bin8 the byte must lie above '*', or its level is that of '#'");
     // read names: drop (default), keep, or id, with the front-coded sections in a side file
     const std::string n_name = a.get("--names", nullptr, "drop"), n_path = a.get("--name-file", nullptr, "");
     const int n_mode = n_name == "drop" ? 0 : n_name == "keep" ? 1 : n_name == "id" ? 2 : -1;
@@ -330,6 +353,11 @@ int cmd_encode(const Args &a) {
     if (q_mode > 0)  // the pipeline takes the coder from its contexts
         for (ntc_ctx *c : ctxs)
             if (ntc_ctx_set_option(c, "quality_coder", q_coder)) die("encode: --quality-coder: the option was refused");
+    if (q_mode > 0)  // ... and the smoothing
+        for (ntc_ctx *c : ctxs)
+            if (ntc_ctx_set_option(c, "quality_smooth", qs_on ? std::atol(qs_m.c_str()) : 0) ||
+                ntc_ctx_set_option(c, "quality_smooth_to", qs_to[0]))
+                die("encode: --quality-smooth: the option was refused");
     const ntc_file_opts fo{policy, nx_fd, q_mode, q_fd, nullptr, nullptr};
     const ntc_file_opts2 fo2{(uint32_t)sizeof(ntc_file_opts2), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd, nullptr};
     const ntc_file_opts3 fo3{(uint32_t)sizeof(ntc_file_opts3), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd,
@@ -349,12 +377,23 @@ int cmd_encode(const Args &a) {
     if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
     if (n_fd >= 0 && ::close(n_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + n_path);
     if (d_fd >= 0 && ::close(d_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + d_path);
-    char qjson[1280] = "";  // the quality and name files' figures, when they were written
+    char qjson[1536] = "";  // the quality and name files' figures, when they were written
     if (q_mode > 0)
         std::snprintf(qjson, 320, "\"qualities\": \"%s\", \"quality_coder\": \"%s\", \"q_sections\": %llu, "
                                   "\"q_quals\": %llu, \"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
                       q_name.c_str(), qc_name.c_str(), (unsigned long long)qs.sections, (unsigned long long)qs.quals,
                       (unsigned long long)qs.packed_bytes, (unsigned long long)qs.deflated_bytes);
+    if (qs_on) {
+        unsigned long long smoothed = 0;
+        for (ntc_ctx *c : ctxs) {
+            int64_t v = 0;
+            if (ntc_ctx_get_option(c, "quality_smoothed_total", &v) == NTC_OK) smoothed += (unsigned long long)v;
+        }
+        const std::string to_json = qs_to == "\\" ? "\\\\" : qs_to;  // (the one byte of the range that JSON escapes)
+        std::snprintf(qjson + std::strlen(qjson), 160, "\"quality_smooth\": %ld, \"quality_smooth_to\": \"%s\", "
+                                                       "\"q_smoothed\": %llu, ",
+                      std::atol(qs_m.c_str()), to_json.c_str(), smoothed);
+    }
     if (n_mode > 0)
         std::snprintf(qjson + std::strlen(qjson), 320, "\"names\": \"%s\", \"n_sections\": %llu, \"n_names\": %llu, "
                                                        "\"n_name_bytes\": %llu, \"n_payload_bytes\": %llu, "
@@ -403,14 +442,6 @@ int cmd_encode(const Args &a) {
 bool host_unpack_on() {
     const char *h = std::getenv("NTC_HOST_UNPACK");
     return h && std::atoi(h) > 0;
-}
-
-// all of s is decimal digits (at least one, at most 18: no overflow)
-bool all_digits(const std::string &s) {
-    if (s.empty() || s.size() > 18) return false;
-    for (const char c : s)
-        if (c < '0' || c > '9') return false;
-    return true;
 }
 
 // --reads A-B, 1-based and inclusive as decode prints seq.N; also A, A- and -B.  *b = 0: to the
@@ -713,6 +744,7 @@ void usage(FILE *f) {
                  "MI355X.\n\nusage: ntcomp build -o PREFIX [-k K] [-m MEM_GB] [--temp-dir DIR] FILES...\n"
                  "       ntcomp encode -i PREFIX [--non-acgt error|mask|keep] [--exceptions PATH]\n"
                  "                     [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]\n"
+                 "                     [--quality-smooth [M]] [--quality-smooth-to C]\n"
                  "                     [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]\n"
                  "                     FILE > encoded.dat\n"
                  "                     [--mate-file R2 | --interleaved] [--mate-check ids|off]\n"
@@ -734,6 +766,11 @@ void usage(FILE *f) {
                  "                     whose qualities are printed: the output is then FASTQ\n"
                  "  --quality-coder CODER  encode --qualities keep|bin8: pack (default; packed codes, deflated on the\n"
                  "                     host) or rans (order-1 rANS coded on the GPU, no host deflate)\n"
+                 "  --quality-smooth [M]  encode --qualities keep|bin8: smooth the scores inside long matches to the\n"
+                 "                     index (lossy): a score above '#' in a long record of at least M bases (12..16777215,\n"
+                 "                     32 when M is left out) becomes the --quality-smooth-to byte\n"
+                 "  --quality-smooth-to C  the byte --quality-smooth writes: one of '$'..'~' (default I; under bin8\n"
+                 "                     above '*')\n"
                  "  --names MODE       encode: FASTQ read names: drop (default), keep (lossless: the header line\n"
                  "                     after '@'), or id (the name up to its first space or tab, lossy); keep and id\n"
                  "                     write them, front-coded on the GPU, to the --name-file\n"

@@ -6,6 +6,9 @@
 //               (LDS first, then one atomicOr per word and workgroup)
 //   k_q_alpha   per block: alphabet, width, counts, payload word offset; totals and the
 //               status to the host mailbox (no sync of its own)
+//   k_q_smooth  option "quality_smooth" only, between k_q_gather and k_q_alpha once the encode
+//               has its records: one wave per read at a time, the rule of qsmooth_core.h in place, the
+//               presence maps rebuilt from the smoothed bytes, the bytes replaced counted
 //   k_q_pack    one wave per span of kQSpan qualities: 8 bytes per lane and load (512
 //               contiguous bytes per wave), ranks from the presence words, the lanes of
 //               one output word combined by shuffles, contiguous 64-bit stores
@@ -17,6 +20,7 @@
 
 #include "kernels.h"
 #include "qrans_core.h"
+#include "qsmooth_core.h"
 #include "quality_core.h"
 #include "window_core.h"
 
@@ -142,6 +146,91 @@ __global__ __launch_bounds__(256) void k_q_pack(QEncArgs a) {
     }
 }
 
+// Smoothing (qsmooth_core.h): a workgroup takes kQsReads consecutive reads of one block, a wave
+// one read at a time.  The read's records come kQsChunk at a time, a record per lane; a wave
+// scan of their lengths gives the chunk's entries, which the wave keeps in its own row of
+// LDS.  The lanes then sweep the chunk's qualities an aligned 8-byte word each: the word's
+// trusted mask from the entries, the rule, the presence bits of what is left.  A word that
+// lies wholly inside the chunk is stored whole; a word at either edge is shared with the
+// neighbouring read or chunk, whose wave owns the other bytes, and has its replaced bytes
+// stored one by one.  No byte is written by two waves, and none is read after another wave
+// may have written it, so the pass needs no ordering between waves.  Presence bits and the
+// count gather in registers, then in LDS, and reach memory once per workgroup: a million
+// atomics on one word take 21 ms.
+constexpr uint32_t kQsReads = 128;
+
+__global__ __launch_bounds__(256) void k_q_smooth(QSmoothArgs a) {
+    __shared__ uint32_t ents[4][kQsChunk];
+    __shared__ uint32_t pres[4];
+    __shared__ unsigned long long total;
+    if (*a.q.status != ~0ull) return;  // a failed read: the call fails, no section is returned
+    if (threadIdx.x < 4) pres[threadIdx.x] = 0;
+    if (threadIdx.x == 4) total = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t *ent = ents[threadIdx.x >> 6];
+    const uint32_t floor = qs_floor(a.q.mode), target = qs_target(a.q.mode, a.to);
+    const uint32_t cpb = (a.q.block_reads + kQsReads - 1) / kQsReads;
+    const uint64_t b = blockIdx.x / cpb, c0 = blockIdx.x % cpb;
+    const uint64_t r0 = b * a.q.block_reads + c0 * kQsReads;
+    const uint64_t r1 = umin(umin(r0 + kQsReads, (b + 1) * a.q.block_reads), a.q.n_reads);
+    uint64_t p0 = 0, p1 = 0;
+    uint32_t replaced = 0;
+    for (uint64_t r = r0 + (threadIdx.x >> 6); r < r1; r += 4) {
+        const uint64_t o = a.q.offs[r], j0 = a.roffs[r], m = a.roffs[r + 1] - j0;
+        uint64_t hi = a.q.offs[r + 1] - o;  // the chunk's records end here
+        for (uint64_t c = 0; c < m; c += kQsChunk) {
+            const uint32_t cnt = (uint32_t)umin(kQsChunk, m - c);
+            const uint64_t rec = lane < cnt ? a.recs[j0 + c + lane] : 0;
+            uint32_t inc = lane < cnt ? qs_rec_len(rec) : 0;
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                const uint32_t t = __shfl_up(inc, d, 64);
+                if (lane >= d) inc += t;
+            }
+            const uint32_t span = __shfl(inc, 63, 64);
+            if (span > hi) break;  // (records that outrun the read: the encode did not write them)
+            if (span == 0) continue;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the last chunk's reads of ent are done
+            __builtin_amdgcn_wave_barrier();
+            if (lane < cnt) ent[lane] = qs_entry(span, inc, rec, a.m);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const uint64_t lo = o + (hi - span), end = o + hi;  // the chunk's bytes of quals
+            for (uint64_t at = (lo & ~7ull) + 8 * lane; at < end; at += 512) {
+                uint64_t live, changed;
+                const uint64_t mask = qs_word_mask(ent, cnt, span, (int64_t)at - (int64_t)lo, &live);
+                uint64_t *word = (uint64_t *)(a.q.quals + at);
+                const uint64_t v = qs_apply(*word, mask, floor, target, &changed);
+                qs_presence(v, live, &p0, &p1);
+                if (!changed) continue;
+                replaced += q_popc(changed) >> 3;
+                if (live == ~0ull) {
+                    *word = v;
+                } else {
+                    for (uint32_t j = 0; j < 8; j++)
+                        if ((changed >> (8 * j)) & 1) a.q.quals[at + j] = (uint8_t)target;
+                }
+            }
+            hi -= span;
+        }
+    }
+    for (int d = 1; d < 64; d <<= 1) {
+        p0 |= shfl_xor64(p0, d);
+        p1 |= shfl_xor64(p1, d);
+        replaced += __shfl_xor(replaced, d);
+    }
+    if (lane == 0) {
+        const uint32_t w[4] = {(uint32_t)p0, (uint32_t)(p0 >> 32), (uint32_t)p1, (uint32_t)(p1 >> 32)};
+        for (uint32_t i = 0; i < 4; i++)
+            if (w[i]) atomicOr(&pres[i], w[i]);
+        if (replaced) atomicAdd(&total, (unsigned long long)replaced);
+    }
+    __syncthreads();
+    // (a stale read of the block's map only costs an atomic that adds nothing)
+    if (threadIdx.x < 4 && (pres[threadIdx.x] & ~a.q.pres[4 * b + threadIdx.x])) atomicOr(&a.q.pres[4 * b + threadIdx.x], pres[threadIdx.x]);
+    if (threadIdx.x == 4 && total) atomicAdd(a.count, total);
+}
+
 // Workgroup t of block b: qualities [t kQTile, ...) of the block, a byte per thread and store
 // (64 contiguous bytes per wave).  Nothing is written for a block whose count differs from
 // the bases the walk produced for its reads.
@@ -236,6 +325,33 @@ void launch_quality_gather(const QEncArgs &a, hipStream_t s) {
 void launch_quality_pack(const QEncArgs &a, uint64_t total, hipStream_t s) {
     if (a.n_blocks == 0) return;
     launch_quality_gather(a, s);
+    const uint64_t spans = total / kQSpan + a.n_blocks;  // at most: a block's last span may be short
+    hipLaunchKernelGGL(k_q_pack, dim3((uint32_t)((spans + 3) / 4)), dim3(256), 0, s, a);
+}
+
+void launch_quality_lines(const QEncArgs &a, hipStream_t s) {
+    if (a.n_blocks == 0) return;
+    (void)hipMemsetAsync(a.pres, 0, a.n_blocks * 16, s);  // a failure shows in the caller's hipGetLastError
+    (void)hipMemsetAsync(a.status, 0xFF, 8, s);
+    const uint64_t cpb = (a.block_reads + kQChunk - 1) / kQChunk;
+    hipLaunchKernelGGL(k_q_gather, dim3((uint32_t)(a.n_blocks * cpb)), dim3(256), 0, s, a);
+}
+
+void launch_quality_smooth(const QSmoothArgs &a, hipStream_t s) {
+    if (a.q.n_blocks == 0) return;
+    (void)hipMemsetAsync(a.q.pres, 0, a.q.n_blocks * 16, s);
+    (void)hipMemsetAsync(a.count, 0, 8, s);
+    const uint64_t cpb = (a.q.block_reads + kQsReads - 1) / kQsReads;
+    hipLaunchKernelGGL(k_q_smooth, dim3((uint32_t)(a.q.n_blocks * cpb)), dim3(256), 0, s, a);
+}
+
+void launch_quality_alpha(const QEncArgs &a, hipStream_t s) {
+    if (a.n_blocks == 0) return;
+    hipLaunchKernelGGL(k_q_alpha, dim3(1), dim3(256), 0, s, a);
+}
+
+void launch_quality_spans(const QEncArgs &a, uint64_t total, hipStream_t s) {
+    if (a.n_blocks == 0) return;
     const uint64_t spans = total / kQSpan + a.n_blocks;  // at most: a block's last span may be short
     hipLaunchKernelGGL(k_q_pack, dim3((uint32_t)((spans + 3) / 4)), dim3(256), 0, s, a);
 }
