@@ -66,6 +66,13 @@ typedef struct ntc_block_meta {
                                     blocks, as zlib's own stored-block fallback would write
                                     it; half the CPU of NTC_DEFLATE_LIBDEFLATE, same streams
                                     after inflate, within 0.1 % of its size              */
+#define NTC_DEFLATE_GPU 3        /* the coder of the device (deflate.hip):
+                                    32 KiB chunks coded on their own, each stored, Huffman
+                                    over literals, or Huffman over literals and greedy
+                                    in-chunk matches, whichever is exactly smallest.  Here
+                                    (ntc_deflate_block / _stream) its host restatement runs:
+                                    the device's bytes, no libdeflate, no GPU.  Block streams
+                                    only: the side-section deflaters refuse it.           */
 
 void ntc_file_header(uint8_t out[32]);
 /* NTC_ERR_EMPTY_READ when the block has no long or no short records (see above). */
@@ -76,8 +83,9 @@ int ntc_write_block(const uint64_t *recs, uint64_t n_recs, uint64_t num_records,
 int ntc_pack_block(const uint64_t *recs, uint64_t n_recs, uint64_t num_records, ntc_block_meta *meta,
                    uint8_t **payload, uint64_t *payload_len);
 /* Header + gzip member per stream, the bytes write_block_to writes.  payload is the base
- * the meta offsets are relative to.  engine: NTC_DEFLATE_ZLIB, _LIBDEFLATE or _ADAPTIVE
- * (NTC_ERR_UNSUPPORTED if libdeflate.so.0 is missing).  Returns meta->status when the
+ * the meta offsets are relative to.  engine: NTC_DEFLATE_ZLIB, _LIBDEFLATE, _ADAPTIVE
+ * (NTC_ERR_UNSUPPORTED if libdeflate.so.0 is missing) or _GPU; any other value is
+ * NTC_ERR_INVALID_ARG.  Returns meta->status when the
  * block is dropped (nothing written).                                                  */
 int ntc_deflate_block(const ntc_block_meta *meta, const uint8_t *payload, int engine, uint8_t **out,
                       uint64_t *out_len);
@@ -120,6 +128,28 @@ int ntc_pack_blocks_device(ntc_ctx *ctx, const uint64_t *d_recs, const uint64_t 
 int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_offsets, uint64_t n_reads,
                           uint32_t block_reads, ntc_block_meta *meta, uint8_t **payload, uint64_t *payload_bytes,
                           int64_t *bad_read);
+
+/* ---- GPU deflate (NTC_DEFLATE_GPU on the device) ---------------------------------------- */
+/* The gzip members of n_blocks packed blocks, made where the packer left them: d_payload
+ * (device) and the HOST metas as ntc_pack_blocks_device gives them.  Stream s of block b
+ * becomes one member in d_out (device, out_capacity bytes), the members back to back;
+ * member_off_len (host, 4 pairs per block) says where each starts in d_out and how many bytes
+ * it has.  The bytes are those of ntc_deflate_stream with NTC_DEFLATE_GPU, less its 32-byte
+ * stream header.  A block whose status is not 0 yields nothing (pairs of zeros); an empty
+ * stream yields a member that inflates to nothing.  *out_bytes = bytes used.  A capacity below
+ * the sum over the streams of 18 + n + 5 ceil(n / 32768) + 5 (n = 8 encoded_size) is
+ * NTC_ERR_CAPACITY with *out_bytes = that sum; nothing was launched.  Synchronous.           */
+int ntc_deflate_blocks_device(ntc_ctx *ctx, const uint8_t *d_payload, const ntc_block_meta *metas, uint64_t n_blocks,
+                              uint8_t *d_out, uint64_t out_capacity, uint64_t *member_off_len, uint64_t *out_bytes);
+/* ntc_ctx_set_option(ctx, "gpu_deflate", 1) (default 0: nothing is launched, no byte or copy
+ * changes) makes ntc_encode_pack_batch, ntc_encode_pack_fastq and ntc_encode_pack_fastq_paired
+ * run that pass behind the packer: *payload then holds the members, not the raw streams, which
+ * never leave the device, and the meta offsets no longer apply.  ntc_encode_members fetches
+ * where they lie, 4 pairs (offset in *payload, bytes) per block, zeros for a dropped block:
+ * what the last such call on this context left, to be fetched before the next one, like
+ * ntc_encode_digests.  *n_blocks = the call's blocks (0 when the option was off);
+ * NTC_ERR_CAPACITY when cap_blocks is smaller.                                             */
+int ntc_encode_members(ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_blocks, uint64_t *n_blocks);
 
 /* ---- GPU unpacker (the inverse of the packer) ------------------------------------------ */
 /* decode_block (src/lib.rs:320-368) split at inflate.  ntc_read_block_streams (host): one

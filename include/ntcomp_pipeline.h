@@ -32,7 +32,12 @@ typedef struct ntc_pipeline_opts {
     int32_t threads;          /* host pool (parse, deflate); <= 0: ntc_host_threads()        */
     int32_t blocks_per_batch; /* 65,536-read blocks per GPU call; <= 0: 4 (encode), 2 (decode) */
     uint64_t batch_bases;     /* encode: bases per pinned batch buffer; 0: 64 Mi (grows for long reads) */
-    int32_t deflate_engine;   /* NTC_DEFLATE_ZLIB (0), _LIBDEFLATE (1) or _ADAPTIVE (2)        */
+    int32_t deflate_engine;   /* NTC_DEFLATE_ZLIB (0), _LIBDEFLATE (1), _ADAPTIVE (2) or _GPU
+                                 (3: the contexts deflate the block streams behind their packer,
+                                 option "gpu_deflate"; the host writes stream headers and copies
+                                 members; side sections go to the pool under _ADAPTIVE, or _ZLIB
+                                 without libdeflate; NTC_ERR_UNSUPPORTED in a build without the
+                                 GPU hooks).  Encode only: decode ignores the field            */
     int32_t host_parse;       /* encode, plain FASTQ: 0 = the text goes to the GPU, which parses
                                  it (ntc_encode_pack_fastq); 1 = parsed by the host pool      */
 } ntc_pipeline_opts;

@@ -41,7 +41,8 @@ EXPORTED = [
     "ntc_memcpy_d2h", "ntc_debug_matching_statistics", "ntc_build_index", "ntc_index_free",
     "ntc_index_view_of", "ntc_index_save", "ntc_index_save_as", "ntc_index_load", "ntc_synth_genome", "ntc_synth_strains", "ntc_synth_reads", "ntc_minimizer_keys",
     "ntc_file_header", "ntc_write_block", "ntc_read_block", "ntc_buffer_free", "ntc_pack_block",
-    "ntc_deflate_block", "ntc_deflate_stream", "ntc_pack_blocks_device", "ntc_encode_pack_batch", "ntc_fastq_parse",
+    "ntc_deflate_block", "ntc_deflate_stream", "ntc_pack_blocks_device", "ntc_deflate_blocks_device",
+    "ntc_encode_members", "ntc_encode_pack_batch", "ntc_fastq_parse",
     "ntc_encode_pack_fastq", "ntc_read_block_into", "ntc_read_block_streams", "ntc_unpack_streams",
     "ntc_unpacked_records", "ntc_decode_fasta_unpacked",
     "ntc_fastx_open", "ntc_fastx_next_batch", "ntc_fastx_close", "ntc_fasta_format", "ntc_fastx_next_batch_into",
@@ -188,7 +189,7 @@ class DigestMeta(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
-DEFLATE_ENGINES = {"zlib": 0, "libdeflate": 1, "adaptive": 2}  # NTC_DEFLATE_* (include/ntcomp_codec.h)
+DEFLATE_ENGINES = {"zlib": 0, "libdeflate": 1, "adaptive": 2, "gpu": 3}  # NTC_DEFLATE_* (include/ntcomp_codec.h)
 
 
 class PipelineOpts(ctypes.Structure):
@@ -400,6 +401,8 @@ def lib():
         "ntc_deflate_block": (I, [ctypes.POINTER(BlockMeta), P, I, ctypes.POINTER(P), ctypes.POINTER(u64)]),
         "ntc_deflate_stream": (I, [ctypes.POINTER(BlockMeta), I, P, I, ctypes.POINTER(P), ctypes.POINTER(u64)]),
         "ntc_pack_blocks_device": (I, [P, P, P, u64, u32, P, u64, P, ctypes.POINTER(u64)]),
+        "ntc_deflate_blocks_device": (I, [P, P, P, u64, P, u64, P, ctypes.POINTER(u64)]),
+        "ntc_encode_members": (I, [P, P, u64, ctypes.POINTER(u64)]),
         "ntc_encode_pack_batch": (I, [P, P, P, u64, u32, P, ctypes.POINTER(P), ctypes.POINTER(u64),
                                       ctypes.POINTER(i64)]),
         "ntc_fastq_parse": (I, [P, P, u64, u64, P, u64, P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int64)]),
@@ -946,6 +949,33 @@ class GpuContext:
                                                   block_reads, ctypes.c_void_p(d_payload), cap, metas,
                                                   ctypes.byref(used)), "ntc_pack_blocks_device")
         return list(metas)[:nb], int(used.value)
+
+    def deflate_device(self, d_payload, metas, d_out, cap):
+        """The gzip members of packed blocks, made on the GPU (ntc_deflate_blocks_device): d_payload
+        and metas as pack_device left them -> (uint64 array [blocks, 4, 2] of each member's offset in
+        d_out and its bytes, bytes used).  NtcError(NTC_ERR_CAPACITY) carries .needed."""
+        arr = (BlockMeta * max(len(metas), 1))(*metas)
+        off_len = np.zeros((len(metas), 4, 2), dtype=np.uint64)
+        used = ctypes.c_uint64()
+        rc = self.L.ntc_deflate_blocks_device(self.h, ctypes.c_void_p(d_payload), arr, len(metas), ctypes.c_void_p(d_out),
+                                              cap, _p(off_len) if len(metas) else None, ctypes.byref(used))
+        if rc:
+            e = NtcError(rc, self.L.ntc_last_error(self.h).decode(errors="replace"))
+            e.needed = int(used.value)
+            raise e
+        return off_len, int(used.value)
+
+    def encode_members(self):
+        """Where the members lie in the payload of the last encode_pack* call under option
+        "gpu_deflate" (ntc_encode_members) -> uint64 array [blocks, 4, 2] of (offset, bytes)."""
+        nb = ctypes.c_uint64()
+        rc = self.L.ntc_encode_members(self.h, None, 0, ctypes.byref(nb))
+        if rc not in (0, 5):
+            self._check(rc, "ntc_encode_members")
+        off_len = np.zeros((nb.value, 4, 2), dtype=np.uint64)
+        if nb.value:
+            self._check(self.L.ntc_encode_members(self.h, _p(off_len), nb.value, ctypes.byref(nb)), "ntc_encode_members")
+        return off_len
 
     def encode_pack(self, bases, offsets, block_reads=65536, non_acgt=None, digests=None):
         """Reads -> packed blocks (ntc_encode_pack_batch): the records stay in HBM and the

@@ -335,7 +335,8 @@ def _component_names(mask):
 def cmd_encode(args):
     """main.rs:141-181 through the native pipeline (ntc_encode_file): plain FASTQ parsed
     on the GPU (--host-parse: on the host pool, as every other input is), GPU encode +
-    block packer per context, deflate on the host pool, blocks written in file order."""
+    block packer per context, deflate on the host pool (--deflate gpu: on the GPU, behind the
+    packer), blocks written in file order."""
     _check_nx_args(args)
     _check_q_args(args)
     _check_n_args(args)
@@ -556,11 +557,13 @@ def main(argv=None):
     e.add_argument("--contexts-per-gpu", type=int, default=ENCODE_CONTEXTS_PER_GPU,
                    help="contexts per device sharing one index copy; calls alternate over them")
     e.add_argument("--blocks-per-batch", type=int, default=4, help="65,536-read blocks per GPU call")
-    e.add_argument("--deflate", choices=["auto", "zlib", "libdeflate", "adaptive"], default="auto",
+    e.add_argument("--deflate", choices=["auto", "zlib", "libdeflate", "adaptive", "gpu"], default="auto",
                    help="gzip engine for the block streams, level 6 (the reference's Compression::default()): "
                         "adaptive (auto, when libdeflate.so.0 loads: libdeflate, with streams of >= 7.9 bits of "
                         "entropy per byte stored), libdeflate (~3x faster than zlib) or zlib.  The deflate bytes "
-                        "differ, the inflated streams do not; no engine reproduces the reference's zlib-rs bytes")
+                        "differ, the inflated streams do not; no engine reproduces the reference's zlib-rs bytes.  gpu: the "
+                        "streams are deflated on the GPU behind the packer (32 KiB chunks, greedy in-chunk matches; about "
+                        "2 %% larger) and the host only copies the members; side files are deflated as under auto")
     e.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
     e.add_argument("--host-parse", action="store_true",
                    help="parse a plain FASTQ on the host pool instead of the GPU")

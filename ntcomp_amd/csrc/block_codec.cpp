@@ -53,6 +53,7 @@
 #include "quality_core.h"
 #include "names_core.h"
 #include "digest_core.h"
+#include "deflate_core.h"
 
 namespace {
 
@@ -280,6 +281,11 @@ constexpr double kStoreEntropy = 7.9;
 bool gzip_append(const uint8_t *data, size_t n, int engine, std::vector<uint8_t> &out) {
     static const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
     const size_t start = out.size();
+    if (engine == NTC_DEFLATE_GPU) {  // the device coder's host restatement (deflate_core.h): the same bytes
+        out.resize(start + ntc::df_member_bound(n));
+        out.resize(start + ntc::df_member_host(data, n, out.data() + start));
+        return true;
+    }
     out.insert(out.end(), hdr, hdr + 10);
     bool ok = true;
     if (engine == NTC_DEFLATE_ADAPTIVE && n >= 4096 && entropy0(data, std::min(n, kEntropySample)) >= kStoreEntropy)
@@ -565,29 +571,44 @@ int deflate_stream_into(const ntc_block_meta *meta, int s, const uint8_t *payloa
     const size_t hpos = buf.size();
     buf.resize(hpos + 32);
     if (!gzip_append(payload + m.offset, m.encoded_size * 8, engine, buf)) return NTC_ERR_FORMAT;
+    ntc::stream_header(buf.data() + hpos, *meta, s, buf.size() - hpos - 32);
+    return NTC_OK;
+}
+
+}  // namespace
+
+void ntc::stream_header(uint8_t out[32], const ntc_block_meta &meta, int s, uint64_t member_bytes) {
+    const ntc_stream_meta &m = meta.stream[s];
     BlockHeader h{};
-    h.block_size = (uint32_t)(buf.size() - hpos - 32);
-    h.num_records = (uint32_t)meta->num_records;
+    h.block_size = (uint32_t)member_bytes;
+    h.num_records = (uint32_t)meta.num_records;
     h.num_u64 = (uint32_t)m.num_u64;
     h.encoded_size = (uint32_t)m.encoded_size;
     h.rice_param = m.param;
     h.bitpacker_exponent = 8;
     std::vector<uint8_t> hb;
     write_header(hb, h);
-    std::memcpy(buf.data() + hpos, hb.data(), 32);
-    return NTC_OK;
+    std::memcpy(out, hb.data(), 32);
 }
+bool ntc::libdeflate_loaded() { return libdeflate().ok; }
 
+namespace {
 int deflate_checks(const ntc_block_meta *meta, const uint8_t *payload, int engine, uint8_t **out, uint64_t *out_len) {
     if (!meta || !out || !out_len) return NTC_ERR_INVALID_ARG;
     *out = nullptr;
     *out_len = 0;
     if (meta->status != NTC_OK) return meta->status;
     if (!payload) return NTC_ERR_INVALID_ARG;
-    if (engine != NTC_DEFLATE_ZLIB && engine != NTC_DEFLATE_LIBDEFLATE && engine != NTC_DEFLATE_ADAPTIVE)
+    if (engine != NTC_DEFLATE_ZLIB && engine != NTC_DEFLATE_LIBDEFLATE && engine != NTC_DEFLATE_ADAPTIVE &&
+        engine != NTC_DEFLATE_GPU)
         return NTC_ERR_INVALID_ARG;
-    if (engine != NTC_DEFLATE_ZLIB && !libdeflate().ok) return NTC_ERR_UNSUPPORTED;
+    if (engine != NTC_DEFLATE_ZLIB && engine != NTC_DEFLATE_GPU && !libdeflate().ok) return NTC_ERR_UNSUPPORTED;
     return NTC_OK;
+}
+
+// the side sections take the host engines only (NTC_DEFLATE_GPU codes block streams)
+bool side_engine_ok(int engine) {
+    return engine == NTC_DEFLATE_ZLIB || engine == NTC_DEFLATE_LIBDEFLATE || engine == NTC_DEFLATE_ADAPTIVE;
 }
 
 int hand_out(const std::vector<uint8_t> &buf, uint8_t **out, uint64_t *out_len) {
@@ -954,6 +975,7 @@ int ntc_q_deflate_section(const ntc_qual_meta *meta, const uint8_t *words, int e
     if (!meta || !out || !out_len || (meta->payload_bytes && !words)) return NTC_ERR_INVALID_ARG;
     *out = nullptr;
     *out_len = 0;
+    if (!side_engine_ok(engine)) return NTC_ERR_INVALID_ARG;
     if (meta->reserved[0] == 1) {  // coder 1: the body as it came off the device, no gzip member
         if (!ntc::q_meta_ok(meta->n_quals, meta->width, meta->n_syms, meta->alphabet) || meta->payload_bytes >> 32 ||
             !ntc::qr_body_ok(meta->n_quals, meta->n_syms, words, meta->payload_bytes))
@@ -1118,6 +1140,7 @@ int ntc_n_deflate_section(const ntc_name_meta *meta, const uint8_t *payload, int
     if (!meta || !out || !out_len || (meta->payload_bytes && !payload)) return NTC_ERR_INVALID_ARG;
     *out = nullptr;
     *out_len = 0;
+    if (!side_engine_ok(engine)) return NTC_ERR_INVALID_ARG;
     if (!n_meta_ok(*meta) || !n_section_ok(*meta, payload)) return NTC_ERR_INVALID_ARG;
     std::vector<uint8_t> buf(32);
     if (!gzip_append(payload, meta->payload_bytes, engine, buf)) return NTC_ERR_FORMAT;

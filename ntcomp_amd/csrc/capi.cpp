@@ -25,6 +25,7 @@
 #include "qsmooth_core.h"
 #include "names_core.h"
 #include "digest_core.h"
+#include "deflate_core.h"
 #include "pair_core.h"
 #include "window_core.h"
 #include "ntc_internal.h"
@@ -55,7 +56,8 @@ enum WsSlot {
     WS_QR_COUNTS, WS_QR_CUM, WS_QR_SCRATCH, WS_QR_SCAN,
     WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES,
     WS_DG_TABLE, WS_DGD_IN,
-    WS_PAIR_IN, WS_PAIR_TAB, WS_PAIR_ST, WS_PAIR_SCAN, WS_PAIR_OUT, WS_COUNT
+    WS_PAIR_IN, WS_PAIR_TAB, WS_PAIR_ST, WS_PAIR_SCAN, WS_PAIR_OUT,
+    WS_DF_DESC, WS_DF_TOKENS, WS_DF_STAGE, WS_DF_RES, WS_DF_OUT, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -154,6 +156,17 @@ struct PairState {
     uint64_t first = 0;
 };
 
+// deflate on the device (deflate.hip): the option "gpu_deflate"; the chunk and stream lists of the
+// call in flight (the source of its upload) and the members the last encode_pack call left
+struct DeflateState {
+    int opt = 0;
+    std::vector<DfChunkDesc> chunks;
+    std::vector<DfStreamDesc> streams;
+    std::vector<uint64_t> dev_off_len;  // as the device wrote them, the total behind them
+    std::vector<uint64_t> members;      // 4 pairs (offset, bytes) per block of the last call
+    void begin() { members.clear(); }   // an encode call starts: the last call's members are gone
+};
+
 // the text window of the next ntc_decode_fasta / _unpacked (ntc_decode_set_window): pending
 // like the side data above, gone after that call whether it succeeds or fails
 struct WindowState {
@@ -235,6 +248,7 @@ struct ntc_ctx {
     DigestState dig;
     PairState pair;
     WindowState win;
+    DeflateState df;
     int discard_text = 0;  // option "discard_text": a FASTA decode call formats its text and leaves it on the device
     FastqArgs fq_last{};              // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
@@ -299,6 +313,7 @@ inline void side_begin(ntc_ctx *ctx) {
     ctx->qual.begin();
     ctx->names.begin();
     ctx->dig.begin();
+    ctx->df.begin();
 }
 
 const char *status_name(int code) {
@@ -1983,6 +1998,7 @@ const Option kOptions[] = {
     {"discard_text", 0, 1, kInRange, "discard_text must be 0 or 1", OPT_VALUE(discard_text)},
     {"paired", 0, 2, kInRange, "paired must be 0 (off), 1 (ids) or 2 (no check)", OPT_VALUE(pair.mode)},
     {"digests", 0, 1, kInRange, "digests must be 0 or 1", OPT_VALUE(dig.opt)},
+    {"gpu_deflate", 0, 1, kInRange, "gpu_deflate must be 0 or 1", OPT_VALUE(df.opt)},
     {"non_acgt", 0, 2, kInRange, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)", OPT_VALUE(nx.policy)},
     // what the last upload and the last calls left
     {"subst_hash", 0, 0, kInRange, nullptr, nullptr, get_subst_hash},
@@ -2371,6 +2387,103 @@ int ntc_pack_blocks_device(ntc_ctx *ctx, const uint64_t *d_recs, const uint64_t 
 }  // extern "C"
 
 namespace {
+// The members of n_blocks packed blocks (deflate.hip): d_payload as the packer left it, metas on
+// the host.  member_off_len: 4 pairs per block of where a stream's member starts in d_out and
+// its bytes (zeros for a block whose status is not 0).  *out_bytes: the bytes used, or with
+// NTC_ERR_CAPACITY the bytes needed: the sum of the members' bounds, which needs no device pass.
+int deflate_blocks_impl(ntc_ctx *ctx, const uint8_t *d_payload, const ntc_block_meta *metas, uint64_t n_blocks,
+                        uint8_t *d_out, uint64_t out_capacity, uint64_t *member_off_len, uint64_t *out_bytes) {
+    DeflateState &D = ctx->df;
+    D.chunks.clear();
+    D.streams.clear();
+    uint64_t need = 0;
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (metas[b].status != NTC_OK) continue;
+        for (int s = 0; s < 4; s++) {
+            const ntc_stream_meta &m = metas[b].stream[s];
+            if (m.encoded_size >> 28) return set_err(ctx, NTC_ERR_INVALID_ARG, "a stream of 2 GiB or more");
+            const uint64_t n = m.encoded_size * 8, nc = df_chunks(n);
+            if ((D.chunks.size() + nc) >> 31) return set_err(ctx, NTC_ERR_CAPACITY, "too many chunks in one call: split the batch");
+            D.streams.push_back(DfStreamDesc{n, (uint32_t)D.chunks.size(), (uint32_t)nc});
+            for (uint64_t c = 0; c < nc; c++) {
+                const uint64_t off = c * kDfChunk;
+                D.chunks.push_back(DfChunkDesc{m.offset + off, (uint32_t)std::min<uint64_t>(n - off, kDfChunk), c + 1 == nc});
+            }
+            need += df_member_bound(n);
+        }
+    }
+    *out_bytes = need;
+    if (need > out_capacity)
+        return set_err(ctx, NTC_ERR_CAPACITY, "deflate output needs " + std::to_string(need) + " bytes");
+    for (uint64_t i = 0; i < n_blocks * 8; i++) member_off_len[i] = 0;
+    *out_bytes = 0;
+    const uint64_t N = D.chunks.size(), S = D.streams.size();
+    if (!S) return NTC_OK;
+    void *d_desc, *d_tokens, *d_stage, *d_res;
+    int rc;
+    const uint64_t res_bytes = N * sizeof(DfResult) + N * 8 + (2 * S + 1) * 8 + S * 4;
+    if ((rc = ensure(ctx, WS_DF_DESC, N * sizeof(DfChunkDesc) + S * sizeof(DfStreamDesc), &d_desc))) return rc;
+    if ((rc = ensure(ctx, WS_DF_TOKENS, N * kDfChunk * 4, &d_tokens))) return rc;
+    if ((rc = ensure(ctx, WS_DF_STAGE, N * kDfSlot, &d_stage))) return rc;
+    if ((rc = ensure(ctx, WS_DF_RES, res_bytes, &d_res))) return rc;
+    DfArgs a{};
+    a.payload = d_payload;
+    a.chunks = (const DfChunkDesc *)d_desc;
+    a.streams = (const DfStreamDesc *)(a.chunks + N);
+    a.n_chunks = (uint32_t)N;
+    a.n_streams = (uint32_t)S;
+    a.tokens = (uint32_t *)d_tokens;
+    a.stage = (uint8_t *)d_stage;
+    a.results = (DfResult *)d_res;
+    a.chunk_off = (uint64_t *)(a.results + N);
+    a.member_off_len = a.chunk_off + N;
+    a.crcs = (uint32_t *)(a.member_off_len + 2 * S + 1);
+    a.out = d_out;
+    HIP_TRY(ctx, hipMemcpyAsync(d_desc, D.chunks.data(), N * sizeof(DfChunkDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync((void *)a.streams, D.streams.data(), S * sizeof(DfStreamDesc), hipMemcpyHostToDevice,
+                                ctx->stream));
+    launch_deflate(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    D.dev_off_len.resize(2 * S + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(D.dev_off_len.data(), a.member_off_len, (2 * S + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t s = 0;
+    for (uint64_t b = 0; b < n_blocks; b++) {
+        if (metas[b].status != NTC_OK) continue;
+        for (int k = 0; k < 8; k++) member_off_len[b * 8 + k] = D.dev_off_len[2 * s + k];
+        s += 4;
+    }
+    *out_bytes = D.dev_off_len[2 * S];
+    return NTC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ntc_deflate_blocks_device(ntc_ctx *ctx, const uint8_t *d_payload, const ntc_block_meta *metas, uint64_t n_blocks,
+                              uint8_t *d_out, uint64_t out_capacity, uint64_t *member_off_len, uint64_t *out_bytes) {
+    if (!ctx || !out_bytes || (n_blocks && (!metas || !member_off_len)))
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *out_bytes = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (uint64_t b = 0; b < n_blocks; b++)
+        if (metas[b].status == NTC_OK && (!d_payload || !d_out))
+            return set_err(ctx, NTC_ERR_INVALID_ARG, "null device buffer");
+    return deflate_blocks_impl(ctx, d_payload, metas, n_blocks, d_out, out_capacity, member_off_len, out_bytes);
+}
+
+int ntc_encode_members(ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_blocks, uint64_t *n_blocks) {
+    if (!ctx || !n_blocks) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_blocks = ctx->df.members.size() / 8;
+    if (*n_blocks > cap_blocks || (*n_blocks && !member_off_len))
+        return set_err(ctx, NTC_ERR_CAPACITY, "member array too small");
+    std::copy(ctx->df.members.begin(), ctx->df.members.end(), member_off_len);
+    return NTC_OK;
+}
+
+}  // extern "C"
+
+namespace {
 // encode + GPU block packer over reads already in HBM (d_offs: n_reads + 1 offsets, room for
 // n_reads + 1 more behind them, where the record offsets go); the tail of
 // ntc_encode_pack_batch and ntc_encode_pack_fastq.  dg: the digest components of the call (0:
@@ -2418,6 +2531,20 @@ int encode_pack_staged(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_o
         cap = used;  // exact requirement from the first pass
     }
     if (rc) return rc;
+    if (ctx->df.opt) {  // option "gpu_deflate": the members in place of the raw streams, which stay in HBM
+        uint64_t bound = 0;
+        for (uint64_t b = 0; b < n_blocks; b++)
+            for (int s = 0; s < 4 && meta[b].status == NTC_OK; s++) bound += df_member_bound(meta[b].stream[s].encoded_size * 8);
+        void *d_members;
+        if ((rc = ensure(ctx, WS_DF_OUT, bound, &d_members))) return rc;
+        ctx->df.members.assign(n_blocks * 8, 0);
+        if ((rc = deflate_blocks_impl(ctx, (const uint8_t *)d_payload, meta, n_blocks, (uint8_t *)d_members,
+                                      ctx->ws[WS_DF_OUT].bytes, ctx->df.members.data(), &used))) {
+            ctx->df.members.clear();
+            return rc;
+        }
+        d_payload = d_members;
+    }
     uint8_t *h = (uint8_t *)std::malloc(used ? used : 1);
     if (!h) return set_err(ctx, NTC_ERR_CAPACITY, "host payload allocation");
     if (used && hipMemcpy(h, d_payload, used, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -2447,6 +2574,7 @@ int ntc_encode_pack_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *re
     if (ctx->qual.mode != 0) return q_unsupported(ctx, "ntc_encode_pack_batch");
     if (ctx->names.mode != 0) return n_unsupported(ctx, "ntc_encode_pack_batch");
     ctx->dig.begin();
+    ctx->df.begin();
     for (uint64_t r = 0; r < n_reads; r++)
         if (read_offsets[r + 1] < read_offsets[r])
             return set_err(ctx, NTC_ERR_INVALID_ARG, "read offsets must be non-decreasing");
@@ -2710,6 +2838,7 @@ int encode_pack_fastq_impl(ntc_ctx *ctx, const uint8_t *fastq, uint64_t fastq_by
         ctx->qual.begin();
         ctx->names.begin();
         ctx->dig.begin();
+        ctx->df.begin();
     }
     if (src && bad_read) *bad_read = qrc ? q_bad : n_bad;
     if (src && !rc) {
@@ -3590,6 +3719,8 @@ struct NxHookFill {
             return ntc_index_info(ctx, n_nodes, k, nullptr);
         };
         ntc::g_d_hooks.set_discard = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "discard_text", on); };
+        ntc::g_z_hooks.set_mode = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "gpu_deflate", on); };
+        ntc::g_z_hooks.encode_members = ntc_encode_members;
     }
 } g_nx_hook_fill;
 }  // namespace

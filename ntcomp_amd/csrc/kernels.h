@@ -425,6 +425,34 @@ struct QRDecArgs {
     unsigned long long *status;
 };
 void launch_quality_rans_decode(const QRDecArgs &a, hipStream_t s);
+// Deflate of the packed streams (deflate.hip, deflate_core.h).  Stream s is chunks first_chunk ..
+// + n_chunks, chunk c the n bytes at payload + src_off (last: its stream's last chunk).  With N
+// chunks and S streams: tokens: N * kDfChunk words, stage: N * kDfSlot bytes, results: N,
+// chunk_off: N words, crcs: S words, member_off_len: 2 S + 1 words (device; pairs of where a
+// member starts in out and its bytes, then the total), out: the sum of df_member_bound(n) bytes.
+struct DfResult;
+struct DfChunkDesc {
+    uint64_t src_off;
+    uint32_t n, last;
+};
+struct DfStreamDesc {
+    uint64_t n;
+    uint32_t first_chunk, n_chunks;
+};
+struct DfArgs {
+    const uint8_t *payload;
+    const DfChunkDesc *chunks;
+    const DfStreamDesc *streams;
+    uint32_t n_chunks, n_streams;
+    uint32_t *tokens;
+    uint8_t *stage;
+    DfResult *results;
+    uint64_t *chunk_off;
+    uint32_t *crcs;
+    uint64_t *member_off_len;
+    uint8_t *out;
+};
+void launch_deflate(const DfArgs &a, hipStream_t s);
 // launch_fasta's FASTQ twin: "@seq.{first_id + r}\n{read r}\n+\n{qualities r}\n"
 void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t n,
                        uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,

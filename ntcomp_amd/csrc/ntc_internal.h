@@ -179,6 +179,16 @@ struct WHooks {
     int (*decode_set_window)(::ntc_ctx *ctx, uint64_t first, uint64_t count);  // ntc_decode_set_window
 };
 extern WHooks g_w_hooks;
+// ... and for NTC_DEFLATE_GPU: with the table null, ntc_encode_file* answers NTC_ERR_UNSUPPORTED to it
+struct ZHooks {
+    int (*set_mode)(::ntc_ctx *ctx, int on);  // ctx option "gpu_deflate"
+    int (*encode_members)(::ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_blocks, uint64_t *n_blocks);
+};
+extern ZHooks g_z_hooks;
+// the 32-byte header in front of stream s's gzip member of member_bytes bytes (block_codec.cpp)
+void stream_header(uint8_t out[32], const ::ntc_block_meta &meta, int s, uint64_t member_bytes);
+// libdeflate.so.0 loads: what `--deflate auto` asks
+bool libdeflate_loaded();
 struct PgzReader;
 PgzReader *pgz_open(const char *path, int threads);
 int pgz_read(PgzReader *r, char *dst, size_t cap, size_t *got);

@@ -7,7 +7,7 @@
 //   ntcomp build -o P [-k 31] [-p 8] [-d] [-t 1] [-m 4] [--temp-dir D] [--verbose]
 //                [-l LIST] [--builder auto|host|gpu] [--device N] [--index-format own|sbwt-rs] FILES...
 //   ntcomp encode -i P [--gpus N | --devices 0,0,..] [--threads T] [--blocks-per-batch B]
-//                 [--deflate auto|zlib|libdeflate|adaptive] [--host-parse] [--stats]
+//                 [--deflate auto|zlib|libdeflate|adaptive|gpu] [--host-parse] [--stats]
 //                 [--non-acgt error|mask|keep] [--exceptions PATH]
 //                 [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]
 //                 [--quality-smooth [M]] [--quality-smooth-to C]
@@ -314,6 +314,11 @@ int cmd_encode(const Args &a) {
     if (check_name != "ids" && check_name != "off") bad_args("encode: --mate-check: ids or off");
     if (pairs && a.flag("--host-parse")) bad_args("encode: pairs are woven and checked on the GPU: not with --host-parse");
     const int pair_mode = !pairs ? 0 : check_name == "ids" ? 1 : 2;
+    // the engine of the block streams, settled before a GPU is opened
+    std::string engine = a.get("--deflate", nullptr, "auto");
+    if (engine != "auto" && engine != "zlib" && engine != "libdeflate" && engine != "adaptive" && engine != "gpu")
+        bad_args("encode: --deflate: auto, zlib, libdeflate, adaptive or gpu");
+    if (engine == "auto") engine = libdeflate_present() ? "adaptive" : "zlib";
     if (prefix.empty()) die("encode: -i/--index is required");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
@@ -322,16 +327,13 @@ int cmd_encode(const Args &a) {
     auto ctxs = open_gpus(ix, devices_of(a), per_gpu_of(a, kEncodeContextsPerGpu));
     const double t_gpu = since(t0);
     info("Encoding fastX data...");
-    std::string engine = a.get("--deflate", nullptr, "auto");
-    if (engine == "auto") engine = libdeflate_present() ? "adaptive" : "zlib";
     ntc_pipeline_opts o{};
     o.threads = std::atoi(a.get("--threads", nullptr, "0").c_str());
     o.blocks_per_batch = std::atoi(a.get("--blocks-per-batch", nullptr, "4").c_str());
     o.deflate_engine = engine == "adaptive"     ? NTC_DEFLATE_ADAPTIVE
                        : engine == "libdeflate" ? NTC_DEFLATE_LIBDEFLATE
-                       : engine == "zlib"       ? NTC_DEFLATE_ZLIB
-                                                : -1;
-    if (o.deflate_engine < 0) die("--deflate: auto, zlib, libdeflate or adaptive");
+                       : engine == "gpu"        ? NTC_DEFLATE_GPU
+                                                : NTC_DEFLATE_ZLIB;
     o.host_parse = a.flag("--host-parse") ? 1 : 0;
     ntc_pipeline_stats st{};
     ntc_nx_stats nx{};
@@ -746,7 +748,7 @@ void usage(FILE *f) {
                  "                     [--qualities drop|keep|bin8] [--quality-file PATH] [--quality-coder pack|rans]\n"
                  "                     [--quality-smooth [M]] [--quality-smooth-to C]\n"
                  "                     [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]\n"
-                 "                     FILE > encoded.dat\n"
+                 "                     [--deflate auto|zlib|libdeflate|adaptive|gpu] FILE > encoded.dat\n"
                  "                     [--mate-file R2 | --interleaved] [--mate-check ids|off]\n"
                  "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH]\n"
                  "                     [--digest-file PATH] [--mate-out R2.out] [--reads A-B | --shard I/N]\n"
@@ -754,6 +756,9 @@ void usage(FILE *f) {
                  "       ntcomp verify -i PREFIX --digest-file PATH [--exceptions PATH] [--quality-file PATH]\n"
                  "                     [--name-file PATH] [--reads A-B | --shard I/N] FILE\n"
                  "       ntcomp info [--blocks] FILE\n\n"
+                 "  --deflate ENGINE   encode: who gzips the block streams: auto (adaptive when libdeflate.so.0 loads, else\n"
+                 "                     zlib), zlib, libdeflate, adaptive, or gpu (on the GPU behind the packer: 32 KiB\n"
+                 "                     chunks, greedy in-chunk matches, about 2 %% larger; the host only copies)\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
                  "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
                  "                     the replaced symbols to the --exceptions file (lossless)\n"

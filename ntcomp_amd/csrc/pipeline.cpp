@@ -185,6 +185,7 @@ NHooks g_n_hooks = {nullptr, nullptr, nullptr};
 DHooks g_d_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 PHooks g_p_hooks = {nullptr, nullptr, nullptr};
 WHooks g_w_hooks = {nullptr};
+ZHooks g_z_hooks = {nullptr, nullptr};
 }
 
 namespace {
@@ -447,6 +448,7 @@ struct Encoder {
     const int policy;          // -1: the contexts as they are
     const bool keep;
     int engine = 0, q_coder = 0, RT = 1;  // RT: the reader's gang
+    bool gpu_deflate = false;  // NTC_DEFLATE_GPU: the calls return members; engine then serves the side sections
     uint64_t per_batch = 0, d_nodes = 0;
     uint32_t nx_sub = 0, d_k = 0;
     ntc_fastx *fx = nullptr, *fx2 = nullptr;
@@ -963,6 +965,44 @@ void Encoder::run_gpu(int c) {
         std::shared_ptr<uint8_t> pl(payload, ntc_buffer_free);
         SideData sd;
         if (!collect_side(c, nblk, sd)) return;
+        // NTC_DEFLATE_GPU: the payload holds the streams' members; a block's parts are copies of
+        // them behind their headers, and nothing of it goes to the pool but its side sections
+        std::vector<uint64_t> members;
+        std::vector<uint8_t *> parts;
+        if (gpu_deflate) {
+            uint64_t got = 0;
+            members.resize(nblk * 8);
+            const int rm = ntc::g_z_hooks.encode_members(ctxs[c], members.data(), nblk, &got);
+            if (rm || got != nblk) {
+                sh.fail(rm ? rm : NTC_ERR_FORMAT, std::string("encode: members: ") + ntc_last_error(ctxs[c]));
+                return;
+            }
+            parts.assign(nblk * 4, nullptr);
+            const auto drop_parts = [&] {
+                for (uint8_t *p : parts) ntc_buffer_free(p);
+            };
+            for (uint64_t k = 0; k < nblk; k++) {
+                if (metas[k].status == NTC_ERR_EMPTY_READ) continue;
+                if (metas[k].status != NTC_OK) {
+                    drop_parts();
+                    sh.fail(metas[k].status, "malformed block");
+                    return;
+                }
+                for (int s = 0; s < 4; s++) {
+                    const uint64_t off = members[k * 8 + 2 * s], len = members[k * 8 + 2 * s + 1];
+                    uint8_t *p = off + len <= plen && len >= 18 ? (uint8_t *)std::malloc(32 + len) : nullptr;
+                    if (!p) {
+                        drop_parts();
+                        sh.fail(NTC_ERR_CAPACITY, "encode: members: allocation");
+                        return;
+                    }
+                    ntc::stream_header(p, metas[k], s, len);
+                    std::memcpy(p + 32, payload + off, len);
+                    parts[k * 4 + s] = p;
+                }
+            }
+            pl.reset();
+        }
         const std::vector<ntc_nx_run> &runs = sd.runs;
         etrace("gpu done, first block", b.first_block);
         std::lock_guard<std::mutex> g(sh.mu);
@@ -982,7 +1022,11 @@ void Encoder::run_gpu(int c) {
                 bo.nx.push_back(runs[run_at]);
                 bo.nx.back().read -= k * (uint64_t)BR;
             }
-            bo.left = ok ? 4 : 1;
+            bo.left = gpu_deflate ? 0 : ok ? 4 : 1;
+            for (int q = 0; q < 4 && gpu_deflate && ok; q++) {
+                bo.part[q] = parts[k * 4 + q];
+                bo.len[q] = 32 + members[k * 8 + 2 * q + 1];
+            }
             if (q_mode && ok) {  // a dropped block takes its section with it
                 bo.q.has = true;
                 bo.q.meta = sd.qmetas[k];
@@ -1003,7 +1047,8 @@ void Encoder::run_gpu(int c) {
             std::sort(order, order + 4, [&](int x, int y) {
                 return metas[k].stream[x].encoded_size > metas[k].stream[y].encoded_size;
             });
-            for (int q = 0; q < (ok ? 4 : 1); q++) tasks.push_back(Task{pl, metas[k], blk, TaskKind::Stream, order[q], nullptr});
+            for (int q = 0; q < (ok ? 4 : 1) && !gpu_deflate; q++)
+                tasks.push_back(Task{pl, metas[k], blk, TaskKind::Stream, order[q], nullptr});
             pending_tasks++;
         }
         sh.cv.notify_all();
@@ -1227,6 +1272,14 @@ int ntc::pipe::encode_file(const FileJob &job, const FileStats &stats) {
 
     ntc_pipeline_opts o{};
     if (job.opts) o = *job.opts;
+    // NTC_DEFLATE_GPU: the contexts deflate behind their packer ("gpu_deflate"); the side sections stay
+    // with the pool, under the engine `--deflate auto` stands for
+    const ntc::ZHooks &zh = ntc::g_z_hooks;
+    E.gpu_deflate = o.deflate_engine == NTC_DEFLATE_GPU;
+    if (E.gpu_deflate && (!zh.set_mode || !zh.encode_members)) return NTC_ERR_UNSUPPORTED;
+    ModeGuard z_guard(zh.set_mode, ctxs, E.gpu_deflate ? n_ctx : 0, 1);
+    if (z_guard.rc()) return z_guard.rc();
+    if (E.gpu_deflate) o.deflate_engine = ntc::libdeflate_loaded() ? NTC_DEFLATE_ADAPTIVE : NTC_DEFLATE_ZLIB;
     const int T = o.threads > 0 ? o.threads : ntc_host_threads();
     // 4 blocks per GPU call and 64 Mi-base buffers: the first batch is on the GPU after
     // ~30 ms and the pinned ring stays small (10 M x 150 bp: pipeline 0.59 -> 0.32 s against
