@@ -151,6 +151,47 @@ int ntc_deflate_blocks_device(ntc_ctx *ctx, const uint8_t *d_payload, const ntc_
  * NTC_ERR_CAPACITY when cap_blocks is smaller.                                             */
 int ntc_encode_members(ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_blocks, uint64_t *n_blocks);
 
+/* ---- GPU inflate of gzip members of at most 64 KiB (BGZF) -------------------------------- */
+/* Member i is the src_bytes bytes at comp + src_off: one whole gzip member (RFC 1952 with any
+ * of FEXTRA, FNAME, FCOMMENT, FHCRC; RFC 1951 with any number of stored, fixed and dynamic
+ * blocks) that fills those bytes exactly and inflates to exactly out_bytes <= 65,536 bytes,
+ * which go to dst + dst_off.  Each member is decoded on its own (inflate.hip: one workgroup per
+ * member) and its CRC-32 and ISIZE are checked there.  res[i].status:
+ *   0 sound: out_bytes bytes written, crc their CRC-32
+ *   1 bad header (magic, method, a reserved flag bit, the header's CRC16)
+ *   2 bad block (type 3, stored LEN != ~NLEN, HLIT > 286, HDIST > 30)
+ *   3 bad code (what zlib's inflate_table refuses, no end-of-block code, a bad repeat, bits that
+ *     are no code, length symbols 286/287, distance symbols 30/31)
+ *   4 bad distance (past the bytes produced so far)
+ *   5 output overrun (the member holds more than out_bytes)
+ *   6 input overrun (bits needed past src_bytes, or bytes left behind the trailer)
+ *   7 CRC mismatch      8 ISIZE mismatch (against out_bytes or the bytes produced)
+ *   9 too large (out_bytes > 65,536; nothing was looked at)
+ * A member whose status is not 0 writes nothing to dst: no failure touches another member's
+ * bytes or its own.  *n_failed = the members with a status other than 0.  The call returns
+ * NTC_OK when it ran, whatever the statuses.  NTC_ERR_INVALID_ARG, before anything is launched:
+ * a null argument, a member outside comp[0, comp_bytes) or dst[0, dst_cap), two members whose
+ * dst ranges overlap, n >= 2^31.
+ *   ntc_inflate_members         host to host through the GPU; with ctx == NULL the decoder's
+ *                               host restatement runs (the same function with one lane): the
+ *                               device's bytes and statuses, no GPU
+ *   ntc_inflate_members_device  d_comp and d_dst are device buffers; m and res stay on the host.
+ * Both are synchronous.                                                                      */
+#define NTC_INFLATE_MAX_OUT 65536u
+typedef struct ntc_inflate_member {
+    uint64_t src_off;
+    uint32_t src_bytes;
+    uint32_t out_bytes;
+    uint64_t dst_off;
+} ntc_inflate_member; /* 24 bytes */
+typedef struct ntc_inflate_result {
+    uint32_t status, out_bytes, crc, reserved;
+} ntc_inflate_result; /* 16 bytes */
+int ntc_inflate_members(ntc_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const ntc_inflate_member *m, uint64_t n,
+                        uint8_t *dst, uint64_t dst_cap, ntc_inflate_result *res, uint64_t *n_failed);
+int ntc_inflate_members_device(ntc_ctx *ctx, const void *d_comp, uint64_t comp_bytes, const ntc_inflate_member *m,
+                               uint64_t n, void *d_dst, uint64_t dst_cap, ntc_inflate_result *res, uint64_t *n_failed);
+
 /* ---- GPU unpacker (the inverse of the packer) ------------------------------------------ */
 /* decode_block (src/lib.rs:320-368) split at inflate.  ntc_read_block_streams (host): one
  * block's four stream headers at data[0..len) and their gzip members inflated into

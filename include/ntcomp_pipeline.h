@@ -368,6 +368,62 @@ int ntc_decode_file_ex5(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
                         const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p,
                         ntc_r_stats *r);
 
+/* ---- BGZF input inflated on the GPU --------------------------------------------------------- */
+/* ntc_encode_file_ex6 is ntc_encode_file_ex4 with the engine that inflates a BGZF input.
+ * ntc_file_opts6 holds ntc_file_opts5's fields in the same order (the range of reads is not read
+ * here), then its own; struct_bytes must be at least sizeof(ntc_file_opts6).
+ *   NTC_INFLATE_HOST (0)  as ever: libdeflate on the reader's threads
+ *   NTC_INFLATE_GPU  (1)  the reader hands every run of whole BGZF members to an inflater on the
+ *                         first context's device (ntc_inflate_members' decoder; DESIGN.md section
+ *                         27): compressed bytes up, text down into the reader's buffer at the
+ *                         offsets the ISIZE fields give.  Everything after that is unchanged, so
+ *                         encoded.dat and every side file are byte for byte those of the host
+ *                         engine.  A run in which any member fails is not delivered and goes
+ *                         through the host's path, members, errors and exit status as ever; a
+ *                         tail that is not BGZF and a member larger than the room left take the
+ *                         host's paths too.
+ * Under NTC_INFLATE_GPU: NTC_ERR_INVALID_ARG with host_parse = 1; NTC_ERR_UNSUPPORTED, the case in
+ * stats->error, when in_path or mate_path does not start with a BGZF member, and when the GPU
+ * stage's hook table is null (a build without it).  Any other engine is NTC_ERR_INVALID_ARG.
+ * i (may be NULL): the engine, the members and text bytes inflated on the device, the runs
+ * handed to it and those that fell back, and the seconds spent inside the inflater.            */
+#define NTC_INFLATE_HOST 0
+#define NTC_INFLATE_GPU 1
+typedef struct ntc_file_opts6 {
+    uint32_t struct_bytes; /* sizeof(ntc_file_opts6)                           */
+    int32_t nx_policy;     /* NTC_NX_*                                         */
+    int32_t nx_fd;         /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;        /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;          /* encode: quality file, -1 = none                  */
+    const char *nx_path;   /* decode: exceptions file, NULL = none             */
+    const char *q_path;    /* decode: quality file, NULL = none                */
+    int32_t n_mode;        /* 0 drop, 1 keep, 2 id                             */
+    int32_t n_fd;          /* encode: name file, -1 = none                     */
+    const char *n_path;    /* decode: name file, NULL = none                   */
+    int32_t d_mode;        /* 0 none, 1 write digests                          */
+    int32_t d_fd;          /* encode: digest file, -1 = none                   */
+    const char *d_path;    /* decode: digest file, NULL = none                 */
+    int32_t pair_mode;     /* 0 off, 1 pairs + mate check, 2 pairs, no check   */
+    const char *mate_path; /* encode: the mate-2 input, NULL = in_path is interleaved */
+    int32_t out_fd2;       /* decode: the mate-2 text, -1 = none               */
+    uint64_t read_first;   /* decode: the range's first read, from 0           */
+    uint64_t read_count;   /* decode: its reads, 0 = the whole file            */
+    int32_t inflate_engine; /* encode: NTC_INFLATE_*                           */
+    int32_t reserved;      /* 0                                                */
+} ntc_file_opts6;
+typedef struct ntc_i_stats {
+    uint32_t engine;       /* the inflate_engine of the call                   */
+    uint32_t reserved;
+    uint64_t members;      /* BGZF members inflated on the device              */
+    uint64_t bytes;        /* their text                                       */
+    uint64_t runs;         /* runs of members handed to the inflater           */
+    uint64_t fallback_runs; /* ... that were not delivered: a member failed    */
+    double seconds;        /* inside the inflater: copies, kernel, waiting     */
+} ntc_i_stats;
+int ntc_encode_file_ex6(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts6 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n, ntc_d_stats *d, ntc_p_stats *p, ntc_i_stats *i);
+
 #ifdef __cplusplus
 }
 #endif

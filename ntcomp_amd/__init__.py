@@ -42,7 +42,7 @@ EXPORTED = [
     "ntc_index_view_of", "ntc_index_save", "ntc_index_save_as", "ntc_index_load", "ntc_synth_genome", "ntc_synth_strains", "ntc_synth_reads", "ntc_minimizer_keys",
     "ntc_file_header", "ntc_write_block", "ntc_read_block", "ntc_buffer_free", "ntc_pack_block",
     "ntc_deflate_block", "ntc_deflate_stream", "ntc_pack_blocks_device", "ntc_deflate_blocks_device",
-    "ntc_encode_members", "ntc_encode_pack_batch", "ntc_fastq_parse",
+    "ntc_encode_members", "ntc_inflate_members", "ntc_inflate_members_device", "ntc_encode_pack_batch", "ntc_fastq_parse",
     "ntc_encode_pack_fastq", "ntc_read_block_into", "ntc_read_block_streams", "ntc_unpack_streams",
     "ntc_unpacked_records", "ntc_decode_fasta_unpacked",
     "ntc_fastx_open", "ntc_fastx_next_batch", "ntc_fastx_close", "ntc_fasta_format", "ntc_fastx_next_batch_into",
@@ -58,7 +58,7 @@ EXPORTED = [
     "ntc_encode_digests", "ntc_decode_set_digests", "ntc_decode_digests", "ntc_d_write_header",
     "ntc_d_write_section", "ntc_d_read", "ntc_encode_file_ex3", "ntc_decode_file_ex3",
     "ntc_encode_pack_fastq_paired", "ntc_decode_pair_split", "ntc_encode_file_ex4", "ntc_decode_file_ex4",
-    "ntc_decode_set_window", "ntc_decode_file_ex5", "ntc_archive_info",
+    "ntc_decode_set_window", "ntc_decode_file_ex5", "ntc_archive_info", "ntc_encode_file_ex6",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -245,6 +245,25 @@ class FileOpts5(ctypes.Structure):
     _fields_ = FileOpts4._fields_ + [("read_first", ctypes.c_uint64), ("read_count", ctypes.c_uint64)]
 
 
+class FileOpts6(ctypes.Structure):
+    """ntc_file_opts6 (include/ntcomp_pipeline.h): ntc_file_opts5 and the engine that inflates a BGZF input."""
+    _fields_ = FileOpts5._fields_ + [("inflate_engine", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# who inflates a BGZF input (ntc_file_opts6.inflate_engine)
+INFLATE_ENGINES = {"host": 0, "gpu": 1}
+
+
+class IStats(ctypes.Structure):
+    """ntc_i_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [("engine", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("members", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("fallback_runs", ctypes.c_uint64),
+                ("seconds", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class RStats(ctypes.Structure):
     """ntc_r_stats (include/ntcomp_pipeline.h)."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("blocks_total", "reads_total", "first_block", "blocks_read",
@@ -403,6 +422,8 @@ def lib():
         "ntc_pack_blocks_device": (I, [P, P, P, u64, u32, P, u64, P, ctypes.POINTER(u64)]),
         "ntc_deflate_blocks_device": (I, [P, P, P, u64, P, u64, P, ctypes.POINTER(u64)]),
         "ntc_encode_members": (I, [P, P, u64, ctypes.POINTER(u64)]),
+        "ntc_inflate_members": (I, [P, P, u64, P, u64, P, u64, P, ctypes.POINTER(u64)]),
+        "ntc_inflate_members_device": (I, [P, P, u64, P, u64, P, u64, P, ctypes.POINTER(u64)]),
         "ntc_encode_pack_batch": (I, [P, P, P, u64, u32, P, ctypes.POINTER(P), ctypes.POINTER(u64),
                                       ctypes.POINTER(i64)]),
         "ntc_fastq_parse": (I, [P, P, u64, u64, P, u64, P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int64)]),
@@ -454,6 +475,10 @@ def lib():
                                     ctypes.POINTER(NStats)]),
         "ntc_decode_file_ex2": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts2), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats)]),
+        "ntc_encode_file_ex6": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts6), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
+                                    ctypes.POINTER(NStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats),
+                                    ctypes.POINTER(IStats)]),
         "ntc_encode_file_ex3": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts3), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(NxStats), ctypes.POINTER(QStats),
                                     ctypes.POINTER(NStats), ctypes.POINTER(DStats)]),
@@ -965,6 +990,18 @@ class GpuContext:
             raise e
         return off_len, int(used.value)
 
+    def inflate_members_device(self, d_comp, comp_bytes, members, d_dst, dst_cap):
+        """Inflate gzip members from one device buffer into another (ntc_inflate_members_device):
+        members as for inflate_members -> an INFLATE_RESULT array."""
+        m = _inflate_descs(members)
+        res = np.zeros(len(m), dtype=INFLATE_RESULT)
+        bad = ctypes.c_uint64()
+        self._check(self.L.ntc_inflate_members_device(self.h, ctypes.c_void_p(d_comp), comp_bytes, _p(m) if len(m) else None,
+                                                      len(m), ctypes.c_void_p(d_dst), dst_cap,
+                                                      _p(res) if len(m) else None, ctypes.byref(bad)),
+                    "ntc_inflate_members_device")
+        return res
+
     def encode_members(self):
         """Where the members lie in the payload of the last encode_pack* call under option
         "gpu_deflate" (ntc_encode_members) -> uint64 array [blocks, 4, 2] of (offset, bytes)."""
@@ -1329,6 +1366,70 @@ def deflate_stream(meta, stream, payload, engine="zlib"):
         lib().ntc_buffer_free(out)
 
 
+# ---- inflate of gzip members of at most 64 KiB (ntc_inflate_members, include/ntcomp_codec.h) ----
+INFLATE_MAX_OUT = 65536
+INFLATE_MEMBER = np.dtype([("src_off", "<u8"), ("src_bytes", "<u4"), ("out_bytes", "<u4"), ("dst_off", "<u8")])
+INFLATE_RESULT = np.dtype([("status", "<u4"), ("out_bytes", "<u4"), ("crc", "<u4"), ("reserved", "<u4")])
+INFLATE_STATUS = {0: "ok", 1: "bad header", 2: "bad block", 3: "bad code", 4: "bad distance", 5: "output overrun",
+                  6: "input overrun", 7: "CRC mismatch", 8: "ISIZE mismatch", 9: "too large"}
+
+
+def bgzf_members(blob):
+    """The BGZF members at the start of blob -> list of (offset, size, ISIZE).  A member is a gzip
+    member with FEXTRA whose extra field holds the subfield 'B' 'C' of two bytes, BSIZE = size - 1;
+    the list ends at the first bytes that are no such member, or whose size passes the blob."""
+    blob = memoryview(blob)
+    out, at, n = [], 0, len(blob)
+    while n - at >= 18 and bytes(blob[at:at + 4]) == b"\x1f\x8b\x08\x04":
+        xlen = blob[at + 10] | blob[at + 11] << 8
+        p, end, size = at + 12, at + 12 + xlen, None
+        while p + 4 <= min(end, n):
+            slen = blob[p + 2] | blob[p + 3] << 8
+            if blob[p] == 66 and blob[p + 1] == 67 and slen == 2 and p + 6 <= min(end, n):
+                size = (blob[p + 4] | blob[p + 5] << 8) + 1
+                break
+            p += 4 + slen
+        if size is None or size < xlen + 12 + 8 or at + size > n:
+            break
+        out.append((at, size, int.from_bytes(blob[at + size - 4:at + size], "little")))
+        at += size
+    return out
+
+
+def _inflate_descs(members):
+    if isinstance(members, np.ndarray) and members.dtype == INFLATE_MEMBER:
+        return np.ascontiguousarray(members)
+    m = np.zeros(len(members), dtype=INFLATE_MEMBER)
+    at = 0
+    for i, t in enumerate(members):
+        if len(t) == 3:  # (offset, size, ISIZE) as bgzf_members lists them: the outputs back to back
+            m[i] = (t[0], t[1], t[2], at)
+            at += t[2]
+        else:
+            m[i] = tuple(t)
+    return m
+
+
+def inflate_members(ctx, blob, members, out=None):
+    """Inflate gzip members of blob (ntc_inflate_members): on ctx's GPU, or with ctx None through the
+    decoder's host restatement.  members: an INFLATE_MEMBER array, tuples (src_off, src_bytes,
+    out_bytes, dst_off), or bgzf_members' triples (their outputs then lie back to back).  Returns
+    (the output as a uint8 array, an INFLATE_RESULT array); a member whose status is not 0 leaves
+    its bytes of the output as they were (zeros, or what `out` held)."""
+    m = _inflate_descs(members)
+    src = np.frombuffer(bytes(blob), dtype=np.uint8) if len(blob) else np.zeros(1, dtype=np.uint8)
+    if out is None:
+        out = np.zeros(int(max((int(d["dst_off"]) + int(d["out_bytes"]) for d in m), default=0)), dtype=np.uint8)
+    res = np.zeros(len(m), dtype=INFLATE_RESULT)
+    bad = ctypes.c_uint64()
+    rc = lib().ntc_inflate_members(ctx.h if ctx is not None else None, _p(src), len(blob), _p(m) if len(m) else None, len(m),
+                                   _p(out) if len(out) else None, len(out), _p(res) if len(m) else None, ctypes.byref(bad))
+    if rc:
+        raise NtcError(rc, lib().ntc_last_error(ctx.h).decode(errors="replace") if ctx is not None else "ntc_inflate_members")
+    assert int(bad.value) == int((res["status"] != 0).sum())
+    return out, res
+
+
 def read_block(data):
     """One block of decode_block (lib.rs:320-363) -> (u64 records, bytes consumed,
     num_records header field).  NtcError(NTC_ERR_IO) at a clean end of input."""
@@ -1388,7 +1489,7 @@ def concat_streams(blocks):
 # ---- FASTX ingest ---------------------------------------------------------------------
 def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_bases=0, deflate="zlib",
                 host_parse=False, non_acgt=None, nx_fd=-1, qualities=None, q_fd=-1, names=None, n_fd=-1, d_fd=None,
-                mate_path=None, pair_mode=None):
+                mate_path=None, pair_mode=None, inflate="host"):
     """`ntcomp encode` file to file (ntc_encode_file, include/ntcomp_pipeline.h): FASTX ->
     GPU encode + block packer on every context -> deflate pool -> encoded.dat on out_fd.
     A plain FASTQ is parsed on the GPU unless host_parse.  Returns the per-stage stats as
@@ -1403,11 +1504,23 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
     descriptor ("NTCD"), and the stats gain a "d" dict (ntc_d_stats).  pair_mode ("ids", "nocheck";
     ntc_encode_file_ex4): the reads are pairs, in_path interleaved, or with mate_path the mate-1 file
     beside the mate-2 file mate_path (then pair_mode defaults to "ids"); the stats gain a "p" dict
-    (ntc_p_stats)."""
+    (ntc_p_stats).  inflate ("host", "gpu"; ntc_encode_file_ex6): under "gpu" the runs of members of a
+    BGZF input are inflated on the first context's device, the output is byte for byte that of
+    "host", and the stats gain an "i" dict (ntc_i_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, batch_bases, DEFLATE_ENGINES[deflate], 1 if host_parse else 0)
     if mate_path is not None and pair_mode is None:
         pair_mode = "ids"
     pairs = _pair_code(pair_mode) if pair_mode is not None else 0
+    if INFLATE_ENGINES[inflate]:
+        fo = FileOpts6(ctypes.sizeof(FileOpts6), _policy_code(non_acgt or 0), nx_fd, _quality_code(qualities or 0), q_fd, None,
+                       None, _names_code(names or 0), n_fd, None, 0 if d_fd is None else 1, -1 if d_fd is None else d_fd, None,
+                       pairs, None if mate_path is None else os.fsencode(mate_path), -1, 0, 0, INFLATE_ENGINES[inflate], 0)
+        side = [("nx", NxStats()), ("q", QStats()), ("n", NStats()), ("d", DStats()), ("p", PStats()), ("i", IStats())]
+        d = _run_pipeline("ntc_encode_file_ex6", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                          tail=tuple(ctypes.byref(s) for _, s in side))
+        asked = {"nx": True, "q": qualities is not None, "n": names is not None, "d": d_fd is not None, "p": bool(pairs), "i": True}
+        d.update({key: _stats_dict(s) for key, s in side if asked[key]})
+        return d
     level = 4 if pairs else 3 if d_fd is not None else 2 if names is not None else 1 if qualities is not None else 0
     if level == 0 and non_acgt is None:
         return _run_pipeline("ntc_encode_file", ctxs, in_path, out_fd, o)

@@ -260,6 +260,27 @@ def _check_p_args(args):
     return None if not pairs else "nocheck" if args.mate_check == "off" else "ids"
 
 
+def _check_i_args(args):
+    """encode: --inflate gpu takes BGZF inputs alone (their first 18 bytes decide) and feeds the GPU parser."""
+    if args.inflate not in ("host", "gpu"):
+        _bad_args("encode: --inflate: host or gpu")
+    if args.inflate != "gpu":
+        return
+    if args.host_parse:
+        _bad_args("encode: --inflate gpu feeds the GPU parser: not with --host-parse")
+    for p in (args.query_file, args.mate_file):
+        if not p:
+            continue
+        try:
+            with open(p, "rb") as f:
+                h = f.read(18)
+        except OSError:
+            h = b""
+        if not (len(h) == 18 and h[:3] == b"\x1f\x8b\x08" and h[3] & 4 and h[10] | h[11] << 8 >= 6 and h[12:14] == b"BC"
+                and (h[16] | h[17] << 8) + 1 >= 26):
+            _bad_args(f"encode: --inflate gpu: {p} does not start with a BGZF member")
+
+
 def parse_reads(spec):
     """--reads A-B, 1-based and inclusive as decode prints seq.N; also A, A- and -B.  Returns
     (a, b) with b None for "to the last read"; ValueError for anything else."""
@@ -342,6 +363,7 @@ def cmd_encode(args):
     _check_n_args(args)
     _check_d_args(args, "encode", (args.exceptions, args.quality_file, args.name_file, args.query_file))
     pair_mode = _check_p_args(args)
+    _check_i_args(args)
     import ntcomp_amd as nt
     st = _Stats(args.stats)
     log("Loading SBWT index...")
@@ -389,7 +411,9 @@ def cmd_encode(args):
             nx_args.update(d_fd=d_file.fileno())
         if pair_mode:
             nx_args.update(pair_mode=pair_mode, mate_path=args.mate_file)
-        res = st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
+        if args.inflate == "gpu":
+            nx_args.update(inflate="gpu")
+        res =st.wrap("pipeline", nt.encode_file)(ctxs, args.query_file, out.fileno(), threads=args.threads,
                                                   blocks_per_batch=args.blocks_per_batch, deflate=args.deflate,
                                                   host_parse=args.host_parse, **nx_args)
     except nt.NtcError as e:
@@ -425,7 +449,11 @@ def cmd_encode(args):
               **({"names": args.names, **{"n_" + k: v for k, v in res["n"].items()}} if "n" in res else {}),
               **({"d_" + k: v for k, v in res["d"].items() if k != "not_checkable"} if "d" in res else {}),
               **({"pairs": res["p"]["pairs"], "mate_check": "off" if pair_mode == "nocheck" else "ids",
-                  "mate1_bytes": res["p"]["bytes1"], "mate2_bytes": res["p"]["bytes2"]} if "p" in res else {}))
+                  "mate1_bytes": res["p"]["bytes1"], "mate2_bytes": res["p"]["bytes2"]} if "p" in res else {}),
+              inflate=args.inflate,
+              **{"inflate_" + k: v for k, v in res.get("i", dict.fromkeys(("members", "bytes", "runs", "fallback_runs"), 0)).items()
+                 if k not in ("engine", "seconds")},
+              inflate_s=round(res.get("i", {}).get("seconds", 0.0), 3))
 
 
 def cmd_decode(args, verify=False):
@@ -564,6 +592,10 @@ def main(argv=None):
                         "differ, the inflated streams do not; no engine reproduces the reference's zlib-rs bytes.  gpu: the "
                         "streams are deflated on the GPU behind the packer (32 KiB chunks, greedy in-chunk matches; about "
                         "2 %% larger) and the host only copies the members; side files are deflated as under auto")
+    e.add_argument("--inflate", default="host", metavar="ENGINE",
+                   help="who inflates a BGZF input: host (default; libdeflate on the reader's threads) or gpu (runs of "
+                        "members inflated on the first GPU; every input must be BGZF; the output is byte for byte the host "
+                        "engine's; not with --host-parse)")
     e.add_argument("--stats", action="store_true", help="print per-stage seconds to stderr")
     e.add_argument("--host-parse", action="store_true",
                    help="parse a plain FASTQ on the host pool instead of the GPU")

@@ -26,6 +26,7 @@
 #include "names_core.h"
 #include "digest_core.h"
 #include "deflate_core.h"
+#include "inflate_core.h"
 #include "pair_core.h"
 #include "window_core.h"
 #include "ntc_internal.h"
@@ -57,7 +58,8 @@ enum WsSlot {
     WS_N_COLS, WS_N_BLOCKS, WS_N_PAYLOAD, WS_ND_IN, WS_ND_COLS, WS_ND_NAMES,
     WS_DG_TABLE, WS_DGD_IN,
     WS_PAIR_IN, WS_PAIR_TAB, WS_PAIR_ST, WS_PAIR_SCAN, WS_PAIR_OUT,
-    WS_DF_DESC, WS_DF_TOKENS, WS_DF_STAGE, WS_DF_RES, WS_DF_OUT, WS_COUNT
+    WS_DF_DESC, WS_DF_TOKENS, WS_DF_STAGE, WS_DF_RES, WS_DF_OUT,
+    WS_INF_COMP, WS_INF_DESC, WS_INF_DST, WS_INF_RES, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -2483,6 +2485,215 @@ int ntc_encode_members(ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_bloc
 
 }  // extern "C"
 
+// ---- inflate of gzip members (inflate.hip) ----------------------------------------------------
+namespace {
+static_assert(sizeof(ntc_inflate_member) == 24 && sizeof(InfMemberDesc) == 24 && offsetof(ntc_inflate_member, dst_off) == 16 &&
+                  offsetof(InfMemberDesc, dst_off) == 16 && offsetof(InfMemberDesc, out_bytes) == 12,
+              "ntc_inflate_member is the kernel's descriptor");
+static_assert(sizeof(ntc_inflate_result) == sizeof(InfResult) && NTC_INFLATE_MAX_OUT == kInfMaxOut, "ntc_inflate_result is the kernel's result");
+
+// What ntc_inflate_members refuses before anything runs.  order: the members with bytes to
+// write, by dst_off; span: [0] / [1] the first and one past the last byte of comp they cover,
+// [2] / [3] the same of dst.
+int inflate_check(ntc_ctx *ctx, uint64_t comp_bytes, const ntc_inflate_member *m, uint64_t n, uint64_t dst_cap,
+                  std::vector<uint32_t> &order, uint64_t span[4]) {
+    if (n >> 31) return set_err(ctx, NTC_ERR_INVALID_ARG, "2^31 members or more in one call");
+    span[0] = span[2] = UINT64_MAX, span[1] = span[3] = 0;
+    order.clear();
+    for (uint64_t i = 0; i < n; i++) {
+        if (m[i].src_off > comp_bytes || m[i].src_bytes > comp_bytes - m[i].src_off)
+            return set_err(ctx, NTC_ERR_INVALID_ARG, "member " + std::to_string(i) + " lies outside the compressed bytes");
+        if (m[i].dst_off > dst_cap || m[i].out_bytes > dst_cap - m[i].dst_off)
+            return set_err(ctx, NTC_ERR_INVALID_ARG, "member " + std::to_string(i) + " lies outside the output");
+        span[0] = std::min(span[0], m[i].src_off), span[1] = std::max(span[1], m[i].src_off + m[i].src_bytes);
+        span[2] = std::min(span[2], m[i].dst_off), span[3] = std::max(span[3], m[i].dst_off + m[i].out_bytes);
+        if (m[i].out_bytes) order.push_back((uint32_t)i);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return m[a].dst_off < m[b].dst_off; });
+    for (size_t k = 1; k < order.size(); k++)
+        if (m[order[k - 1]].dst_off + m[order[k - 1]].out_bytes > m[order[k]].dst_off)
+            return set_err(ctx, NTC_ERR_INVALID_ARG, "members " + std::to_string(order[k - 1]) + " and " +
+                                                         std::to_string(order[k]) + " overlap in the output");
+    if (!n) span[0] = span[2] = 0;
+    return NTC_OK;
+}
+
+// descriptors up, the kernel, results down (device buffers d_comp / d_dst; the descriptors'
+// offsets less src_base / dst_base)
+int inflate_launch(ntc_ctx *ctx, const uint8_t *d_comp, uint64_t src_base, const ntc_inflate_member *m, uint64_t n,
+                   uint8_t *d_dst, uint64_t dst_base, ntc_inflate_result *res) {
+    void *d_desc, *d_res;
+    int rc;
+    if ((rc = ensure(ctx, WS_INF_DESC, n * sizeof(InfMemberDesc), &d_desc))) return rc;
+    if ((rc = ensure(ctx, WS_INF_RES, n * sizeof(InfResult), &d_res))) return rc;
+    std::vector<InfMemberDesc> desc(n);
+    for (uint64_t i = 0; i < n; i++)
+        desc[i] = InfMemberDesc{m[i].src_off - src_base, m[i].src_bytes, m[i].out_bytes, m[i].dst_off - dst_base};
+    HIP_TRY(ctx, hipMemcpyAsync(d_desc, desc.data(), n * sizeof(InfMemberDesc), hipMemcpyHostToDevice, ctx->stream));
+    InfArgs a{};
+    a.comp = d_comp;
+    a.members = (const InfMemberDesc *)d_desc;
+    a.n_members = (uint32_t)n;
+    a.dst = d_dst;
+    a.results = (InfResult *)d_res;
+    launch_inflate(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(res, d_res, n * sizeof(InfResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (desc lives until here)
+    return NTC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ntc_inflate_members(ntc_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, const ntc_inflate_member *m, uint64_t n,
+                        uint8_t *dst, uint64_t dst_cap, ntc_inflate_result *res, uint64_t *n_failed) {
+    if (!n_failed || (n && (!m || !res || !comp))) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_failed = 0;
+    std::vector<uint32_t> order;
+    uint64_t span[4];
+    int rc;
+    if ((rc = inflate_check(ctx, comp_bytes, m, n, dst_cap, order, span))) return rc;
+    if (!order.empty() && !dst) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    if (!n) return NTC_OK;
+    if (!ctx) {  // the host restatement: the kernel's function, one lane
+        InfWork *W = new InfWork;
+        for (uint64_t i = 0; i < n; i++) {
+            inf_member(W, comp + m[i].src_off, m[i].src_bytes, m[i].out_bytes, dst + m[i].dst_off, (InfResult *)&res[i], 0, 1);
+            *n_failed += res[i].status != 0;
+        }
+        delete W;
+        return NTC_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the compressed bytes the members cover go up; the output's place starts 16-aligned so that
+    // a member lands as aligned on the device as it will on the host
+    const uint64_t dst_base = span[2] & ~15ull;
+    void *d_comp, *d_dst;
+    if ((rc = ensure(ctx, WS_INF_COMP, span[1] - span[0], &d_comp))) return rc;
+    if ((rc = ensure(ctx, WS_INF_DST, span[3] - dst_base, &d_dst))) return rc;
+    if (span[1] > span[0])
+        HIP_TRY(ctx, hipMemcpyAsync(d_comp, comp + span[0], span[1] - span[0], hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = inflate_launch(ctx, (const uint8_t *)d_comp, span[0], m, n, (uint8_t *)d_dst, dst_base, res))) return rc;
+    for (uint64_t i = 0; i < n; i++) *n_failed += res[i].status != 0;
+    // the sound members' bytes come down, neighbours in one copy; nothing else of dst is touched
+    for (size_t k = 0; k < order.size();) {
+        if (res[order[k]].status) {
+            k++;
+            continue;
+        }
+        const uint64_t from = m[order[k]].dst_off;
+        uint64_t to = from + m[order[k]].out_bytes;
+        for (k++; k < order.size() && !res[order[k]].status && m[order[k]].dst_off == to; k++) to += m[order[k]].out_bytes;
+        HIP_TRY(ctx, hipMemcpyAsync(dst + from, (const uint8_t *)d_dst + (from - dst_base), to - from, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NTC_OK;
+}
+
+int ntc_inflate_members_device(ntc_ctx *ctx, const void *d_comp, uint64_t comp_bytes, const ntc_inflate_member *m,
+                               uint64_t n, void *d_dst, uint64_t dst_cap, ntc_inflate_result *res, uint64_t *n_failed) {
+    if (!ctx || !n_failed || (n && (!m || !res || !d_comp))) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_failed = 0;
+    std::vector<uint32_t> order;
+    uint64_t span[4];
+    int rc;
+    if ((rc = inflate_check(ctx, comp_bytes, m, n, dst_cap, order, span))) return rc;
+    if (!order.empty() && !d_dst) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    if (!n) return NTC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = inflate_launch(ctx, (const uint8_t *)d_comp, 0, m, n, (uint8_t *)d_dst, 0, res))) return rc;
+    for (uint64_t i = 0; i < n; i++) *n_failed += res[i].status != 0;
+    return NTC_OK;
+}
+
+}  // extern "C"
+
+// The file pipeline's inflater (`--inflate gpu`, ntc_internal.h IHooks): one per encode call, on
+// the first context's device, used by the reader thread alone.  It owns a stream, grow-only
+// device buffers for a run's compressed bytes, descriptors, text and results, and a pinned
+// staging buffer that takes the compressed bytes (the reader's window is pageable) and the
+// results.  The text goes from the device straight to the caller's buffer.
+namespace ntc {
+struct Inflater {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    void *d_comp = nullptr, *d_text = nullptr, *d_desc = nullptr, *d_res = nullptr;
+    uint64_t comp_cap = 0, text_cap = 0, n_cap = 0;
+    uint8_t *stage = nullptr;  // pinned: compressed bytes, then descriptors, then results
+    uint64_t stage_cap = 0;
+    std::mutex mu;
+    ~Inflater() {
+        (void)hipSetDevice(device);
+        for (void *p : {d_comp, d_text, d_desc, d_res})
+            if (p) (void)hipFree(p);
+        if (stage) (void)hipHostFree(stage);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    static bool grow(void **p, uint64_t *cap, uint64_t want) {
+        if (*cap >= want) return true;
+        if (*p) (void)hipFree(*p);
+        *p = nullptr, *cap = 0;
+        want += want / 4 + 4096;
+        if (hipMalloc(p, want) != hipSuccess) return (void)hipGetLastError(), false;
+        *cap = want;
+        return true;
+    }
+    int run(const uint8_t *comp, uint64_t comp_bytes, const ntc_inflate_member *m, uint64_t n, uint8_t *dst, uint64_t dst_bytes,
+            uint64_t *n_failed) {
+        *n_failed = 0;
+        if (!n) return NTC_OK;
+        if (n >> 31) return NTC_ERR_CAPACITY;
+        std::lock_guard<std::mutex> guard(mu);  // (a pair's two readers share it)
+        // (the reader lays the members back to back in comp and dst: nothing to check but the ends)
+        for (uint64_t i = 0; i < n; i++)
+            if (m[i].src_off + m[i].src_bytes > comp_bytes || m[i].dst_off + m[i].out_bytes > dst_bytes ||
+                (i && m[i].dst_off < m[i - 1].dst_off + m[i - 1].out_bytes))
+                return NTC_ERR_INVALID_ARG;
+        if (hipSetDevice(device) != hipSuccess) return NTC_ERR_HIP;
+        const uint64_t desc_bytes = n * sizeof(InfMemberDesc), res_bytes = n * sizeof(InfResult);
+        const uint64_t comp_room = (comp_bytes + 63) & ~63ull;
+        const uint64_t need = comp_room + desc_bytes + res_bytes;
+        if (stage_cap < need) {
+            if (stage) (void)hipHostFree(stage);
+            stage = nullptr, stage_cap = 0;
+            if (hipHostMalloc((void **)&stage, need + need / 4, hipHostMallocDefault) != hipSuccess) return NTC_ERR_HIP;
+            stage_cap = need + need / 4;
+        }
+        uint64_t cap_desc = n_cap * sizeof(InfMemberDesc), cap_res = n_cap * sizeof(InfResult);
+        if (!grow(&d_comp, &comp_cap, comp_bytes) || !grow(&d_text, &text_cap, dst_bytes) || !grow(&d_desc, &cap_desc, desc_bytes) ||
+            !grow(&d_res, &cap_res, res_bytes))
+            return NTC_ERR_CAPACITY;
+        n_cap = std::min(cap_desc / sizeof(InfMemberDesc), cap_res / sizeof(InfResult));
+        std::memcpy(stage, comp, comp_bytes);
+        InfMemberDesc *h_desc = (InfMemberDesc *)(stage + comp_room);
+        for (uint64_t i = 0; i < n; i++) h_desc[i] = InfMemberDesc{m[i].src_off, m[i].src_bytes, m[i].out_bytes, m[i].dst_off};
+        InfResult *h_res = (InfResult *)(stage + comp_room + desc_bytes);
+        if (hipMemcpyAsync(d_comp, stage, comp_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+            hipMemcpyAsync(d_desc, h_desc, desc_bytes, hipMemcpyHostToDevice, stream) != hipSuccess)
+            return NTC_ERR_HIP;
+        InfArgs a{};
+        a.comp = (const uint8_t *)d_comp;
+        a.members = (const InfMemberDesc *)d_desc;
+        a.n_members = (uint32_t)n;
+        a.dst = (uint8_t *)d_text;
+        a.results = (InfResult *)d_res;
+        launch_inflate(a, stream);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return NTC_ERR_HIP;
+        for (uint64_t i = 0; i < n; i++) *n_failed += h_res[i].status != 0;
+        if (*n_failed) return NTC_OK;  // nothing of the run is delivered
+        if (dst_bytes && (hipMemcpyAsync(dst, d_text, dst_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                          hipStreamSynchronize(stream) != hipSuccess))
+            return NTC_ERR_HIP;
+        return NTC_OK;
+    }
+};
+}  // namespace ntc
+
 namespace {
 // encode + GPU block packer over reads already in HBM (d_offs: n_reads + 1 offsets, room for
 // n_reads + 1 more behind them, where the record offsets go); the tail of
@@ -3721,6 +3932,25 @@ struct NxHookFill {
         ntc::g_d_hooks.set_discard = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "discard_text", on); };
         ntc::g_z_hooks.set_mode = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "gpu_deflate", on); };
         ntc::g_z_hooks.encode_members = ntc_encode_members;
+        ntc::g_i_hooks.create = [](ntc_ctx *ctx, ntc::Inflater **out) {
+            if (!ctx || !out) return (int)NTC_ERR_INVALID_ARG;
+            *out = nullptr;
+            if (hipSetDevice(ctx->device) != hipSuccess) return set_err(ctx, NTC_ERR_HIP, "hipSetDevice");
+            ntc::Inflater *inf = new ntc::Inflater;
+            inf->device = ctx->device;
+            if (hipStreamCreateWithFlags(&inf->stream, hipStreamNonBlocking) != hipSuccess) {
+                inf->stream = nullptr;
+                delete inf;
+                return set_err(ctx, NTC_ERR_HIP, "the inflater's stream");
+            }
+            *out = inf;
+            return (int)NTC_OK;
+        };
+        ntc::g_i_hooks.run = [](ntc::Inflater *inf, const uint8_t *comp, uint64_t comp_bytes, const ntc_inflate_member *m,
+                                uint64_t n, uint8_t *dst, uint64_t dst_bytes, uint64_t *n_failed) {
+            return inf->run(comp, comp_bytes, m, n, dst, dst_bytes, n_failed);
+        };
+        ntc::g_i_hooks.destroy = [](ntc::Inflater *inf) { delete inf; };
     }
 } g_nx_hook_fill;
 }  // namespace

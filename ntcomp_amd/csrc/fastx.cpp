@@ -39,6 +39,9 @@
 #include <thread>
 #include <vector>
 
+#include <chrono>
+
+#include "../../include/ntcomp_codec.h"
 #include "../../include/ntcomp_host.h"
 #include "ntc_internal.h"
 
@@ -224,6 +227,9 @@ struct ByteReader {  // read up to n decoded bytes: > 0 bytes, 0 at the end, < 0
         }
         return 1;
     }
+    // `--inflate gpu`: only the BGZF member reader takes an inflater
+    virtual bool set_inflater(ntc::Inflater *) { return false; }
+    virtual const ntc::InflateCounts *inflate_counts() const { return nullptr; }
 };
 
 struct GzReader : ByteReader {  // plain or gzip (zlib's transparent gz* reader)
@@ -457,6 +463,14 @@ struct DeflateReader : ByteReader {
     uint64_t delivered = 0, members = 0;
     GzReader *zfall = nullptr;  // zlib takes over after a libdeflate failure
     bool ok = false;
+    std::atomic<ntc::Inflater *> gpu{nullptr};  // `--inflate gpu` (not owned): inflate_members_into goes through it
+    ntc::InflateCounts counts;
+    bool set_inflater(ntc::Inflater *inf) override {
+        if (!bgzf) return false;
+        gpu.store(inf);
+        return true;
+    }
+    const ntc::InflateCounts *inflate_counts() const override { return bgzf ? &counts : nullptr; }
     DeflateReader(const char *p, FILE *file, uint64_t size, bool is_bgzf) : path(p), f(file), bgzf(is_bgzf) {
         void *h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
         if (h) {
@@ -511,6 +525,30 @@ struct DeflateReader : ByteReader {
         }
         return true;
     }
+    // `--inflate gpu`: the members at[] (sizes sz[], outputs at off[]) through the inflater into
+    // dst.  1 delivered, 0 a member failed and nothing was delivered, -1 the device failed
+    int gpu_run(ntc::Inflater *inf, const std::vector<size_t> &at, const std::vector<size_t> &sz, const std::vector<size_t> &off,
+                char *dst) {
+        std::vector<ntc_inflate_member> m(at.size());
+        for (size_t j = 0; j < at.size(); j++) {
+            if (off[j + 1] - off[j] > 0xFFFFFFFFull) return 0;
+            m[j] = ntc_inflate_member{at[j] - at[0], (uint32_t)sz[j], (uint32_t)(off[j + 1] - off[j]), off[j]};
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        uint64_t failed = 0;
+        const int rc = ntc::g_i_hooks.run(inf, comp.data() + at[0], at.back() + sz.back() - at[0], m.data(), m.size(),
+                                          (uint8_t *)dst, off.back(), &failed);
+        counts.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        counts.runs++;
+        if (rc != 0) return -1;
+        if (failed) {
+            counts.fallback_runs++;
+            return 0;
+        }
+        counts.members += at.size();
+        counts.bytes += off.back();
+        return 1;
+    }
     // The next run of up to kBatch BGZF members, inflated in parallel (bgzip's members are
     // independent).  1 done, 0 no member here, -1 error
     static constexpr size_t kBatch = 256;
@@ -547,6 +585,17 @@ struct DeflateReader : ByteReader {
             cap = std::max<size_t>(off.back() + 1, kBatch << 16);
             out = (char *)std::malloc(cap);
             if (!out) return -1;
+        }
+        if (ntc::Inflater *inf = gpu.load()) {  // `--inflate gpu`; a run with a member that fails goes on below, as ever
+            const int rg = gpu_run(inf, at, sz, off, out);
+            if (rg < 0) return -1;
+            if (rg == 1) {
+                ci = at.back() + sz.back();
+                members += at.size();
+                out_n = off.back();
+                out_pos = 0;
+                return 1;
+            }
         }
         const unsigned T = std::max(1u, std::min<unsigned>(8, std::thread::hardware_concurrency()));
         while (pool.size() < T) {
@@ -632,6 +681,15 @@ struct DeflateReader : ByteReader {
             c += b;
         }
         if (at.empty()) return 0;
+        if (ntc::Inflater *inf = gpu.load()) {  // `--inflate gpu`: the same run through the device's decoder
+            const int rg = gpu_run(inf, at, sz, off, dst);
+            if (rg < 0) return -1;
+            if (rg == 0) return 0;  // as below: nothing is delivered, the buffered path takes the same members
+            ci = at.back() + sz.back();
+            members += at.size();
+            delivered += off.back();
+            return (int64_t)off.back();
+        }
         const unsigned T = (unsigned)std::max(1, std::min(16, ntc_host_threads()));
         while (pool.size() < T) {
             void *d = alloc_fn();
@@ -1219,7 +1277,8 @@ static ntc_fastx *open_mapped_fastq(const char *path) {
     return fx;
 }
 
-int ntc_fastx_open(const char *path, ntc_fastx **out) {
+// inf (may be null): the inflater a BGZF member reader uses from its first member on
+static int fastx_open_with(const char *path, ntc_fastx **out, ntc::Inflater *inf) {
     if (!path || !out) return NTC_ERR_INVALID_ARG;
     *out = nullptr;
     init_norm();
@@ -1231,6 +1290,7 @@ int ntc_fastx_open(const char *path, ntc_fastx **out) {
     int orc = NTC_OK;
     ByteReader *f = open_reader(path, &orc);
     if (!f) return orc;
+    if (inf) f->set_inflater(inf);  // (before the producer thread starts to read ahead)
     auto *fx = new ntc_fastx();
     fx->f = f;
     fx->src = new ChunkSource(f);
@@ -1255,7 +1315,13 @@ int ntc_fastx_open(const char *path, ntc_fastx **out) {
     return NTC_OK;
 }
 
+int ntc_fastx_open(const char *path, ntc_fastx **out) { return fastx_open_with(path, out, nullptr); }
+
 }  // extern "C"
+
+namespace ntc {
+int fastx_open_inflating(const char *path, Inflater *inf, ntc_fastx **out) { return fastx_open_with(path, out, inf); }
+}  // namespace ntc
 
 namespace ntc {
 const uint8_t *fastx_mapped(ntc_fastx *fx, uint64_t *size) {
@@ -1267,6 +1333,13 @@ void fastx_seek_mapped(ntc_fastx *fx, uint64_t pos) {
     if (fx && fx->mm) fx->mm_pos = std::min<size_t>((size_t)pos, fx->mm_n);
 }
 bool fastx_streamed_fastq(ntc_fastx *fx) { return fx && !fx->mm && fx->src && fx->format == '@'; }
+bool fastx_is_bgzf(ntc_fastx *fx) { return fx && fx->f && fx->f->inflate_counts() != nullptr; }
+void fastx_inflate_counts(ntc_fastx *fx, InflateCounts *out) {
+    const InflateCounts *c = fx && fx->f ? fx->f->inflate_counts() : nullptr;
+    if (!c) return;
+    out->members += c->members, out->bytes += c->bytes, out->runs += c->runs, out->fallback_runs += c->fallback_runs;
+    out->seconds += c->seconds;
+}
 uint64_t fastx_stream_read(ntc_fastx *fx, uint8_t *dst, uint64_t cap, bool *io_error) {
     uint64_t got = 0;
     while (got < cap) {

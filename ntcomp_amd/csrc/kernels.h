@@ -453,6 +453,24 @@ struct DfArgs {
     uint8_t *out;
 };
 void launch_deflate(const DfArgs &a, hipStream_t s);
+// Inflate of gzip members (inflate.hip, inflate_core.h).  Member i is the src_bytes bytes at comp +
+// src_off and inflates to out_bytes bytes at dst + dst_off (ntc_inflate_member's layout); its
+// status, bytes and CRC-32 go to results[i].  Everything is device memory; the caller has checked
+// that the members lie inside comp and dst and that no two dst ranges overlap.
+struct InfResult;
+struct InfMemberDesc {
+    uint64_t src_off;
+    uint32_t src_bytes, out_bytes;
+    uint64_t dst_off;
+};
+struct InfArgs {
+    const uint8_t *comp;
+    const InfMemberDesc *members;
+    uint32_t n_members;
+    uint8_t *dst;
+    InfResult *results;
+};
+void launch_inflate(const InfArgs &a, hipStream_t s);
 // launch_fasta's FASTQ twin: "@seq.{first_id + r}\n{read r}\n+\n{qualities r}\n"
 void launch_fastq_text(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t n,
                        uint64_t first_id, const unsigned long long *d_status, uint64_t *sizes, uint64_t *out_offs,

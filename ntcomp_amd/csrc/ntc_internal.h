@@ -95,6 +95,7 @@ struct ntc_nx_run;
 struct ntc_qual_meta;
 struct ntc_name_meta;
 struct ntc_digest_meta;
+struct ntc_inflate_member;
 namespace ntc {
 // a plain FASTQ that ntc_fastx_open mapped: its bytes (null for any other input), and
 // moving the mapped parser to byte pos (a record start) -- pipeline.cpp's GPU-parse reader
@@ -185,6 +186,30 @@ struct ZHooks {
     int (*encode_members)(::ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_blocks, uint64_t *n_blocks);
 };
 extern ZHooks g_z_hooks;
+// ... and for `--inflate gpu`: an inflater lives on one device, with a stream, device buffers and a
+// pinned staging buffer of its own (capi.cpp), and inflates a run of BGZF members from host memory
+// into host memory (inflate.hip).  run: member i is m[i] of comp[0, comp_bytes) and goes to dst at
+// its dst_off; the text is copied to dst only when every member is sound (*n_failed = 0).  With
+// the table null, ntc_encode_file_ex6 answers NTC_ERR_UNSUPPORTED to inflate_engine 1.
+struct Inflater;
+struct IHooks {
+    int (*create)(::ntc_ctx *ctx, Inflater **out);  // on ctx's device
+    int (*run)(Inflater *inf, const uint8_t *comp, uint64_t comp_bytes, const ::ntc_inflate_member *m, uint64_t n,
+               uint8_t *dst, uint64_t dst_bytes, uint64_t *n_failed);
+    void (*destroy)(Inflater *inf);
+};
+extern IHooks g_i_hooks;
+// what a reader did through its inflater
+struct InflateCounts {
+    uint64_t members = 0, bytes = 0;  // inflated on the device
+    uint64_t runs = 0, fallback_runs = 0;  // calls, and those that delivered nothing (a member failed)
+    double seconds = 0;  // inside the inflater
+};
+// fastx.cpp: ntc_fastx_open with an inflater (not owned) that a BGZF member reader uses from its
+// first member on; true when fx is such a reader; add its counts to *out
+int fastx_open_inflating(const char *path, Inflater *inf, ntc_fastx **out);
+bool fastx_is_bgzf(ntc_fastx *fx);
+void fastx_inflate_counts(ntc_fastx *fx, InflateCounts *out);
 // the 32-byte header in front of stream s's gzip member of member_bytes bytes (block_codec.cpp)
 void stream_header(uint8_t out[32], const ::ntc_block_meta &meta, int s, uint64_t member_bytes);
 // libdeflate.so.0 loads: what `--deflate auto` asks

@@ -81,7 +81,7 @@ bool takes_value(const std::string &o) {
     static const char *v[] = {"-o", "--output-prefix", "-k", "-p", "--prefix-precalc", "-t", "--threads", "-m",
                               "--mem-gb", "--temp-dir", "-l", "--input-list", "--builder", "--device",
                               "--index-format", "-i", "--index", "--gpus", "--devices", "--blocks-per-batch",
-                              "--deflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
+                              "--deflate", "--inflate", "--contexts-per-gpu", "--non-acgt", "--exceptions",
                               "--qualities", "--quality-file", "--quality-coder", "--quality-smooth",
                               "--quality-smooth-to", "--names", "--name-file",
                               "--digest-file", "--mate-file", "--mate-check", "--mate-out", "--reads", "--shard"};
@@ -319,6 +319,22 @@ int cmd_encode(const Args &a) {
     if (engine != "auto" && engine != "zlib" && engine != "libdeflate" && engine != "adaptive" && engine != "gpu")
         bad_args("encode: --deflate: auto, zlib, libdeflate, adaptive or gpu");
     if (engine == "auto") engine = libdeflate_present() ? "adaptive" : "zlib";
+    // ... and the engine that inflates a BGZF input: the first 18 bytes of every input decide
+    const std::string inflate = a.get("--inflate", nullptr, "host");
+    if (inflate != "host" && inflate != "gpu") bad_args("encode: --inflate: host or gpu");
+    if (inflate == "gpu") {
+        if (a.flag("--host-parse")) bad_args("encode: --inflate gpu feeds the GPU parser: not with --host-parse");
+        for (const std::string &p : {a.pos[0], mate_path}) {
+            if (p.empty()) continue;
+            unsigned char h[18] = {0};
+            FILE *f = std::fopen(p.c_str(), "rb");
+            const size_t got = f ? std::fread(h, 1, 18, f) : 0;
+            if (f) std::fclose(f);
+            if (got != 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || (h[10] | h[11] << 8) < 6 || h[12] != 'B' ||
+                h[13] != 'C' || (h[16] | h[17] << 8) + 1 < 26)
+                bad_args("encode: --inflate gpu: " + p + " does not start with a BGZF member");
+        }
+    }
     if (prefix.empty()) die("encode: -i/--index is required");
     info("Loading SBWT index...");
     ntc_index_host *ix = nullptr;
@@ -367,8 +383,13 @@ int cmd_encode(const Args &a) {
     const ntc_file_opts4 fo4{(uint32_t)sizeof(ntc_file_opts4), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd,
                              nullptr, d_fd >= 0 ? 1 : 0, d_fd, nullptr, pair_mode, mate_path.empty() ? nullptr : mate_path.c_str(), -1};
     ntc_p_stats pst{};
+    ntc_i_stats ist{};
+    const ntc_file_opts6 fo6{(uint32_t)sizeof(ntc_file_opts6), policy, nx_fd, q_mode, q_fd, nullptr, nullptr, n_mode, n_fd, nullptr,
+                             d_fd >= 0 ? 1 : 0, d_fd, nullptr, pair_mode, mate_path.empty() ? nullptr : mate_path.c_str(), -1, 0, 0,
+                             NTC_INFLATE_GPU, 0};
     std::fflush(stdout);
-    const int rc = pair_mode ? ntc_encode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &nx, &qs, &ns, &dst, &pst)
+    const int rc = inflate == "gpu" ? ntc_encode_file_ex6(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo6, &o, &st, &nx, &qs, &ns, &dst, &pst, &ist)
+                   : pair_mode ? ntc_encode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &nx, &qs, &ns, &dst, &pst)
                    : d_fd >= 0 ? ntc_encode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo3, &o, &st, &nx, &qs, &ns, &dst)
                    : n_mode > 0 ? ntc_encode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st, &nx, &qs, &ns)
                    : q_mode > 0 ? ntc_encode_file_ex(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo, &o, &st, &nx, &qs)
@@ -379,7 +400,7 @@ int cmd_encode(const Args &a) {
     if (q_fd >= 0 && ::close(q_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + q_path);
     if (n_fd >= 0 && ::close(n_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + n_path);
     if (d_fd >= 0 && ::close(d_fd) != 0 && rc == NTC_OK) die("encode: cannot write " + d_path);
-    char qjson[1536] = "";  // the quality and name files' figures, when they were written
+    char qjson[2048] = "";  // the quality and name files' figures, when they were written
     if (q_mode > 0)
         std::snprintf(qjson, 320, "\"qualities\": \"%s\", \"quality_coder\": \"%s\", \"q_sections\": %llu, "
                                   "\"q_quals\": %llu, \"q_packed_bytes\": %llu, \"q_deflated_bytes\": %llu, ",
@@ -413,6 +434,10 @@ int cmd_encode(const Args &a) {
                                                        "\"mate2_bytes\": %llu, ",
                       (unsigned long long)pst.pairs, check_name.c_str(), (unsigned long long)pst.bytes1,
                       (unsigned long long)pst.bytes2);
+    std::snprintf(qjson + std::strlen(qjson), 250, "\"inflate\": \"%s\", \"inflate_members\": %llu, \"inflate_bytes\": %llu, "
+                                                   "\"inflate_runs\": %llu, \"inflate_fallback_runs\": %llu, \"inflate_s\": %.3f, ",
+                  inflate.c_str(), (unsigned long long)ist.members, (unsigned long long)ist.bytes, (unsigned long long)ist.runs,
+                  (unsigned long long)ist.fallback_runs, ist.seconds);
     g_ctxs = ctxs;  // main frees the contexts and the host index before leaving
     g_ix = ix;
     if (rc) {
@@ -749,7 +774,7 @@ void usage(FILE *f) {
                  "                     [--quality-smooth [M]] [--quality-smooth-to C]\n"
                  "                     [--names drop|keep|id] [--name-file PATH] [--digest-file PATH]\n"
                  "                     [--deflate auto|zlib|libdeflate|adaptive|gpu] FILE > encoded.dat\n"
-                 "                     [--mate-file R2 | --interleaved] [--mate-check ids|off]\n"
+                 "                     [--mate-file R2 | --interleaved] [--mate-check ids|off] [--inflate host|gpu]\n"
                  "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH]\n"
                  "                     [--digest-file PATH] [--mate-out R2.out] [--reads A-B | --shard I/N]\n"
                  "                     FILE > out.fasta\n"
@@ -759,6 +784,9 @@ void usage(FILE *f) {
                  "  --deflate ENGINE   encode: who gzips the block streams: auto (adaptive when libdeflate.so.0 loads, else\n"
                  "                     zlib), zlib, libdeflate, adaptive, or gpu (on the GPU behind the packer: 32 KiB\n"
                  "                     chunks, greedy in-chunk matches, about 2 %% larger; the host only copies)\n"
+                 "  --inflate ENGINE   encode: who inflates a BGZF input: host (default; libdeflate on the reader's threads) or\n"
+                 "                     gpu (runs of members inflated on the first GPU; every input must be BGZF; the\n"
+                 "                     output is byte for byte the host engine's; not with --host-parse)\n"
                  "  --non-acgt POLICY  encode: reads with N or IUPAC symbols: error (default) stops at the first,\n"
                  "                     mask replaces each symbol by the substitute base (lossy), keep also writes\n"
                  "                     the replaced symbols to the --exceptions file (lossless)\n"

@@ -74,6 +74,7 @@ struct FileJob {
     bool has_policy = false;   // false (ntc_encode_file): the contexts' policy as it is, no side file
     bool may_discard = false;  // decode _ex3 / _ex4: out_fd -1 runs everything but the text's copy and write
     uint64_t read_first = 0, read_count = 0;  // decode _ex5: the range of reads, count 0 = the whole file
+    int inflate_engine = 0;                   // encode _ex6: NTC_INFLATE_*
     FileJob(ntc_ctx *const *c, int n, const char *in, int out, const ntc_pipeline_opts *o)
         : ctxs(c), n_ctx(n), in_path(in), out_fd(out), opts(o) {}
     // the fields of ntc_file_opts, ntc_file_opts2 and ntc_file_opts3 (the same names in each)
@@ -103,6 +104,7 @@ struct FileStats {
     ntc_d_stats *d = nullptr;
     ntc_p_stats *p = nullptr;
     ntc_r_stats *r = nullptr;
+    ntc_i_stats *i = nullptr;
 };
 int encode_file(const FileJob &job, const FileStats &out);
 int decode_file(const FileJob &job, const FileStats &out);
@@ -186,6 +188,7 @@ DHooks g_d_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 PHooks g_p_hooks = {nullptr, nullptr, nullptr};
 WHooks g_w_hooks = {nullptr};
 ZHooks g_z_hooks = {nullptr, nullptr};
+IHooks g_i_hooks = {nullptr, nullptr, nullptr};
 }
 
 namespace {
@@ -1272,6 +1275,12 @@ int ntc::pipe::encode_file(const FileJob &job, const FileStats &stats) {
 
     ntc_pipeline_opts o{};
     if (job.opts) o = *job.opts;
+    // NTC_INFLATE_GPU: the reader's BGZF runs go through an inflater on the first context's device
+    const ntc::IHooks &ih = ntc::g_i_hooks;
+    if (job.inflate_engine != NTC_INFLATE_HOST && job.inflate_engine != NTC_INFLATE_GPU) return NTC_ERR_INVALID_ARG;
+    const bool gpu_inflate = job.inflate_engine == NTC_INFLATE_GPU;
+    if (gpu_inflate && o.host_parse) return NTC_ERR_INVALID_ARG;
+    if (gpu_inflate && (!ih.create || !ih.run || !ih.destroy)) return NTC_ERR_UNSUPPORTED;
     // NTC_DEFLATE_GPU: the contexts deflate behind their packer ("gpu_deflate"); the side sections stay
     // with the pool, under the engine `--deflate auto` stands for
     const ntc::ZHooks &zh = ntc::g_z_hooks;
@@ -1295,18 +1304,46 @@ int ntc::pipe::encode_file(const FileJob &job, const FileStats &stats) {
     E.etrace_n = etr ? (uint64_t)std::atoll(etr) : 0;
 
     ntc_fastx *&fx = E.fx, *&fx2 = E.fx2;
-    int rc = ntc_fastx_open(job.in_path, &fx);
-    if (rc) return rc;
+    // `--inflate gpu`: one inflater, made before the inputs are opened so that their readers use it
+    // from the first member on
+    ntc::Inflater *inflater = nullptr;
+    if (gpu_inflate)
+        if (const int irc = ih.create(ctxs[0], &inflater)) return irc;
+    const auto open_input = [&](const char *path, ntc_fastx **out) {
+        return inflater ? ntc::fastx_open_inflating(path, inflater, out) : ntc_fastx_open(path, out);
+    };
+    int rc = open_input(job.in_path, &fx);
+    if (rc) {
+        if (inflater) ih.destroy(inflater);
+        return rc;
+    }
     ntc_fastx_set_threads(fx, T);
     E.text = o.host_parse ? nullptr : ntc::fastx_mapped(fx, &E.text_n);
     // the mate-2 input goes through the same ingest; the two decoders share the thread budget
     if (fo.mate_path) {
-        if ((rc = ntc_fastx_open(fo.mate_path, &fx2))) {
+        if ((rc = open_input(fo.mate_path, &fx2))) {
             ntc_fastx_close(fx);
+            if (inflater) ih.destroy(inflater);
             return rc;
         }
         ntc_fastx_set_threads(fx, std::max(1, T / 2));
         ntc_fastx_set_threads(fx2, std::max(1, T / 2));
+    }
+    // ... and every input must be BGZF, read member by member
+    if (gpu_inflate) {
+        const char *not_bgzf = !ntc::fastx_is_bgzf(fx) ? job.in_path : fx2 && !ntc::fastx_is_bgzf(fx2) ? fo.mate_path : nullptr;
+        if (not_bgzf) {
+            ntc_fastx_close(fx);
+            if (fx2) ntc_fastx_close(fx2);
+            ih.destroy(inflater);
+            if (stats.pipe) {
+                *stats.pipe = ntc_pipeline_stats{};
+                stats.pipe->bad_read = -1;
+                std::snprintf(stats.pipe->error, sizeof(stats.pipe->error), "inflate gpu: %s does not start with a BGZF member",
+                              not_bgzf);
+            }
+            return NTC_ERR_UNSUPPORTED;
+        }
     }
 
     // pinned ring: the GPU threads hold at most n_ctx buffers, the reader fills one more.
@@ -1323,6 +1360,7 @@ int ntc::pipe::encode_file(const FileJob &job, const FileStats &stats) {
             for (auto &x : ring) pinned_free(x.offs);
             ntc_fastx_close(fx);
             if (fx2) ntc_fastx_close(fx2);
+            if (inflater) ih.destroy(inflater);
             return NTC_ERR_HIP;
         }
     }
@@ -1379,8 +1417,18 @@ int ntc::pipe::encode_file(const FileJob &job, const FileStats &stats) {
         pinned_free(b.text);
     }
     E.etrace("buffers freed", 0);
+    ntc::InflateCounts ic;
+    ntc::fastx_inflate_counts(fx, &ic);
+    if (fx2) ntc::fastx_inflate_counts(fx2, &ic);
     ntc_fastx_close(fx);
     if (fx2) ntc_fastx_close(fx2);
+    if (inflater) ih.destroy(inflater);
+    if (stats.i) {
+        *stats.i = ntc_i_stats{};
+        stats.i->engine = (uint32_t)job.inflate_engine;
+        stats.i->members = ic.members, stats.i->bytes = ic.bytes, stats.i->runs = ic.runs, stats.i->fallback_runs = ic.fallback_runs;
+        stats.i->seconds = ic.seconds;
+    }
     E.etrace("input closed", 0);
     const int result = sh.error == -1 ? NTC_OK : sh.error;
     S.alloc_s += E.t_pin.load();
@@ -1459,6 +1507,19 @@ int ntc_encode_file_ex4(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
     job.fo = *fo;
     job.has_policy = true;
     return encode_file(job, {stats, nx, q, n, d, p});
+}
+
+int ntc_encode_file_ex6(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts6 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
+                        ntc_n_stats *n, ntc_d_stats *d, ntc_p_stats *p, ntc_i_stats *i) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts6) || fo->nx_policy < 0 || fo->reserved) return NTC_ERR_INVALID_ARG;
+    FileJob job(ctxs, n_ctx, in_path, out_fd, opts);
+    job.take_ex3(*fo);
+    job.fo.pair_mode = fo->pair_mode, job.fo.mate_path = fo->mate_path, job.fo.out_fd2 = fo->out_fd2;
+    job.inflate_engine = fo->inflate_engine;
+    FileStats out{stats, nx, q, n, d, p};
+    out.i = i;
+    return encode_file(job, out);
 }
 
 }  // extern "C"
