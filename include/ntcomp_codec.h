@@ -192,6 +192,59 @@ int ntc_inflate_members(ntc_ctx *ctx, const uint8_t *comp, uint64_t comp_bytes, 
 int ntc_inflate_members_device(ntc_ctx *ctx, const void *d_comp, uint64_t comp_bytes, const ntc_inflate_member *m,
                                uint64_t n, void *d_dst, uint64_t dst_cap, ntc_inflate_result *res, uint64_t *n_failed);
 
+/* ---- BGZF members of a text, made on the GPU ---------------------------------------------- */
+/* A text of n bytes becomes BGZF members: gzip members with the 'B' 'C' extra field, each of at
+ * most 65,280 bytes of text (NTC_BGZF_MEMBER) and at most 65,316 bytes itself, independent of
+ * one another, so that bgzip, gzip and zlib read their concatenation.
+ *   rec_off == NULL  the members are the consecutive 65,280-byte slices of the text.
+ *   rec_off          n_rec + 1 non-decreasing offsets, rec_off[0] = 0, rec_off[n_rec] = n (else
+ *                    NTC_ERR_INVALID_ARG).  cut_j is the largest offset <= 61,440 j (NTC_BGZF_GRID);
+ *                    the bytes between two cuts are one member, or when they pass 65,280,
+ *                    slices of 65,280.  Every member then starts and ends on a record boundary
+ *                    unless a record is longer than 3,841 bytes.
+ * A member is coded as two chunks (32,768 bytes, then the rest) by the coder of `--deflate gpu`
+ * (ntc_deflate_stream, engine NTC_DEFLATE_GPU), so it is at most its text + 36 bytes.
+ * ntc_bgzf_bound(n) = n + 36 (ceil(n / 61,440) + floor(n / 65,280)): the most bytes the rule can
+ * make of n bytes whatever the offsets.  out_cap below it is NTC_ERR_CAPACITY with *out_bytes =
+ * the bound, before anything is launched.  No EOF member (NTC_BGZF_EOF) is appended.
+ * members (may be NULL): the table, entry i = member i's text offset, text bytes, place in out
+ * and bytes there; *n_members = their number; NTC_ERR_CAPACITY when members_cap is smaller.
+ *   ntc_bgzf_compress         host to host through the GPU (bgzf.hip); with ctx == NULL the host
+ *                             restatement, the same rule and coder run by one lane: same bytes.
+ *   ntc_bgzf_compress_device  d_text, d_rec_off and d_out are device buffers.
+ * Both are synchronous; n < 4 GiB per call.
+ * ntc_ctx_set_option(ctx, "bgzf_text", 1) (default 0: nothing new is launched, no byte or copy
+ * changes) makes ntc_decode_fasta and ntc_decode_fasta_unpacked plan and code the formatted text
+ * on the device, its records being the offsets: out then gets the members alone and *out_len
+ * their bytes; the capacity to offer (and what a size query answers) is ntc_bgzf_bound(text
+ * bytes) + 72.  Under "paired" each of the two parts is planned on its own and
+ * ntc_decode_pair_split gives the bytes of part 1's members; a window (ntc_decode_set_window)
+ * gives the members of the window's text; "discard_text" wins: nothing is compressed.
+ * "bgzf_workgroups" (default 0: two per compute unit): the workgroups that share the chunks of
+ * a call, a test hook.
+ * ntc_bgzf_last: what the context's last call that made members left -- either call above, or
+ * a text decode under "bgzf_text" -- as counts and, when members is not NULL, its table (for a
+ * paired decode both parts', places as in `out`).                                              */
+#define NTC_BGZF_MEMBER 65280
+#define NTC_BGZF_GRID 61440
+#define NTC_BGZF_EOF "\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00\x42\x43\x02\x00\x1b\x00\x03\x00\x00\x00\x00\x00\x00\x00\x00\x00"
+#define NTC_BGZF_EOF_BYTES 28
+typedef struct ntc_bgzf_member {
+    uint64_t text_off, text_bytes, place, bytes;
+} ntc_bgzf_member; /* 32 bytes */
+typedef struct ntc_bgzf_counts {
+    uint64_t members, text_bytes, bytes;
+    uint64_t chunks_stored, chunks_huffman, chunks_matches; /* the chunks by the encoding chosen */
+    double seconds; /* inside the plan, the coder and the members' copy, waiting included */
+} ntc_bgzf_counts;
+uint64_t ntc_bgzf_bound(uint64_t n);
+int ntc_bgzf_compress(ntc_ctx *ctx, const uint8_t *text, uint64_t n, const uint64_t *rec_off, uint64_t n_rec, uint8_t *out,
+                      uint64_t out_cap, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members, uint64_t *out_bytes);
+int ntc_bgzf_compress_device(ntc_ctx *ctx, const void *d_text, uint64_t n, const uint64_t *d_rec_off, uint64_t n_rec, void *d_out,
+                             uint64_t out_cap, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members,
+                             uint64_t *out_bytes);
+int ntc_bgzf_last(ntc_ctx *ctx, ntc_bgzf_counts *counts, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members);
+
 /* ---- GPU unpacker (the inverse of the packer) ------------------------------------------ */
 /* decode_block (src/lib.rs:320-368) split at inflate.  ntc_read_block_streams (host): one
  * block's four stream headers at data[0..len) and their gzip members inflated into

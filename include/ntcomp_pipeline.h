@@ -424,6 +424,67 @@ int ntc_encode_file_ex6(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
                         const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_nx_stats *nx, ntc_q_stats *q,
                         ntc_n_stats *n, ntc_d_stats *d, ntc_p_stats *p, ntc_i_stats *i);
 
+/* ---- decoded text written as BGZF, compressed on the GPU ------------------------------------ */
+/* ntc_decode_file_ex7 is ntc_decode_file_ex5 with the output's format.  ntc_file_opts7 holds
+ * ntc_file_opts6's fields in the same order (inflate_engine is not read here), then its own;
+ * struct_bytes must be at least sizeof(ntc_file_opts7).
+ *   NTC_OUT_TEXT (0)  as ever: the text.
+ *   NTC_OUT_BGZF (1)  every batch's text is cut into BGZF members at record boundaries and
+ *                     compressed on the device that formatted it (the context option "bgzf_text",
+ *                     ntc_bgzf_compress's plan and coder); only the members
+ *                     cross to the host.  They are written in batch order, and the 28-byte EOF
+ *                     member (NTC_BGZF_EOF) is appended only when the call returns NTC_OK: a
+ *                     decode that fails -- a digest mismatch, a damaged block under a range --
+ *                     leaves a file without the marker, which is how BGZF tools tell a truncated
+ *                     file.  Under pairs out_fd and out_fd2 are each a BGZF file of their own.
+ *                     Members never span a batch, so for a given blocks_per_batch the bytes do
+ *                     not depend on the contexts or threads; across batch sizes only the inflated
+ *                     text is the same.  The outputs of ranges that partition the archive,
+ *                     concatenated, are a BGZF file of the whole text (an EOF member in the middle
+ *                     is an empty member).  out_fd -1 wins: nothing is compressed.
+ * NTC_ERR_UNSUPPORTED for NTC_OUT_BGZF when the GPU stage's hook table is null (a build without
+ * it); any other format, or a non-zero reserved2, is NTC_ERR_INVALID_ARG.
+ * z (may be NULL): the format, the members written (the EOF members not counted), their text and
+ * bytes, the chunks by the encoding chosen, and the seconds the contexts spent making them.      */
+#define NTC_OUT_TEXT 0
+#define NTC_OUT_BGZF 1
+typedef struct ntc_file_opts7 {
+    uint32_t struct_bytes; /* sizeof(ntc_file_opts7)                           */
+    int32_t nx_policy;     /* NTC_NX_*                                         */
+    int32_t nx_fd;         /* encode: exceptions file, -1 = none               */
+    int32_t q_mode;        /* 0 drop, 1 keep, 2 bin8                           */
+    int32_t q_fd;          /* encode: quality file, -1 = none                  */
+    const char *nx_path;   /* decode: exceptions file, NULL = none             */
+    const char *q_path;    /* decode: quality file, NULL = none                */
+    int32_t n_mode;        /* 0 drop, 1 keep, 2 id                             */
+    int32_t n_fd;          /* encode: name file, -1 = none                     */
+    const char *n_path;    /* decode: name file, NULL = none                   */
+    int32_t d_mode;        /* encode: 0 off, 1 digests                         */
+    int32_t d_fd;          /* encode: digest file, -1 = none                   */
+    const char *d_path;    /* decode: digest file, NULL = none                 */
+    int32_t pair_mode;     /* 0 off, 1 pairs + mate check, 2 pairs, no check   */
+    const char *mate_path; /* encode: the mate-2 input, NULL = in_path is interleaved */
+    int32_t out_fd2;       /* decode: the mate-2 text, -1 = none               */
+    uint64_t read_first;   /* decode: the range's first read, from 0           */
+    uint64_t read_count;   /* decode: its reads, 0 = the whole file            */
+    int32_t inflate_engine; /* encode: NTC_INFLATE_*                           */
+    int32_t reserved;      /* 0                                                */
+    int32_t out_format;    /* decode: NTC_OUT_*                                */
+    int32_t reserved2;     /* 0                                                */
+} ntc_file_opts7;
+typedef struct ntc_z_stats {
+    uint32_t out_format;   /* the out_format of the call                       */
+    uint32_t reserved;
+    uint64_t members;      /* BGZF members written, the EOF members not counted */
+    uint64_t text_bytes;   /* the text they hold                               */
+    uint64_t bytes;        /* their bytes                                      */
+    uint64_t chunks_stored, chunks_huffman, chunks_matches; /* by the encoding chosen */
+    double seconds;        /* the contexts' time in the plan, the coder and the members' copy */
+} ntc_z_stats;
+int ntc_decode_file_ex7(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts7 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p,
+                        ntc_r_stats *r, ntc_z_stats *z);
+
 #ifdef __cplusplus
 }
 #endif

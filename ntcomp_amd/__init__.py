@@ -59,6 +59,7 @@ EXPORTED = [
     "ntc_d_write_section", "ntc_d_read", "ntc_encode_file_ex3", "ntc_decode_file_ex3",
     "ntc_encode_pack_fastq_paired", "ntc_decode_pair_split", "ntc_encode_file_ex4", "ntc_decode_file_ex4",
     "ntc_decode_set_window", "ntc_decode_file_ex5", "ntc_archive_info", "ntc_encode_file_ex6",
+    "ntc_bgzf_bound", "ntc_bgzf_compress", "ntc_bgzf_compress_device", "ntc_bgzf_last", "ntc_decode_file_ex7",
 ]
 
 # non-ACGT policies (ctx option "non_acgt", include/ntcomp_gpu.h) and the twelve symbols they cover
@@ -264,6 +265,25 @@ class IStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class FileOpts7(ctypes.Structure):
+    """ntc_file_opts7 (include/ntcomp_pipeline.h): ntc_file_opts6 and the format of the decoded output."""
+    _fields_ = FileOpts6._fields_ + [("out_format", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+
+
+# the format of decode's output (ntc_file_opts7.out_format)
+OUT_FORMATS = {"text": 0, "bgzf": 1}
+
+
+class ZStats(ctypes.Structure):
+    """ntc_z_stats (include/ntcomp_pipeline.h)."""
+    _fields_ = [("out_format", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] + \
+               [(n, ctypes.c_uint64) for n in ("members", "text_bytes", "bytes", "chunks_stored", "chunks_huffman",
+                                               "chunks_matches")] + [("seconds", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (float(self.seconds) if k == "seconds" else int(getattr(self, k))) for k, _ in self._fields_ if k != "reserved"}
+
+
 class RStats(ctypes.Structure):
     """ntc_r_stats (include/ntcomp_pipeline.h)."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("blocks_total", "reads_total", "first_block", "blocks_read",
@@ -424,6 +444,10 @@ def lib():
         "ntc_encode_members": (I, [P, P, u64, ctypes.POINTER(u64)]),
         "ntc_inflate_members": (I, [P, P, u64, P, u64, P, u64, P, ctypes.POINTER(u64)]),
         "ntc_inflate_members_device": (I, [P, P, u64, P, u64, P, u64, P, ctypes.POINTER(u64)]),
+        "ntc_bgzf_bound": (u64, [u64]),
+        "ntc_bgzf_compress": (I, [P, P, u64, P, u64, P, u64, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "ntc_bgzf_compress_device": (I, [P, P, u64, P, u64, P, u64, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "ntc_bgzf_last": (I, [P, P, P, u64, ctypes.POINTER(u64)]),
         "ntc_encode_pack_batch": (I, [P, P, P, u64, u32, P, ctypes.POINTER(P), ctypes.POINTER(u64),
                                       ctypes.POINTER(i64)]),
         "ntc_fastq_parse": (I, [P, P, u64, u64, P, u64, P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int64)]),
@@ -492,6 +516,9 @@ def lib():
         "ntc_decode_file_ex5": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts5), ctypes.POINTER(PipelineOpts),
                                     ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats),
                                     ctypes.POINTER(RStats)]),
+        "ntc_decode_file_ex7": (I, [P, I, ctypes.c_char_p, I, ctypes.POINTER(FileOpts7), ctypes.POINTER(PipelineOpts),
+                                    ctypes.POINTER(PipelineStats), ctypes.POINTER(DStats), ctypes.POINTER(PStats),
+                                    ctypes.POINTER(RStats), ctypes.POINTER(ZStats)]),
         "ntc_decode_set_window": (I, [P, u64, u64]),
         "ntc_archive_info": (I, [ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64)]),
@@ -1002,6 +1029,44 @@ class GpuContext:
                     "ntc_inflate_members_device")
         return res
 
+    def bgzf_compress_device(self, d_text, n, d_out, cap, d_rec_off=0, n_rec=0):
+        """The BGZF members of the n bytes at d_text, made on the GPU into d_out
+        (ntc_bgzf_compress_device); d_rec_off (0: plain cuts): n_rec + 1 uint64 record offsets on the
+        device -> (a BGZF_MEMBER array, bytes used).  NtcError(NTC_ERR_CAPACITY) carries .needed."""
+        tab = np.zeros(max(1, bgzf_members_max(n)), dtype=BGZF_MEMBER)
+        nm, used = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.L.ntc_bgzf_compress_device(self.h, ctypes.c_void_p(d_text), n, ctypes.c_void_p(d_rec_off) if d_rec_off else None,
+                                             n_rec, ctypes.c_void_p(d_out), cap, _p(tab), len(tab), ctypes.byref(nm),
+                                             ctypes.byref(used))
+        if rc:
+            e = NtcError(rc, self.L.ntc_last_error(self.h).decode(errors="replace"))
+            e.needed = int(used.value)
+            raise e
+        return tab[:nm.value].copy(), int(used.value)
+
+    @property
+    def bgzf_text(self):
+        """Whether the text decode calls leave BGZF members in place of their text (ctx option "bgzf_text")."""
+        return bool(self.get_option("bgzf_text"))
+
+    @bgzf_text.setter
+    def bgzf_text(self, on):
+        self.set_option("bgzf_text", 1 if on else 0)
+
+    def bgzf_last(self):
+        """What the last call that made BGZF members left (ntc_bgzf_last): bgzf_compress with this
+        context, bgzf_compress_device, or a text decode under bgzf_text -> (dict of members, text_bytes,
+        bytes, chunks_stored, chunks_huffman, chunks_matches; a BGZF_MEMBER array)."""
+        c = np.zeros(7, dtype=np.uint64)  # ntc_bgzf_counts: six counts, then the seconds as a double
+        nm = ctypes.c_uint64()
+        self._check(self.L.ntc_bgzf_last(self.h, _p(c), None, 0, ctypes.byref(nm)), "ntc_bgzf_last")
+        tab = np.zeros(max(1, nm.value), dtype=BGZF_MEMBER)
+        self._check(self.L.ntc_bgzf_last(self.h, _p(c), _p(tab), len(tab), ctypes.byref(nm)), "ntc_bgzf_last")
+        keys = ("members", "text_bytes", "bytes", "chunks_stored", "chunks_huffman", "chunks_matches")
+        counts = dict(zip(keys, (int(v) for v in c[:6])))
+        counts["seconds"] = float(c[6:].view(np.float64)[0])
+        return counts, tab[:nm.value].copy()
+
     def encode_members(self):
         """Where the members lie in the payload of the last encode_pack* call under option
         "gpu_deflate" (ntc_encode_members) -> uint64 array [blocks, 4, 2] of (offset, bytes)."""
@@ -1194,7 +1259,17 @@ class GpuContext:
         self._check(self.L.ntc_unpacked_records(self.h, _p(out), len(out), ctypes.byref(n)), "ntc_unpacked_records")
         return out[:n.value]
 
-    def decode_fasta_unpacked(self, first_id=1):
+    def decode_fasta_unpacked(self, first_id=1, bgzf=None):
+        """The text of the records the last unpack left (ntc_decode_fasta_unpacked); paired: its two
+        parts.  bgzf (None: as the context's bgzf_text stands): True for BGZF members in place of the
+        text, for this call; bgzf_last() then has their table."""
+        if bgzf is not None and bool(bgzf) != self.bgzf_text:
+            was = self.bgzf_text
+            self.bgzf_text = bgzf
+            try:
+                return self.decode_fasta_unpacked(first_id)
+            finally:
+                self.bgzf_text = was
         need = ctypes.c_uint64()
         rc = self.L.ntc_decode_fasta_unpacked(self.h, first_id, None, 0, ctypes.byref(need))
         if rc not in (0, 5):
@@ -1396,6 +1471,48 @@ def bgzf_members(blob):
     return out
 
 
+# ---- BGZF members of a text (ntc_bgzf_compress, include/ntcomp_codec.h) ----
+BGZF_MEMBER_BYTES = 65280  # text bytes per member at most
+BGZF_GRID = 61440          # grid step of the record-aligned cuts
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+BGZF_MEMBER = np.dtype([("text_off", "<u8"), ("text_bytes", "<u8"), ("place", "<u8"), ("bytes", "<u8")])
+
+
+def bgzf_members_max(n):
+    """The most members the plan makes of n bytes, whatever the record offsets."""
+    return -(-n // BGZF_GRID) + n // BGZF_MEMBER_BYTES
+
+
+def bgzf_bound(n):
+    """ntc_bgzf_bound: the most bytes the members of an n-byte text take."""
+    return int(lib().ntc_bgzf_bound(n))
+
+
+def bgzf_compress(text, rec_off=None, ctx=None, cap=None):
+    """The BGZF members of text (ntc_bgzf_compress): on ctx's GPU, or with ctx None through the
+    host restatement, same bytes.  rec_off (None: plain 65,280-byte cuts): the records' offsets,
+    first 0 and last len(text); the members then end on record boundaries.  No EOF member is
+    appended (BGZF_EOF).  Returns (the members' bytes, a BGZF_MEMBER array).  cap: the output
+    capacity to offer (default: the bound); NtcError(NTC_ERR_CAPACITY) carries .needed."""
+    n = len(text)
+    src = np.frombuffer(bytes(text), dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+    off = None if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
+    if off is not None and len(off) == 0:
+        raise ValueError("rec_off holds at least one offset")
+    cap = bgzf_bound(n) if cap is None else cap
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    tab = np.zeros(max(1, bgzf_members_max(n)), dtype=BGZF_MEMBER)
+    nm, used = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = lib().ntc_bgzf_compress(ctx.h if ctx is not None else None, _p(src), n, None if off is None else _p(off),
+                                 0 if off is None else len(off) - 1, _p(out), cap, _p(tab), len(tab), ctypes.byref(nm),
+                                 ctypes.byref(used))
+    if rc:
+        e = NtcError(rc, lib().ntc_last_error(ctx.h).decode(errors="replace") if ctx is not None else "ntc_bgzf_compress")
+        e.needed = int(used.value)
+        raise e
+    return out[:used.value].tobytes(), tab[:nm.value].copy()
+
+
 def _inflate_descs(members):
     if isinstance(members, np.ndarray) and members.dtype == INFLATE_MEMBER:
         return np.ascontiguousarray(members)
@@ -1539,7 +1656,7 @@ def encode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=4, batch_base
 
 
 def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=None, q_path=None, n_path=None,
-                d_path=None, out_fd2=-1, pair_mode=None, reads=None):
+                d_path=None, out_fd2=-1, pair_mode=None, reads=None, out_format="text"):
     """`ntcomp decode` file to file (ntc_decode_file, include/ntcomp_pipeline.h): encoded.dat
     -> inflate + stream decode pool -> GPU inverse-SBWT walk + FASTA formatting on every
     context -> FASTA on out_fd.  Stats as a dict; a damaged block ends the output after the
@@ -1561,9 +1678,26 @@ def decode_file(ctxs, in_path, out_fd, threads=0, blocks_per_batch=2, nx_path=No
     reads keep their numbers, names and qualities, and the stats gain an "r" dict (ntc_r_stats).
     A range is strict: a damaged block at or before it, or a side file that does not describe the
     archive's blocks, is NTC_ERR_FORMAT; a range the archive does not hold is
-    NTC_ERR_INVALID_ARG."""
+    NTC_ERR_INVALID_ARG.  out_format "bgzf" (ntc_decode_file_ex7): every batch's text is cut into
+    BGZF members at record boundaries and compressed on the GPU; out_fd (and out_fd2) get the
+    members and, when the call succeeds, the EOF member; the stats gain a "z" dict (ntc_z_stats)."""
     o = PipelineOpts(threads, blocks_per_batch, 0, 0, 0)
     pairs = _pair_code(pair_mode) if pair_mode is not None else 0
+    if OUT_FORMATS[out_format]:
+        enc = lambda p: None if p is None else os.fsencode(p)
+        first, count = (int(x) for x in reads) if reads is not None else (0, 0)
+        fo = FileOpts7(ctypes.sizeof(FileOpts7), 0, -1, 0, -1, enc(nx_path), enc(q_path), 0, -1, enc(n_path), 0, -1, enc(d_path),
+                       pairs, None, out_fd2, first, count, 0, 0, OUT_FORMATS[out_format], 0)
+        side = [("d", DStats()), ("p", PStats()), ("r", RStats()), ("z", ZStats())]
+        try:
+            d = _run_pipeline("ntc_decode_file_ex7", ctxs, in_path, out_fd, o, mid=(ctypes.byref(fo),),
+                              tail=tuple(ctypes.byref(s) for _, s in side))
+        except NtcError as e:
+            e.stats["d"] = side[0][1].as_dict()
+            raise
+        asked = {"d": d_path is not None, "p": bool(pairs), "r": reads is not None, "z": True}
+        d.update({key: _stats_dict(s) for key, s in side if asked[key]})
+        return d
     level = 5 if reads is not None else 4 if pairs else 3 if d_path is not None else 2 if n_path is not None else 1 if q_path is not None else 0
     if level == 0:
         if nx_path is None:

@@ -462,6 +462,9 @@ def cmd_decode(args, verify=False):
     GPU, ">seq.N" text written in file order.  verify: the same with every block checked against
     the --digest-file and no text copied off the device or written; one line on stdout."""
     command = "verify" if verify else "decode"
+    bgzf = bool(getattr(args, "bgzf", False))
+    if verify and bgzf:
+        _bad_args("verify: writes no text: not with --bgzf")
     _check_d_args(args, command, (args.exceptions, args.quality_file, args.name_file, args.input_path))
     asked = _check_r_args(args, command)
     import ntcomp_amd as nt
@@ -472,6 +475,12 @@ def cmd_decode(args, verify=False):
         if placed is None:  # an empty slice: nothing to write
             if verify:
                 print(f"verify: OK: 0 blocks of the archive's, 0 reads (--shard {args.shard} is empty)", flush=True)
+            if bgzf:  # an empty BGZF file is its EOF member
+                sys.stdout.buffer.write(nt.BGZF_EOF)
+                sys.stdout.buffer.flush()
+                if getattr(args, "mate_out", None) is not None:
+                    with open(args.mate_out, "wb") as f:
+                        f.write(nt.BGZF_EOF)
             st.report(command=command, reads=0, blocks=0)
             return
         r_args = dict(reads=placed)
@@ -487,6 +496,8 @@ def cmd_decode(args, verify=False):
         except OSError:
             raise SystemExit(f"ntcomp: decode: cannot write {args.mate_out}")
     p_args = dict(out_fd2=mate_out.fileno(), pair_mode="nocheck") if mate_out else {}
+    if bgzf:  # the text as BGZF members, compressed on the GPU that formatted it
+        p_args["out_format"] = "bgzf"
     try:
         res = st.wrap("pipeline", nt.decode_file)(ctxs, args.input_path, -1 if verify else out.fileno(),
                                                   threads=args.threads, blocks_per_batch=args.blocks_per_batch,
@@ -519,7 +530,15 @@ def cmd_decode(args, verify=False):
                   "d_not_checkable": _component_names(res["d"]["not_checkable"])} if "d" in res else {}),
               **({"pairs": res["p"]["pairs"], "mate1_bytes": res["p"]["bytes1"], "mate2_bytes": res["p"]["bytes2"]}
                  if "p" in res else {}),
-              **({"r_" + k: v for k, v in res["r"].items()} if "r" in res else {}))
+              **({"r_" + k: v for k, v in res["r"].items()} if "r" in res else {}),
+              **({} if verify else _bgzf_stats(bgzf, res.get("z", {}))))
+
+
+def _bgzf_stats(on, z):
+    """the --stats fields of decode --bgzf (ntc_z_stats); zeros without the flag"""
+    return dict(bgzf=on, bgzf_members=z.get("members", 0), bgzf_text_bytes=z.get("text_bytes", 0), bgzf_bytes=z.get("bytes", 0),
+                bgzf_chunks_stored=z.get("chunks_stored", 0), bgzf_chunks_huffman=z.get("chunks_huffman", 0),
+                bgzf_chunks_matches=z.get("chunks_matches", 0), bgzf_s=round(z.get("seconds", 0.0), 3))
 
 
 def cmd_info(args):
@@ -657,6 +676,10 @@ def main(argv=None):
               "Only the blocks that hold them are read; the reads keep their numbers, names and qualities")
     s_help = ("only the I-th of N contiguous slices of whole blocks; the N outputs concatenated in order are the full "
               "decode (one process per GPU or node)")
+    d.add_argument("--bgzf", action="store_true",
+                   help="write the text as BGZF (.gz: bgzip's blocked gzip), cut at record boundaries and compressed on the "
+                        "GPU; with --mate-out both outputs.  The EOF member is written only when the decode succeeds; the "
+                        "--shard outputs concatenated are one BGZF file")
     d.add_argument("--reads", metavar="A-B", help=r_help)
     d.add_argument("--shard", metavar="I/N", help=s_help)
     v = sub.add_parser("verify", help="Check encoded data against its digest file without writing the text")
@@ -673,6 +696,7 @@ def main(argv=None):
     v.add_argument("--quality-file", metavar="PATH", help="the side file of encode --qualities keep or bin8")
     v.add_argument("--name-file", metavar="PATH", help="the side file of encode --names keep or id")
     v.add_argument("--exceptions", metavar="PATH", help="the side file of encode --non-acgt keep")
+    v.add_argument("--bgzf", action="store_true", help=argparse.SUPPRESS)  # (refused: verify writes no text)
     v.add_argument("--reads", metavar="A-B", help=r_help + "; the touched blocks are checked whole")
     v.add_argument("--shard", metavar="I/N", help=s_help)
     n = sub.add_parser("info", help="What an encoded file holds, from its block headers (no index, no GPU)")

@@ -25,6 +25,7 @@
 #include "qsmooth_core.h"
 #include "names_core.h"
 #include "digest_core.h"
+#include "bgzf_core.h"
 #include "deflate_core.h"
 #include "inflate_core.h"
 #include "pair_core.h"
@@ -59,7 +60,8 @@ enum WsSlot {
     WS_DG_TABLE, WS_DGD_IN,
     WS_PAIR_IN, WS_PAIR_TAB, WS_PAIR_ST, WS_PAIR_SCAN, WS_PAIR_OUT,
     WS_DF_DESC, WS_DF_TOKENS, WS_DF_STAGE, WS_DF_RES, WS_DF_OUT,
-    WS_INF_COMP, WS_INF_DESC, WS_INF_DST, WS_INF_RES, WS_COUNT
+    WS_INF_COMP, WS_INF_DESC, WS_INF_DST, WS_INF_RES,
+    WS_BZ_PLAN, WS_BZ_TOKENS, WS_BZ_STAGE, WS_BZ_TEXT, WS_BZ_OFF, WS_BZ_OUT, WS_COUNT
 };
 
 // The device index of one upload: freed with the last context that holds it
@@ -169,6 +171,22 @@ struct DeflateState {
     void begin() { members.clear(); }   // an encode call starts: the last call's members are gone
 };
 
+// BGZF output (bgzf.hip): the options "bgzf_text" (a text decode call leaves BGZF members in
+// place of its text) and "bgzf_workgroups" (k_bgzf_chunks' grid, 0: two per CU); the member
+// table and the counts of the last call that made members (ntc_bgzf_last)
+struct BgzfState {
+    int opt = 0;
+    int workgroups = 0;
+    std::vector<BgzfMember> members;
+    uint64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};  // members, chunks, text bytes, bytes, chunks stored / Huffman / with matches
+    double seconds = 0;  // inside the plan, the coder and the members' copy
+    void begin() {
+        members.clear();
+        for (uint64_t &c : counts) c = 0;
+        seconds = 0;
+    }
+};
+
 // the text window of the next ntc_decode_fasta / _unpacked (ntc_decode_set_window): pending
 // like the side data above, gone after that call whether it succeeds or fails
 struct WindowState {
@@ -251,6 +269,7 @@ struct ntc_ctx {
     PairState pair;
     WindowState win;
     DeflateState df;
+    BgzfState bz;
     int discard_text = 0;  // option "discard_text": a FASTA decode call formats its text and leaves it on the device
     FastqArgs fq_last{};              // the last GPU FASTQ parse (run again when the run list was short)
     hipEvent_t pack_ev[3] = {nullptr, nullptr, nullptr};
@@ -2001,6 +2020,8 @@ const Option kOptions[] = {
     {"paired", 0, 2, kInRange, "paired must be 0 (off), 1 (ids) or 2 (no check)", OPT_VALUE(pair.mode)},
     {"digests", 0, 1, kInRange, "digests must be 0 or 1", OPT_VALUE(dig.opt)},
     {"gpu_deflate", 0, 1, kInRange, "gpu_deflate must be 0 or 1", OPT_VALUE(df.opt)},
+    {"bgzf_text", 0, 1, kInRange, "bgzf_text must be 0 or 1", OPT_VALUE(bz.opt)},
+    {"bgzf_workgroups", 0, 65536, kInRange, "bgzf_workgroups must be 0 (two per CU) or 1..65536", OPT_VALUE(bz.workgroups)},
     {"non_acgt", 0, 2, kInRange, "non_acgt must be 0 (error), 1 (mask) or 2 (keep)", OPT_VALUE(nx.policy)},
     // what the last upload and the last calls left
     {"subst_hash", 0, 0, kInRange, nullptr, nullptr, get_subst_hash},
@@ -2610,6 +2631,176 @@ int ntc_inflate_members_device(ntc_ctx *ctx, const void *d_comp, uint64_t comp_b
 
 }  // extern "C"
 
+// ---- BGZF members of a text (bgzf.hip, bgzf_core.h) ---------------------------------------------
+namespace {
+static_assert(sizeof(ntc_bgzf_member) == sizeof(BgzfMember) && offsetof(ntc_bgzf_member, place) == offsetof(BgzfMember, place),
+              "ntc_bgzf_member is the kernel's member table entry");
+
+// The members of the n bytes at d_text into d_out (room for bgzf_bound(n) bytes), all device
+// memory.  d_off (null: plain cuts): n_rec + 1 offsets, d_off[r] - off_base being record r's
+// start.  The table is appended to tab with the places moved by place_base, the counts are added
+// to counts.  One wait between the plan and the coder (the chunk count), one at the end.
+int bgzf_dev(ntc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint64_t *d_off, uint64_t n_rec, uint64_t off_base,
+             uint8_t *d_out, uint64_t place_base, std::vector<BgzfMember> &tab, uint64_t counts[7]) {
+    if (n == 0) return NTC_OK;
+    if (n >> 32) return set_err(ctx, NTC_ERR_CAPACITY, "4 GiB of text or more in one BGZF call: split the batch");
+    const uint64_t C = bgzf_cells(n, d_off != nullptr), M = bgzf_members_max(n), N = M * kBgzfMemberChunks;
+    const uint32_t wgs = ctx->bz.workgroups ? (uint32_t)ctx->bz.workgroups : (uint32_t)std::max(1, 2 * ctx->num_cus);
+    const auto up = [](uint64_t b) { return (b + 15) & ~15ull; };
+    const uint64_t b_cuts = up((C + 1) * 8), b_members = up(M * sizeof(BgzfMember)), b_m32 = up(M * 4),
+                   b_chunks = up(N * sizeof(DfChunkDesc)), b_res = up(N * sizeof(DfResult)), b_coff = up(N * 8);
+    void *d_plan, *d_tokens, *d_stage;
+    int rc;
+    if ((rc = ensure(ctx, WS_BZ_PLAN, 64 + 2 * b_cuts + b_members + 2 * b_m32 + b_chunks + b_res + b_coff, &d_plan))) return rc;
+    if ((rc = ensure(ctx, WS_BZ_TOKENS, (uint64_t)wgs * kDfChunk * 4, &d_tokens))) return rc;
+    if ((rc = ensure(ctx, WS_BZ_STAGE, N * kDfSlot, &d_stage))) return rc;
+    BgzfArgs a{};
+    uint8_t *p = (uint8_t *)d_plan;
+    const auto take = [&p](uint64_t b) {
+        uint8_t *q = p;
+        p += b;
+        return q;
+    };
+    a.counts = (uint64_t *)take(64);
+    a.cuts = (uint64_t *)take(b_cuts);
+    a.cell_first = (uint64_t *)take(b_cuts);
+    a.members = (BgzfMember *)take(b_members);
+    a.member_chunk = (uint32_t *)take(b_m32);
+    a.crcs = (uint32_t *)take(b_m32);
+    a.chunks = (DfChunkDesc *)take(b_chunks);
+    a.results = (DfResult *)take(b_res);
+    a.chunk_off = (uint64_t *)take(b_coff);
+    a.text = d_text;
+    a.n = n;
+    a.off = d_off;
+    a.n_rec = n_rec;
+    a.off_base = off_base;
+    a.n_cells = C;
+    a.tokens = (uint32_t *)d_tokens;
+    a.stage = (uint8_t *)d_stage;
+    a.out = d_out;
+    a.workgroups = wgs;
+    a.max_members = M;
+    a.max_chunks = N;
+    uint64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    launch_bgzf_plan(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(got, a.counts, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (got[0] > M || got[1] > N || got[1] < got[0] || got[2] != n)
+        return set_err(ctx, NTC_ERR_INVALID_ARG, "BGZF plan: the record offsets do not describe the text");
+    a.n_members = (uint32_t)got[0];
+    a.n_chunks = (uint32_t)got[1];
+    if (!a.n_members) return NTC_OK;
+    launch_bgzf_code(a, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    const size_t t0 = tab.size();
+    tab.resize(t0 + a.n_members);
+    HIP_TRY(ctx, hipMemcpyAsync(tab.data() + t0, a.members, a.n_members * sizeof(BgzfMember), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(got, a.counts, 7 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = t0; i < tab.size(); i++) tab[i].place += place_base;
+    for (int i = 0; i < 7; i++) counts[i] += got[i];
+    return NTC_OK;
+}
+
+// what both ntc_bgzf_compress calls refuse before anything runs (off on the host)
+int bgzf_check(ntc_ctx *ctx, uint64_t n, const uint64_t *off, uint64_t n_rec, uint64_t out_cap, uint64_t *out_bytes) {
+    if (off) {
+        if (off[0] != 0 || off[n_rec] != n) return set_err(ctx, NTC_ERR_INVALID_ARG, "record offsets must start at 0 and end at n");
+        for (uint64_t r = 0; r < n_rec; r++)
+            if (off[r] > off[r + 1]) return set_err(ctx, NTC_ERR_INVALID_ARG, "record offsets decrease at record " + std::to_string(r));
+    }
+    *out_bytes = bgzf_bound(n);
+    if (out_cap < bgzf_bound(n))
+        return set_err(ctx, NTC_ERR_CAPACITY, "BGZF output needs " + std::to_string(bgzf_bound(n)) + " bytes");
+    *out_bytes = 0;
+    return NTC_OK;
+}
+
+// the table to the caller: NTC_ERR_CAPACITY (with *n_members set) when it does not fit
+int bgzf_table_out(ntc_ctx *ctx, const std::vector<BgzfMember> &tab, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members) {
+    *n_members = tab.size();
+    if (!members) return NTC_OK;
+    if (tab.size() > members_cap) return set_err(ctx, NTC_ERR_CAPACITY, "member array too small");
+    if (!tab.empty()) std::memcpy(members, tab.data(), tab.size() * sizeof(BgzfMember));
+    return NTC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t ntc_bgzf_bound(uint64_t n) { return bgzf_bound(n); }
+
+int ntc_bgzf_compress(ntc_ctx *ctx, const uint8_t *text, uint64_t n, const uint64_t *rec_off, uint64_t n_rec, uint8_t *out,
+                      uint64_t out_cap, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members, uint64_t *out_bytes) {
+    if (!n_members || !out_bytes || (n && (!text || !out))) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_members = 0;
+    int rc;
+    if ((rc = bgzf_check(ctx, n, rec_off, n_rec, out_cap, out_bytes))) return rc;
+    std::vector<BgzfMember> tab;
+    uint64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (!ctx) {
+        bgzf_host(text, n, rec_off, n_rec, out, tab, counts);
+        *out_bytes = counts[3];
+        return bgzf_table_out(ctx, tab, members, members_cap, n_members);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->bz.begin();
+    const auto t_bz = std::chrono::steady_clock::now();
+    void *d_text, *d_off = nullptr, *d_out;
+    if ((rc = ensure(ctx, WS_BZ_TEXT, n + 16, &d_text))) return rc;
+    if ((rc = ensure(ctx, WS_BZ_OUT, bgzf_bound(n), &d_out))) return rc;
+    if (rec_off && (rc = ensure(ctx, WS_BZ_OFF, (n_rec + 1) * 8, &d_off))) return rc;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, ctx->stream));
+    if (rec_off) HIP_TRY(ctx, hipMemcpyAsync(d_off, rec_off, (n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's buffers are pageable: nothing reads them after the return)
+    if ((rc = bgzf_dev(ctx, (const uint8_t *)d_text, n, (const uint64_t *)d_off, n_rec, 0, (uint8_t *)d_out, 0, tab, counts))) return rc;
+    if ((rc = bgzf_table_out(ctx, tab, members, members_cap, n_members))) return rc;
+    if (counts[3]) HIP_TRY(ctx, hipMemcpy(out, d_out, counts[3], hipMemcpyDeviceToHost));
+    *out_bytes = counts[3];
+    std::copy(counts, counts + 7, ctx->bz.counts);
+    ctx->bz.members = std::move(tab);
+    ctx->bz.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bz).count();
+    return NTC_OK;
+}
+
+int ntc_bgzf_compress_device(ntc_ctx *ctx, const void *d_text, uint64_t n, const uint64_t *d_rec_off, uint64_t n_rec, void *d_out,
+                             uint64_t out_cap, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members,
+                             uint64_t *out_bytes) {
+    if (!ctx || !n_members || !out_bytes || (n && (!d_text || !d_out))) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    *n_members = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    std::vector<uint64_t> off;
+    if (d_rec_off) {  // the offsets are checked on the host, as ntc_bgzf_compress checks them
+        off.resize(n_rec + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(off.data(), d_rec_off, (n_rec + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if ((rc = bgzf_check(ctx, n, d_rec_off ? off.data() : nullptr, n_rec, out_cap, out_bytes))) return rc;
+    ctx->bz.begin();
+    const auto t_bz = std::chrono::steady_clock::now();
+    std::vector<BgzfMember> tab;
+    uint64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    if ((rc = bgzf_dev(ctx, (const uint8_t *)d_text, n, d_rec_off, n_rec, 0, (uint8_t *)d_out, 0, tab, counts))) return rc;
+    if ((rc = bgzf_table_out(ctx, tab, members, members_cap, n_members))) return rc;
+    *out_bytes = counts[3];
+    std::copy(counts, counts + 7, ctx->bz.counts);
+    ctx->bz.members = std::move(tab);
+    ctx->bz.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bz).count();
+    return NTC_OK;
+}
+
+int ntc_bgzf_last(ntc_ctx *ctx, ntc_bgzf_counts *counts, ntc_bgzf_member *members, uint64_t members_cap, uint64_t *n_members) {
+    if (!ctx || !counts || !n_members) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
+    const uint64_t *c = ctx->bz.counts;
+    *counts = ntc_bgzf_counts{c[0], c[2], c[3], c[4], c[5], c[6], ctx->bz.seconds};
+    return bgzf_table_out(ctx, ctx->bz.members, members, members_cap, n_members);
+}
+
+}  // extern "C"
+
 // The file pipeline's inflater (`--inflate gpu`, ntc_internal.h IHooks): one per encode call, on
 // the first context's device, used by the reader thread alone.  It owns a stream, grow-only
 // device buffers for a run's compressed bytes, descriptors, text and results, and a pinned
@@ -3157,6 +3348,10 @@ int sections_cover(ntc_ctx *ctx, const std::vector<Meta> &metas, uint64_t n_read
     return NTC_OK;
 }
 
+// option "bgzf_text": the room a text of `need` bytes asks of the caller's buffer (two parts under
+// the pair split: each may round its member count up once more)
+uint64_t bgzf_text_room(uint64_t need) { return bgzf_bound(need) + 2 * (uint64_t)kBgzfSlack; }
+
 // walk + FASTA text of records already in HBM (d_recs), text D2H into out (need bytes; with a
 // window w only the window's bytes, which *out_len then reports)
 int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint64_t n_reads, uint64_t n_bases,
@@ -3257,7 +3452,9 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
         const uint64_t got = box(ctx, kBoxWindow);
         *out_len = copy = std::min(need, got);
     }
-    if (!ctx->discard_text && copy) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, copy, hipMemcpyDeviceToHost, ctx->stream));
+    // option "bgzf_text": the text stays on the device, its members are copied in its place below
+    const bool bz = ctx->bz.opt && !ctx->discard_text;
+    if (!ctx->discard_text && !bz && copy) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, copy, hipMemcpyDeviceToHost, ctx->stream));
     uint64_t nr = 0, nb = 0;
     rc = ntc_decode_status(ctx, &nr, &nb);  // synchronises
     if (digests) rc = dgd_verdict(ctx, rc);
@@ -3265,6 +3462,26 @@ int decode_fasta_dev(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs, uint
     if (nr != n_reads || nb != n_bases)
         return set_err(ctx, NTC_ERR_FORMAT, "records hold other read / base counts than given");
     if (split) ctx->pair.first = box(ctx, kBoxPairFirst);
+    if (bz) {  // the status is clear, so the text and its offsets stand: plan and code it, each part on its own
+        BgzfState &B = ctx->bz;
+        const auto t_bz = std::chrono::steady_clock::now();
+        void *d_bz;
+        if ((rc = ensure(ctx, WS_BZ_OUT, bgzf_text_room(copy), &d_bz))) return rc;
+        const uint8_t *text = (const uint8_t *)d_out;
+        if (split) {
+            const uint64_t np = n_reads / 2, first = std::min(ctx->pair.first, copy);
+            const uint64_t *o1 = (const uint64_t *)d_pscan + 2 * (np + 1), *o2 = o1 + (np + 1);
+            if ((rc = bgzf_dev(ctx, text, first, o1, np, 0, (uint8_t *)d_bz, 0, B.members, B.counts))) return rc;
+            const uint64_t part1 = B.counts[3];
+            if ((rc = bgzf_dev(ctx, text + first, copy - first, o2, np, 0, (uint8_t *)d_bz + part1, part1, B.members, B.counts)))
+                return rc;
+            ctx->pair.first = part1;
+        } else if ((rc = bgzf_dev(ctx, text, copy, out_offs, n_reads, 0, (uint8_t *)d_bz, 0, B.members, B.counts)))
+            return rc;
+        if (B.counts[3]) HIP_TRY(ctx, hipMemcpy(out, d_bz, B.counts[3], hipMemcpyDeviceToHost));
+        *out_len = B.counts[3];
+        B.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bz).count();
+    }
     return NTC_OK;
 }
 }  // namespace
@@ -3307,14 +3524,18 @@ int ntc_decode_fasta(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint64
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->pair.mode && (n_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, n_reads, n_bases, first_id);
-    *out_len = need;
-    if (need > out_capacity && !ctx->discard_text) {
+    const bool bz = ctx->bz.opt && !ctx->discard_text;
+    if (ctx->bz.opt) ctx->bz.begin();
+    *out_len = bz ? bgzf_text_room(need) : need;
+    if (*out_len > out_capacity && !ctx->discard_text) {
         w.keep();  // (a size query: the window waits for the call it sizes)
-        return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+        return set_err(ctx, NTC_ERR_CAPACITY, bz ? "out_capacity smaller than the bound of the text's BGZF members"
+                                                 : "out_capacity smaller than the FASTA text");
     }
     ctx->pair.valid = ctx->pair.mode && !ctx->discard_text;  // (the parts stay empty unless the call succeeds)
     ctx->pair.first = 0;
     if (n_recs == 0) {
+        if (bz) *out_len = 0;
         if (const int wrc = w.check(n_reads)) return wrc;
         return n_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     }
@@ -3456,17 +3677,21 @@ int ntc_decode_fasta_unpacked(ntc_ctx *ctx, uint64_t first_id, uint8_t *out, uin
     if (!ctx->has_index) return set_err(ctx, NTC_ERR_NO_INDEX, "no index uploaded");
     if (ctx->pair.mode && (ctx->unp_reads & 1)) return set_err(ctx, NTC_ERR_FORMAT, "paired: an odd number of reads");
     const uint64_t need = text_bytes(ctx, ctx->unp_reads, ctx->unp_bases, first_id);
-    *out_len = need;  // (a size query: out_capacity 0)
+    const bool bz = ctx->bz.opt && !ctx->discard_text;
+    if (ctx->bz.opt) ctx->bz.begin();
+    *out_len = bz ? bgzf_text_room(need) : need;  // (a size query: out_capacity 0)
     if (!ctx->discard_text) {
-        if (need > out_capacity) {
+        if (*out_len > out_capacity) {
             w.keep();  // (the window waits for the call the query sizes)
-            return set_err(ctx, NTC_ERR_CAPACITY, "out_capacity smaller than the FASTA text");
+            return set_err(ctx, NTC_ERR_CAPACITY, bz ? "out_capacity smaller than the bound of the text's BGZF members"
+                                                     : "out_capacity smaller than the FASTA text");
         }
         if (need && !out) return set_err(ctx, NTC_ERR_INVALID_ARG, "null argument");
     }
     ctx->pair.valid = ctx->pair.mode && !ctx->discard_text;
     ctx->pair.first = 0;
     if (ctx->unp_recs == 0) {
+        if (bz) *out_len = 0;
         if (const int wrc = w.check(ctx->unp_reads)) return wrc;
         return ctx->unp_reads ? set_err(ctx, NTC_ERR_FORMAT, "reads without records") : NTC_OK;
     }
@@ -3932,6 +4157,11 @@ struct NxHookFill {
         ntc::g_d_hooks.set_discard = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "discard_text", on); };
         ntc::g_z_hooks.set_mode = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "gpu_deflate", on); };
         ntc::g_z_hooks.encode_members = ntc_encode_members;
+        ntc::g_b_hooks.set_mode = [](ntc_ctx *ctx, int on) { return ntc_ctx_set_option(ctx, "bgzf_text", on); };
+        ntc::g_b_hooks.last_counts = [](ntc_ctx *ctx, ntc_bgzf_counts *c) {
+            uint64_t n = 0;
+            return ntc_bgzf_last(ctx, c, nullptr, 0, &n);
+        };
         ntc::g_i_hooks.create = [](ntc_ctx *ctx, ntc::Inflater **out) {
             if (!ctx || !out) return (int)NTC_ERR_INVALID_ARG;
             *out = nullptr;

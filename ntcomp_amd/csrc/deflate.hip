@@ -86,4 +86,9 @@ void launch_deflate(const DfArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_df_place, dim3(a.n_chunks), dim3(256), 0, s, a);
 }
 
+void launch_deflate_place(const DfArgs &a, hipStream_t s) {
+    if (a.n_chunks == 0) return;
+    hipLaunchKernelGGL(k_df_place, dim3(a.n_chunks), dim3(256), 0, s, a);
+}
+
 }  // namespace ntc

@@ -453,6 +453,38 @@ struct DfArgs {
     uint8_t *out;
 };
 void launch_deflate(const DfArgs &a, hipStream_t s);
+// k_df_place alone: chunk c's results[c].size bytes from its slot of stage to out + chunk_off[c]
+// (the other fields are not read)
+void launch_deflate_place(const DfArgs &a, hipStream_t s);
+// BGZF members of a text in HBM (bgzf.hip, bgzf_core.h).  text: n bytes; off (null: plain cuts):
+// n_rec + 1 record offsets, off[r] - off_base being record r's start.  With C = bgzf_cells(n, off
+// != null), M = bgzf_members_max(n) and N = kBgzfMemberChunks M: cuts / cell_first: C + 1 words
+// each, members: M, member_chunk / crcs: M words, chunks / results: N, chunk_off: N words,
+// stage: N * kDfSlot bytes, tokens: workgroups * kDfChunk words, counts: 8 words (members,
+// chunks, text bytes, output bytes, chunks stored / Huffman / Huffman with matches), out:
+// bgzf_bound(n) bytes.  launch_bgzf_plan fills the descriptors and counts[0..2]; the caller reads
+// them, sets n_members and n_chunks, and launch_bgzf_code does the rest.
+struct BgzfMember;
+struct BgzfArgs {
+    const uint8_t *text;
+    uint64_t n;
+    const uint64_t *off;
+    uint64_t n_rec, off_base, n_cells;
+    uint64_t *cuts, *cell_first;
+    BgzfMember *members;
+    uint32_t *member_chunk, *crcs;
+    DfChunkDesc *chunks;
+    DfResult *results;
+    uint64_t *chunk_off;
+    uint8_t *stage;
+    uint32_t *tokens;
+    uint64_t *counts;
+    uint8_t *out;
+    uint64_t max_members, max_chunks;  // the tables' entries: the plan writes no descriptor when it counts more
+    uint32_t n_members, n_chunks, workgroups;
+};
+void launch_bgzf_plan(const BgzfArgs &a, hipStream_t s);
+void launch_bgzf_code(const BgzfArgs &a, hipStream_t s);
 // Inflate of gzip members (inflate.hip, inflate_core.h).  Member i is the src_bytes bytes at comp +
 // src_off and inflates to out_bytes bytes at dst + dst_off (ntc_inflate_member's layout); its
 // status, bytes and CRC-32 go to results[i].  Everything is device memory; the caller has checked

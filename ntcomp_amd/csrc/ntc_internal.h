@@ -96,6 +96,7 @@ struct ntc_qual_meta;
 struct ntc_name_meta;
 struct ntc_digest_meta;
 struct ntc_inflate_member;
+struct ntc_bgzf_counts;
 namespace ntc {
 // a plain FASTQ that ntc_fastx_open mapped: its bytes (null for any other input), and
 // moving the mapped parser to byte pos (a record start) -- pipeline.cpp's GPU-parse reader
@@ -186,6 +187,13 @@ struct ZHooks {
     int (*encode_members)(::ntc_ctx *ctx, uint64_t *member_off_len, uint64_t cap_blocks, uint64_t *n_blocks);
 };
 extern ZHooks g_z_hooks;
+// ... and for BGZF output: with the table null, ntc_decode_file_ex7 answers NTC_ERR_UNSUPPORTED to
+// out_format 1
+struct BHooks {
+    int (*set_mode)(::ntc_ctx *ctx, int on);  // ctx option "bgzf_text"
+    int (*last_counts)(::ntc_ctx *ctx, ::ntc_bgzf_counts *counts);  // ntc_bgzf_last, the counts alone
+};
+extern BHooks g_b_hooks;
 // ... and for `--inflate gpu`: an inflater lives on one device, with a stream, device buffers and a
 // pinned staging buffer of its own (capi.cpp), and inflates a run of BGZF members from host memory
 // into host memory (inflate.hip).  run: member i is m[i] of comp[0, comp_bytes) and goes to dst at

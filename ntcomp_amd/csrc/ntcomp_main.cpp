@@ -17,10 +17,11 @@
 //                 is interleaved; the archive alternates the mates, whose ids are checked on the GPU)
 //   ntcomp decode -i P [--gpus N | --devices ..] [--threads T] [--blocks-per-batch B] [--stats]
 //                 [--exceptions PATH] [--quality-file PATH] [--name-file PATH] [--digest-file PATH]
-//                 [--mate-out R2.out] FILE > out.fasta
+//                 [--mate-out R2.out] [--bgzf] FILE > out.fasta
 //                 (FASTQ with --quality-file, the reads' own names with --name-file; checked block by
 //                 block against the --digest-file; with --mate-out the archive holds pairs: the mate-1
-//                 records go to stdout, the mate-2 records to R2.out)
+//                 records go to stdout, the mate-2 records to R2.out; --bgzf: the text as BGZF, compressed
+//                 on the GPU, both outputs under --mate-out)
 //   ntcomp verify -i P --digest-file PATH [--exceptions PATH] [--quality-file PATH] [--name-file PATH]
 //                 FILE        (decode without the text: one line on stdout, status 0 iff every block matched)
 #include <dlfcn.h>
@@ -91,7 +92,7 @@ bool takes_value(const std::string &o) {
 }
 
 bool is_switch(const std::string &o) {
-    static const char *v[] = {"-d", "--dedup-batches", "--verbose", "--stats", "--host-parse", "--interleaved", "--blocks"};
+    static const char *v[] = {"-d", "--dedup-batches", "--verbose", "--stats", "--host-parse", "--interleaved", "--blocks", "--bgzf"};
     for (const char *x : v)
         if (o == x) return true;
     return false;
@@ -580,12 +581,21 @@ int cmd_decode(const Args &a, bool verify = false) {
     const std::string mate_out = a.get("--mate-out", nullptr, "");
     if (verify && a.flag("--mate-out")) bad_args("verify: writes no text: not with --mate-out");
     if (a.flag("--mate-out") && mate_out.empty()) bad_args("decode: --mate-out needs a path");
+    // the text as BGZF members, compressed on the GPU that formatted it
+    const bool bgzf = a.flag("--bgzf");
+    if (verify && bgzf) bad_args("verify: writes no text: not with --bgzf");
     const RangeAsk ask = range_args(a, cmd);
     if (prefix.empty()) die(std::string(cmd) + ": -i/--index is required");
     const bool ranged = ask.reads || ask.shard;
     uint64_t r_first = 0, r_count = 0;
     if (ranged && !place_range(ask, a, cmd, &r_first, &r_count)) {  // an empty slice: nothing to write
         if (verify) std::printf("verify: OK: 0 blocks of the archive's, 0 reads (--shard %s is empty)\n", ask.spec.c_str());
+        if (bgzf) {  // an empty BGZF file is its EOF member
+            const int fde = mate_out.empty() ? -1 : ::open(mate_out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (::write(1, NTC_BGZF_EOF, NTC_BGZF_EOF_BYTES) != NTC_BGZF_EOF_BYTES ||
+                (!mate_out.empty() && (fde < 0 || ::write(fde, NTC_BGZF_EOF, NTC_BGZF_EOF_BYTES) != NTC_BGZF_EOF_BYTES || ::close(fde) != 0)))
+                die("decode: cannot write the output");
+        }
         return 0;
     }
     ntc_index_host *ix = nullptr;
@@ -616,8 +626,12 @@ int cmd_decode(const Args &a, bool verify = false) {
     const ntc_file_opts5 fo5{(uint32_t)sizeof(ntc_file_opts5), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1, fo3.n_path, 0, -1,
                              fo4.d_path, fd2 >= 0 ? 2 : 0, nullptr, fd2, r_first, r_count};
     ntc_r_stats rst{};
+    const ntc_file_opts7 fo7{(uint32_t)sizeof(ntc_file_opts7), 0, -1, 0, -1, fo.nx_path, fo2.q_path, 0, -1, fo3.n_path, 0, -1,
+                             fo4.d_path, fd2 >= 0 ? 2 : 0, nullptr, fd2, r_first, r_count, 0, 0, NTC_OUT_BGZF, 0};
+    ntc_z_stats zst{};
     std::fflush(stdout);
-    const int rc = ranged ? ntc_decode_file_ex5(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo5, &o, &st, &dst, &pst, &rst)
+    const int rc = bgzf ? ntc_decode_file_ex7(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo7, &o, &st, &dst, &pst, &rst, &zst)
+                   : ranged ? ntc_decode_file_ex5(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo5, &o, &st, &dst, &pst, &rst)
                    : fd2 >= 0 ? ntc_decode_file_ex4(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo4, &o, &st, &dst, &pst)
                    : !d_path.empty() ? ntc_decode_file_ex3(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), verify ? -1 : 1, &fo3, &o, &st, &dst)
                    : !n_path.empty() ? ntc_decode_file_ex2(ctxs.data(), (int)ctxs.size(), a.pos[0].c_str(), 1, &fo2, &o, &st)
@@ -640,7 +654,7 @@ int cmd_decode(const Args &a, bool verify = false) {
                     component_names((dst.blocks_seq ? 1u : 0) | (dst.blocks_sym ? 2u : 0) | (dst.blocks_qual ? 4u : 0) |
                                     (dst.blocks_name ? 8u : 0)).c_str(),
                     component_names(dst.not_checkable).c_str());
-    char djson[960] = "";
+    char djson[1400] = "";
     if (fd2 >= 0)
         std::snprintf(djson, 240, "\"pairs\": %llu, \"mate1_bytes\": %llu, \"mate2_bytes\": %llu, ",
                       (unsigned long long)pst.pairs, (unsigned long long)pst.bytes1, (unsigned long long)pst.bytes2);
@@ -657,6 +671,13 @@ int cmd_decode(const Args &a, bool verify = false) {
                       (unsigned long long)rst.blocks_total, (unsigned long long)rst.reads_total, (unsigned long long)rst.first_block,
                       (unsigned long long)rst.blocks_read, (unsigned long long)rst.reads_written,
                       (unsigned long long)rst.head_skipped, (unsigned long long)rst.tail_skipped);
+    if (!verify)
+        std::snprintf(djson + std::strlen(djson), 400, "\"bgzf\": %s, \"bgzf_members\": %llu, \"bgzf_text_bytes\": %llu, "
+                                            "\"bgzf_bytes\": %llu, \"bgzf_chunks_stored\": %llu, \"bgzf_chunks_huffman\": %llu, "
+                                            "\"bgzf_chunks_matches\": %llu, \"bgzf_s\": %.3f, ",
+                      bgzf ? "true" : "false", (unsigned long long)zst.members, (unsigned long long)zst.text_bytes,
+                      (unsigned long long)zst.bytes, (unsigned long long)zst.chunks_stored, (unsigned long long)zst.chunks_huffman,
+                      (unsigned long long)zst.chunks_matches, zst.seconds);
     if (st.dropped_blocks)  // the reference's `while let Ok(..) = decode_block` just ends here (main.rs:202)
         std::fprintf(stderr, "warning: %s; %llu block(s) not decoded\n", st.error,
                      (unsigned long long)st.dropped_blocks);
@@ -776,7 +797,7 @@ void usage(FILE *f) {
                  "                     [--deflate auto|zlib|libdeflate|adaptive|gpu] FILE > encoded.dat\n"
                  "                     [--mate-file R2 | --interleaved] [--mate-check ids|off] [--inflate host|gpu]\n"
                  "       ntcomp decode -i PREFIX [--exceptions PATH] [--quality-file PATH] [--name-file PATH]\n"
-                 "                     [--digest-file PATH] [--mate-out R2.out] [--reads A-B | --shard I/N]\n"
+                 "                     [--digest-file PATH] [--mate-out R2.out] [--reads A-B | --shard I/N] [--bgzf]\n"
                  "                     FILE > out.fasta\n"
                  "       ntcomp verify -i PREFIX --digest-file PATH [--exceptions PATH] [--quality-file PATH]\n"
                  "                     [--name-file PATH] [--reads A-B | --shard I/N] FILE\n"
@@ -824,6 +845,9 @@ void usage(FILE *f) {
                  "                     the reads keep their numbers, names and qualities\n"
                  "  --shard I/N        decode, verify: only the I-th of N contiguous slices of whole blocks; the N outputs\n"
                  "                     concatenated in order are the full decode (one process per GPU or node)\n"
+                 "  --bgzf             decode: write the text as BGZF (.gz: bgzip's blocked gzip), cut at record boundaries and\n"
+                 "                     compressed on the GPU; with --mate-out both outputs.  The EOF member is written only when\n"
+                 "                     the decode succeeds; the --shard outputs concatenated are one BGZF file\n"
                  "  --blocks           info: one line per block\n");
 }
 

@@ -54,14 +54,15 @@
 #include "../../include/ntcomp_host.h"
 #include "../../include/ntcomp_pipeline.h"
 #include "ntc_internal.h"
+#include "bgzf_core.h"
 #include "digest_core.h"
 
 namespace ntc {
 namespace pipe {
 
-// Everything the thirteen entry points (ntc_{en,de}code_file, _nx, _ex, _ex2, _ex3, _ex4 and
-// ntc_decode_file_ex5) can say.  An entry point that lacks a field leaves it at its "none"
-// value: mode 0, descriptor -1, path null.
+// Everything the entry points (ntc_{en,de}code_file, _nx, _ex, _ex2, _ex3, _ex4,
+// ntc_decode_file_ex5, ntc_encode_file_ex6 and ntc_decode_file_ex7) can say.  An entry point
+// that lacks a field leaves it at its "none" value: mode 0, descriptor -1, path null.
 struct FileJob {
     ntc_ctx *const *ctxs;
     int n_ctx;
@@ -75,6 +76,7 @@ struct FileJob {
     bool may_discard = false;  // decode _ex3 / _ex4: out_fd -1 runs everything but the text's copy and write
     uint64_t read_first = 0, read_count = 0;  // decode _ex5: the range of reads, count 0 = the whole file
     int inflate_engine = 0;                   // encode _ex6: NTC_INFLATE_*
+    int out_format = 0;                       // decode _ex7: NTC_OUT_*
     FileJob(ntc_ctx *const *c, int n, const char *in, int out, const ntc_pipeline_opts *o)
         : ctxs(c), n_ctx(n), in_path(in), out_fd(out), opts(o) {}
     // the fields of ntc_file_opts, ntc_file_opts2 and ntc_file_opts3 (the same names in each)
@@ -105,6 +107,7 @@ struct FileStats {
     ntc_p_stats *p = nullptr;
     ntc_r_stats *r = nullptr;
     ntc_i_stats *i = nullptr;
+    ntc_z_stats *z = nullptr;
 };
 int encode_file(const FileJob &job, const FileStats &out);
 int decode_file(const FileJob &job, const FileStats &out);
@@ -189,6 +192,7 @@ PHooks g_p_hooks = {nullptr, nullptr, nullptr};
 WHooks g_w_hooks = {nullptr};
 ZHooks g_z_hooks = {nullptr, nullptr};
 IHooks g_i_hooks = {nullptr, nullptr, nullptr};
+BHooks g_b_hooks = {nullptr, nullptr};
 }
 
 namespace {
@@ -1696,6 +1700,7 @@ struct Decoder {
     const int out_fd, out_fd2, pair_mode;
     const bool discard;  // out_fd -1: everything but the copy of the text off the device and its write
     const bool split;    // pairs: each batch's text comes back in two parts
+    const bool bgzf;     // NTC_OUT_BGZF: each batch's text comes back as BGZF members (each part's, under pairs)
     SideFile<ntc_nx_run> nxf;  // the exception runs; each batch finds its own by its first read (put_runs)
     uint32_t nx_sub = 0;
     SideFile<ntc_qual_meta> qf;
@@ -1723,13 +1728,14 @@ struct Decoder {
     ntc_pipeline_stats S{};
     ntc_d_stats DS{};
     ntc_p_stats PS{};  // the writer's
+    ntc_z_stats ZS{};  // the members of the batches decoded (under sh.mu)
     off_t out_pos = 0;
     bool seekable = false;
     std::atomic<double> t_unzip{0}, t_gpu{0}, t_write{0}, t_pin{0};
 
     Decoder(const FileJob &job, bool discard_)
         : ctxs(job.ctxs), n_ctx(job.n_ctx), out_fd(job.out_fd), out_fd2(job.fo.out_fd2), pair_mode(job.fo.pair_mode),
-          discard(discard_), split(job.fo.pair_mode && !discard_) {}
+          discard(discard_), split(job.fo.pair_mode && !discard_), bgzf(job.out_format == NTC_OUT_BGZF && !discard_) {}
 
     uint64_t batch_first(uint64_t b) const { return b == 0 ? 0 : b0n + (b - 1) * bpb; }
     uint64_t batch_of(uint64_t blk) const { return blk < b0n ? 0 : 1 + (blk - b0n) / bpb; }
@@ -1985,7 +1991,8 @@ bool Decoder::decode_batch(int c, uint64_t b, DSlot &sl, uint64_t nb, std::vecto
     const uint64_t need = sl.n_bases * (1 + q_per_base) + (7 + q_per_read) * sl.n_reads +
                           digits_total(sl.first_id, sl.n_reads) + name_room(blk_base + sl.first_block, nb) + 64;
     const auto tg = Clock::now();
-    if (!discard && !ensure_pinned((void **)&sl.text, &sl.cap_text, need)) {
+    // (BGZF: the bound of the members of that much text, in up to two parts)
+    if (!discard && !ensure_pinned((void **)&sl.text, &sl.cap_text, bgzf ? ntc::bgzf_bound(need) + 2 * ntc::kBgzfSlack : need)) {
         sh.fail(NTC_ERR_HIP, "pinned host allocation failed");
         return false;
     }
@@ -2049,7 +2056,12 @@ bool Decoder::decode_batch(int c, uint64_t b, DSlot &sl, uint64_t nb, std::vecto
     }
     uint64_t first = 0;
     if (split && ntc::g_p_hooks.pair_split(ctx, &first)) return fail_ctx(NTC_ERR_FORMAT, c);
+    ntc_bgzf_counts zc{};
+    if (bgzf && ntc::g_b_hooks.last_counts(ctx, &zc)) return fail_ctx(NTC_ERR_HIP, c);
     std::lock_guard<std::mutex> g(sh.mu);
+    ZS.members += zc.members, ZS.text_bytes += zc.text_bytes, ZS.bytes += zc.bytes;
+    ZS.chunks_stored += zc.chunks_stored, ZS.chunks_huffman += zc.chunks_huffman, ZS.chunks_matches += zc.chunks_matches;
+    ZS.seconds += zc.seconds;
     {
         std::string unused;
         int64_t bad = -1;
@@ -2075,6 +2087,8 @@ void Decoder::run_gpu(int c) {
     if (discard_guard.rc()) return (void)fail_ctx(NTC_ERR_HIP, c);
     ModeGuard pairs_guard(ntc::g_p_hooks.set_mode, ctxs + c, split ? 1 : 0, pair_mode);
     if (pairs_guard.rc()) return (void)fail_ctx(NTC_ERR_HIP, c);
+    ModeGuard bgzf_guard(ntc::g_b_hooks.set_mode, ctxs + c, bgzf ? 1 : 0, 1);
+    if (bgzf_guard.rc()) return (void)fail_ctx(NTC_ERR_HIP, c);
     std::vector<ntc_nx_run> nx_tmp;  // a batch's exception runs, renumbered from its first read
     std::vector<ntc_qual_meta> q_tmp;  // ... and its quality sections
     std::vector<ntc_name_meta> n_tmp;  // ... and its name sections
@@ -2298,9 +2312,12 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
     if (pair_mode < 0 || pair_mode > 2 || (pair_mode ? out_fd2 < 0 && !discard : out_fd2 != -1)) return NTC_ERR_INVALID_ARG;
     const ntc::PHooks &ph = ntc::g_p_hooks;
     if (pair_mode && (!ph.set_mode || !ph.pair_split)) return NTC_ERR_UNSUPPORTED;
+    if (job.out_format != NTC_OUT_TEXT && job.out_format != NTC_OUT_BGZF) return NTC_ERR_INVALID_ARG;
+    if (job.out_format == NTC_OUT_BGZF && (!ntc::g_b_hooks.set_mode || !ntc::g_b_hooks.last_counts)) return NTC_ERR_UNSUPPORTED;
     for (int i = 0; i < n_ctx; i++)
         if (!ctxs[i]) return NTC_ERR_INVALID_ARG;
     Decoder D(job, discard);
+    D.ZS.out_format = (uint32_t)job.out_format;
     D.PS.mode = (uint32_t)pair_mode;
     // the side files, each read once
     if ((D.nxf.loaded = nx_path != nullptr)) {
@@ -2410,7 +2427,6 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
         pinned_free(sl.text);
     }
     if (D.data) munmap((void *)D.data, fsize);
-    if (D.seekable) (void)lseek(out_fd, D.out_pos, SEEK_SET);
     int result = sh.error == -1 ? NTC_OK : sh.error;
     const int64_t stop_batch = D.stop_batch;
     char damaged[120];
@@ -2435,6 +2451,22 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
     wrong(d_path && !D.ranged && !clean_end, "truncated input: the file ends inside a block");
     wrong(d_path && D.df.n != total_blocks,
           "digests: more sections than blocks (the input is truncated, or the side file belongs to another encoding)");
+    // BGZF: the EOF member ends each output of a call that succeeded, and only of such a call
+    if (D.bgzf && result == NTC_OK) {
+        const uint8_t *eof = ntc::kBgzfEof;
+        const uint64_t ne = sizeof(ntc::kBgzfEof);
+        const bool ok1 = D.seekable ? ::pwrite(out_fd, eof, ne, D.out_pos) == (ssize_t)ne : write_fd(out_fd, eof, ne);
+        const bool ok2 = !D.split || write_fd(out_fd2, eof, ne);
+        if (!ok1 || !ok2) {
+            result = NTC_ERR_IO;
+            sh.msg = "write failed";
+        } else {
+            D.out_pos += (off_t)ne;
+            S.bytes_out += ne * (D.split ? 2 : 1);
+            if (D.split) D.PS.bytes1 += ne, D.PS.bytes2 += ne;
+        }
+    }
+    if (D.seekable) (void)lseek(out_fd, D.out_pos, SEEK_SET);
     S.dropped_blocks = blocks.size() - S.blocks;  // after a damaged block (or none)
     S.alloc_s += D.t_pin.load();
     S.parse_s = D.t_unzip.load();
@@ -2446,6 +2478,7 @@ int ntc::pipe::decode_file(const FileJob &job, const FileStats &stats) {
     if (stats.d) *stats.d = D.DS;
     if (pair_mode && discard) D.PS.pairs = S.reads / 2;
     if (stats.p) *stats.p = D.PS;
+    if (stats.z) *stats.z = D.ZS;
     R.first_block = D.blk_base;
     R.blocks_read = S.blocks;
     R.reads_written = S.reads;
@@ -2523,6 +2556,21 @@ int ntc_decode_file_ex5(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, in
     job.read_first = fo->read_first, job.read_count = fo->read_count;
     FileStats out{stats};
     out.d = d, out.p = p, out.r = r;
+    return decode_file(job, out);
+}
+
+int ntc_decode_file_ex7(ntc_ctx *const *ctxs, int n_ctx, const char *in_path, int out_fd, const ntc_file_opts7 *fo,
+                        const ntc_pipeline_opts *opts, ntc_pipeline_stats *stats, ntc_d_stats *d, ntc_p_stats *p,
+                        ntc_r_stats *r, ntc_z_stats *z) {
+    if (!fo || fo->struct_bytes < sizeof(ntc_file_opts7) || fo->reserved2) return NTC_ERR_INVALID_ARG;
+    FileJob job(ctxs, n_ctx, in_path, out_fd, opts);
+    job.take_ex3(*fo);
+    job.fo.pair_mode = fo->pair_mode, job.fo.mate_path = fo->mate_path, job.fo.out_fd2 = fo->out_fd2;
+    job.may_discard = true;
+    job.read_first = fo->read_first, job.read_count = fo->read_count;
+    job.out_format = fo->out_format;
+    FileStats out{stats};
+    out.d = d, out.p = p, out.r = r, out.z = z;
     return decode_file(job, out);
 }
 
