@@ -185,7 +185,12 @@ int ntc_encode_batch(ntc_ctx *ctx, const uint8_t *bases, const uint64_t *read_of
  * by need: when a call runs out of an overflow pool (reads with many entries or
  * records), ntc_encode_status grows the pools and runs the call again on the same
  * buffers, so d_bases, d_read_offsets and the outputs must stay valid and unchanged until
- * ntc_encode_status returns (option "spill_reruns" counts such re-runs).              */
+ * ntc_encode_status returns (option "spill_reruns" counts such re-runs).
+ * Per-call limit: fewer than 2^38 bases (with max_read_len > 0: n_reads * max_read_len <
+ * 2^38); at or past it the call returns NTC_ERR_CAPACITY ("split the batch") before anything
+ * is launched.  Positions are 64-bit throughout: one call over more than 2^32 bases, and
+ * offsets that start past 2^32, give the records of the same reads encoded apart
+ * (tests/test_gpu_big_batch.py).                                                       */
 int ntc_encode_batch_device(ntc_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_read_offsets,
                             uint64_t n_reads, uint32_t max_read_len, uint64_t *d_rec_out,
                             uint64_t rec_capacity, uint64_t *d_rec_offsets_out);
@@ -199,7 +204,10 @@ int ntc_encode_status(ntc_ctx *ctx, int64_t *bad_read, uint64_t *n_records);
 int ntc_decode_batch(ntc_ctx *ctx, const uint64_t *recs, uint64_t n_recs, uint8_t *bases_out,
                      uint64_t bases_capacity, uint64_t *read_offsets_out,
                      uint64_t offsets_capacity, uint64_t *n_reads_out, uint64_t *n_bases_out);
-/* Device variant; asynchronous; verdict + sizes via ntc_decode_status().             */
+/* Device variant; asynchronous; verdict + sizes via ntc_decode_status().  No per-call limit
+ * but the capacities given: output offsets are 64-bit, and one call that decodes more than
+ * 2^32 bases is tested (tests/test_gpu_big_batch.py); ntc_decode_fasta inherits that for the
+ * bases and for a text of more than 2^32 bytes.                                         */
 int ntc_decode_batch_device(ntc_ctx *ctx, const uint64_t *d_recs, uint64_t n_recs,
                             uint8_t *d_bases_out, uint64_t bases_capacity,
                             uint64_t *d_read_offsets_out, uint64_t offsets_capacity);

@@ -860,6 +860,9 @@ __global__ __launch_bounds__(256) void k_walk_final(const WalkStep *w48, const W
 constexpr int kScanThreads = 256;
 constexpr int kScanItems = 16;
 constexpr uint64_t kScanTile = (uint64_t)kScanThreads * kScanItems;
+// tests/big_batch_lib.py restates the tile (SCAN_TILE) to drive the scan at kScanTile^2 items, its
+// largest two-level run, and one past it: a change of tile size moves those cases with it
+static_assert(kScanTile == 4096, "tests/big_batch_lib.py SCAN_TILE holds the scan's level edges");
 
 __device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int o) {
     uint32_t lo = __shfl_up((uint32_t)v, o, 64), hi = __shfl_up((uint32_t)(v >> 32), o, 64);
